@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- RANSAC votings/s of the HIP voting layer on synthetic 480x640 fields (BASELINE.json configs[2]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,17 +12,25 @@ A "step" is one pass of the whole voting path (mask + 9-key-point vector field -
 synthetic images per GPU, inputs resident in HBM.  The timed mode is the library's DEFAULT: exact mode -- matrix-pipe scoring
 whose inlier counts and winners EQUAL the reference kernels' (pvnet_vote.h, PVNET_F_LITERAL / PVNET_F_APPROX).
 The timed region -- barrier + synchronise, EXACTLY K steps, synchronise [each rank's clock stops when ITS K steps and its
-last gather are done] + barrier, MAX of the ranks' times -- is run --regions
-times (default 15) and the MEDIAN region is reported as `value` / `ms_per_step` (a region of 20 steps lasts ~3 ms: one late
-stream moves a single region by several per cent); `regions` carries every region's rate, min, max and spread, and the
-GPU's clock and package power sampled while the regions ran.  Steps are independent batches, so they are issued round-robin on
---streams HIP streams (default 6); `single_stream` in the output is the same K steps issued strictly one after the
-other (the per-batch latency a caller with ONE frame in flight sees).  With N > 1 every rank votes its own 32 images
-(weak scaling, no data-path collective) and its key-points leave through the path's one real exchange, an RCCL
-all-gather of [32, 9, 2] per step -- bucketed: the key-points of --gather-bucket consecutive steps (default: one per
+last gather are done] + barrier, MAX of the ranks' times -- gives `value` / `ms_per_step`.
+
+Steps are independent batches, so they are issued round-robin on --streams HIP streams (default 6).  With N > 1 every rank
+votes its own 32 images (weak scaling, no data-path collective) and its key-points leave through the path's one real exchange,
+an RCCL all-gather of [32, 9, 2] per step -- bucketed: the key-points of --gather-bucket consecutive steps (default: one per
 stream) are voted straight into a staging block and travel in ONE collective.  Rank 0 prints ONE JSON line.
 
-Besides the contract's fields the line carries
+A plain run does only what that headline needs: inputs, a short time-bounded pre-warm (--prewarm-seconds), W warm-up steps
+(for K < 200 also twelve unrecorded regions of the timed form), ONE timed region of exactly K steps, the outputs
+(--dump-outputs DIR: the key-points rank 0's last timed step returned, DIR/keypoints.npy, float32 [32, 9, 2]; step i always
+votes input set i % buffers with seed SEED0 + i, so equal arguments give equal inputs) and the JSON line.
+
+Everything else is --full's: there the timed region is run --regions times (default 15, after unrecorded regions of the
+same form) and the MEDIAN region is reported as `value` / `ms_per_step` (a region of 20 steps lasts ~3 ms: one late stream
+moves a single region by several per cent); `regions` carries every region's rate, min, max and spread, and the GPU's clock
+and package power sampled while the regions ran; `single_stream` is the same K steps issued strictly one after the other (the
+per-batch latency a caller with ONE frame in flight sees).
+
+Besides the contract's fields the line of a --full run carries
   roofline      the dominant kernel (inlier scoring, score_exact_kernel), compute bound.  Its duration is
                 measured live over >= 200 launches on the op's stream (pvnet_vote_v3_stage_repeat): every workgroup
                 stamps the device's constant-rate clock, max end - min start per launch = what a kernel trace reports
@@ -99,9 +107,15 @@ def parse(argv=None):
                     help="untimed steps issued before the W warmup steps so that short runs do not measure the GPU's "
                          "clock ramp from idle (a step is ~0.12 ms: K=20 alone is a 2.4 ms burst)")
     ap.add_argument("--radius", type=int, default=40, help="disk radius of the synthetic object mask (tn ~ pi r^2)")
-    ap.add_argument("--regions", type=int, default=15,
+    ap.add_argument("--regions", type=int, default=None,
                     help="how many times the timed K-step region is run; the MEDIAN region is reported (min / max / every "
-                         "region's rate alongside)")
+                         "region's rate alongside).  Default: 1 in a plain run, 15 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated and unrecorded regions, single-stream, approximate and literal "
+                         "mode, per-stage times, the roofline, the parity check, the secondary configurations and the CPU "
+                         "baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the key-points the last timed step returned (rank 0) to DIR/keypoints.npy (float32)")
     ap.add_argument("--buffers", type=int, default=4,
                     help="distinct input sets cycled: the TOUCHED bytes of a set are its masks (78.6 MB) + its foreground "
                          "vectors (~11.6 MB), so 4 sets = 361 MB exceed the 256 MiB Infinity Cache")
@@ -127,7 +141,16 @@ def parse(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="TEST ONLY (tests/test_bench_contract.py): gloo on CPU with a stub voter, to exercise the "
                          "launcher / process-group / gather plumbing without a GPU; the line says so and is no measurement")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.regions is None:
+        a.regions = 15 if a.full else 1
+    return a
+
+
+def dump_outputs(directory, keypoints):
+    """--dump-outputs: what a caller of the timed path received from its last step, as float32 .npy"""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "keypoints.npy"), np.ascontiguousarray(keypoints, dtype=np.float32))
 
 
 # ------------------------------------------------------------------------------------------------------- launcher
@@ -150,11 +173,26 @@ def self_launch(argv):
 
 
 # --------------------------------------------------------------------------------------------------------- inputs
+def host_batch(first_index, radius, noisy, pool=None):
+    """synth.make_batch(BATCH, first_index, ...) -- every image from its own seeded generator (synth.make_image) -- with the
+    images generated on the threads of `pool` (numpy releases the GIL in its bulk work): the same arrays, sooner"""
+    kw = dict(h=H, w=W, vn=VN, radius=radius, noise=noisy, background="normal" if noisy else "zeros")
+    mask = np.empty((BATCH, H, W), np.int64)
+    planar = np.empty((BATCH, 2 * VN, H, W), np.float32)
+
+    def one(i):
+        mask[i], planar[i], _ = synth.make_image(first_index + i, **kw)
+
+    list(pool.map(one, range(BATCH)) if pool is not None else map(one, range(BATCH)))
+    return mask, planar
+
+
 def make_inputs(rank, nbuf, radius, noisy, dev):
+    from concurrent.futures import ThreadPoolExecutor
     sets = []
-    for s in range(nbuf):
-        mask, planar, _ = synth.make_batch(BATCH, first_index=(rank * nbuf + s) * BATCH, h=H, w=W, vn=VN,
-                                           radius=radius, noise=noisy, background="normal" if noisy else "zeros")
+    with ThreadPoolExecutor(max_workers=max(1, min(16, usable_cores()))) as pool:
+        host = [host_batch((rank * nbuf + s) * BATCH, radius, noisy, pool) for s in range(nbuf)]
+    for mask, planar in host:
         m = torch.from_numpy(mask).to(dev)  # int64, as torch.argmax delivers it (tools/demo.py:52)
         p = torch.from_numpy(planar).to(dev)  # [b, 2vn, h, w] planar, as the backbone emits it
         sets.append((m, synth.planar_to_vertex_view(p), mask, planar))
@@ -753,6 +791,8 @@ def main(argv=None):
         torch.cuda.synchronize(dev)
         return t
 
+    last = {}
+
     def timed(ns, steps=None, mode=None, **kw):
         """ONE timed region: warm-up, fence, exactly `steps` steps, fence; max over ranks"""
         steps = a.steps if steps is None else steps
@@ -760,9 +800,11 @@ def main(argv=None):
             step(i, ns, mode, **kw)
         fence()
         t0 = time.perf_counter()
+        out = None
         for i in range(steps):
-            step(i, ns, mode, **kw)
+            out = step(i, ns, mode, **kw)
         dt_local = fence() - t0
+        last["keypoints"] = out   # what the region's last step returned (--dump-outputs)
         dt = dt_local
         if dist is not None:
             t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -778,6 +820,39 @@ def main(argv=None):
         xs = sorted(xs)
         k = len(xs) // 2
         return xs[k] if len(xs) % 2 else 0.5 * (xs[k - 1] + xs[k])
+
+    def headline(dt, rates):
+        """the line's fields of every run: the headline (median region, max over ranks) and what it was taken on"""
+        votings_per_s = world * BATCH * a.steps / dt
+        return {
+            "metric": "RANSAC votings/s (480x640, 9 kpts, batch 32) + HBM GB/s vs roofline",
+            "value": votings_per_s, "unit": "votings/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "full": a.full,
+            "regions": {"runs": len(rates), "reported": "median", "min": min(rates), "max": max(rates),
+                        "spread": (max(rates) - min(rates)) / votings_per_s, "values": rates},
+            "mode": "APPROX (--approx, development A/B only)" if a.approx else
+                    "exact (library default): inlier counts and winners equal the reference kernels'",
+            "per_rank_votings_per_s": per_rank,
+            "gather_bucket_steps": G if dist is not None else None,
+            "gather_stream": (("the voting stream that filled the bucket (the library's ncclAllGather, pvnet_vote_allgather)" if rg is not None
+                               else "a voting stream (BENCH_GATHER_ON_VOTING_STREAM=1)" if GATHER_ON_VOTE else "its own stream")
+                              if dist is not None else None),
+            "gather_fallback": gather_fallback,
+            "dtype": "f32 decisions (bf16x3 MFMA products, f32 accumulate; pairs inside the f32 rounding band re-evaluated "
+                     "in the reference's f32 order); refinement f64",
+            "data": "synthetic",
+            "config": {"workload": "BASELINE.json configs[2]: batch=32 synthetic 480x640 fields per GPU, 9 keypoints, "
+                                   "1024 hypotheses, inlier_thresh 0.99, int64 mask, planar strided field",
+                       "batch_per_gpu": BATCH, "global_batch": world * BATCH, "h": H, "w": W, "vn": VN, "hn": HN,
+                       "mask_radius": a.radius,
+                       "field": "clean" if a.clean else "noisy (0.05 rad + 10% outliers), N(0,1) background",
+                       "input_sets_cycled": len(sets),
+                       "streams": nstreams, "prewarm_s": a.prewarm_seconds,
+                       "parallelism": f"images sharded over {world} GPU(s); steps issued round-robin on {nstreams} "
+                                      f"HIP stream(s) per GPU"},
+            "kernel_source_hash": source_hash(),
+        }
 
     MAIN = {"approx": True} if a.approx else {}
     t_pre = time.perf_counter()                      # device pre-warm (untimed, reported in config.prewarm_s)
@@ -799,18 +874,23 @@ def main(argv=None):
     # (the sensor thread is created and started BEFORE the unrecorded regions -- r04c39: whatever its start disturbs, the
     # regions right after it were 5 % low although the unrecorded ones before it had settled -- and its samples are cleared
     # when the recorded regions begin)
-    with GpuSampler(local) as sampler:
-        pre = regions(nstreams, mode=MAIN, n=int(os.environ.get("BENCH_UNRECORDED", "12")) if a.steps < 200 else 1)
-        pre_rates = [world * BATCH * a.steps / r[0] for r in pre]   # (in the line, not only on stderr)
-        sampler.samples.clear()
-        runs = regions(nstreams, mode=MAIN)          # the headline: R regions of K steps, independent batches on S streams
+    # (a plain run times ONE region; before it, short regions (K < 200) get the same unrecorded regions as --full -- 12 x (W + K)
+    #  steps, a fraction of a second -- long ones only the pre-warm and their W warm-up steps; the sensor thread is --full's)
+    if a.full:
+        with GpuSampler(local) as sampler:
+            pre = regions(nstreams, mode=MAIN, n=int(os.environ.get("BENCH_UNRECORDED", "12")) if a.steps < 200 else 1)
+            pre_rates = [world * BATCH * a.steps / r[0] for r in pre]   # (in the line, not only on stderr)
+            sampler.samples.clear()
+            runs = regions(nstreams, mode=MAIN)      # the headline: R regions of K steps, independent batches on S streams
+    else:
+        if a.steps < 200:
+            regions(nstreams, mode=MAIN, n=int(os.environ.get("BENCH_UNRECORDED", "12")))
+        runs = regions(nstreams, mode=MAIN)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last["keypoints"].cpu().numpy())
     dts = [r[0] for r in runs]
     dt = median(dts)
     dt_local = median([r[1] for r in runs])
-    runs1 = regions(1, mode=MAIN, n=max(3, a.regions // 3)) if nstreams > 1 else runs  # the same K steps one after the other
-    dt1 = median([r[0] for r in runs1])
-    runs_apx = regions(nstreams, mode={"approx": True}, n=max(3, a.regions // 3))  # PVNET_F_APPROX on the same inputs
-    dt_apx = median([r[0] for r in runs_apx])
 
     per_rank = [BATCH * a.steps / dt_local]
     gather_ms = None
@@ -819,6 +899,22 @@ def main(argv=None):
         allt = torch.empty((world,), dtype=torch.float64, device=dev)
         dist.all_gather_into_tensor(allt, t)
         per_rank = [BATCH * a.steps / float(x) for x in allt.tolist()]
+    if not a.full:
+        if rank == 0:
+            rates = [world * BATCH * a.steps / x for x in dts]
+            res = headline(dt, rates)
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(res) + "\n").encode())
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    runs1 = regions(1, mode=MAIN, n=max(3, a.regions // 3)) if nstreams > 1 else runs  # the same K steps one after the other
+    dt1 = median([r[0] for r in runs1])
+    runs_apx = regions(nstreams, mode={"approx": True}, n=max(3, a.regions // 3))  # PVNET_F_APPROX on the same inputs
+    dt_apx = median([r[0] for r in runs_apx])
+    if dist is not None:
         fence()
         t0 = time.perf_counter()
         for i in range(50):  # the exchange alone, one bucket after the other: its latency (G x 2.3 KB per rank)
@@ -857,7 +953,6 @@ def main(argv=None):
         seen = allm.tolist()
 
     if rank == 0:
-        votings_per_s = world * BATCH * a.steps / dt
         step_s = dt / a.steps
         rates = [world * BATCH * a.steps / x for x in dts]
         exec_tflops = MFMA_FLOP_PER_PAIR * pairs / score_s / 1e12
@@ -869,22 +964,24 @@ def main(argv=None):
         busy, busy_tag = measured_mfma_busy()
         measured = sum(v for v in traffic.values() if v) if all(traffic.values()) else None
         L = voting.vote_layout(BATCH, H, W, VN, HN, 30000)
-        res = {
-            "metric": "RANSAC votings/s (480x640, 9 kpts, batch 32) + HBM GB/s vs roofline",
-            "value": votings_per_s, "unit": "votings/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "regions": {"runs": len(dts), "reported": "median", "min": min(rates), "max": max(rates),
-                        "spread": (max(rates) - min(rates)) / votings_per_s, "values": rates,
-                        "note": "the timed region (fence, exactly K steps, fence; max over ranks) run `runs` times; value "
-                                "and ms_per_step are the MEDIAN region; before them the same region runs unrecorded (when "
-                                "K < 200: twelve times) so that none of the recorded ones "
-                                "sees the ramp after the device's idle phases",
-                        "unrecorded_values": pre_rates,
-                        "unrecorded_note": "rates of the regions run BEFORE the recorded ones (same form, same clock): rounds 1-3 "
-                                           "recorded from the first region on, so their BENCH numbers include the ramp these show",
-                        "gpu": sampler.summary()},
-            "mode": "APPROX (--approx, development A/B only)" if a.approx else
-                    "exact (library default): inlier counts and winners equal the reference kernels'",
+        res = headline(dt, rates)
+        res["regions"].update({
+            "note": "the timed region (fence, exactly K steps, fence; max over ranks) run `runs` times; value "
+                    "and ms_per_step are the MEDIAN region; before them the same region runs unrecorded (when "
+                    "K < 200: twelve times) so that none of the recorded ones "
+                    "sees the ramp after the device's idle phases",
+            "unrecorded_values": pre_rates,
+            "unrecorded_note": "rates of the regions run BEFORE the recorded ones (same form, same clock): rounds 1-3 "
+                               "recorded from the first region on, so their BENCH numbers include the ramp these show",
+            "gpu": sampler.summary()})
+        res["config"].update({
+            "mean_foreground_px": tn_per_batch / BATCH,
+            "touched_input_bytes": int(len(sets) * compulsory),
+            "concurrent_hint": "explicit: PVNET_F_CONCURRENT (concurrent=True) on the calls of regions that issue on several "
+                               "streams, not in single_stream (voting.concurrent_hint consults the stream history only "
+                               "when a caller passes None); the flag selects a kernel variant -- contiguous item runs + "
+                               "one accumulator pair -- never a result"})
+        res.update({
             "single_stream": {"value": world * BATCH * a.steps / dt1, "ms_per_step": dt1 / a.steps * 1e3,
                               "runs": len(runs1),
                               "note": "the same K steps issued on one stream: per-batch latency of the whole path"},
@@ -895,31 +992,9 @@ def main(argv=None):
             "literal_mode": {"value": world * BATCH * 5 / lit_dt, "unit": "votings/s", "ms_per_step": lit_dt / 5 * 1e3,
                              "note": "PVNET_F_LITERAL: the reference's float32 operation order for every pair on the "
                                      "VALU (5 calls on one stream)"},
-            "per_rank_votings_per_s": per_rank, "gather_ms": gather_ms,
-            "gather_bucket_steps": G if dist is not None else None,
-            "gather_stream": (("the voting stream that filled the bucket (the library's ncclAllGather, pvnet_vote_allgather)" if rg is not None
-                               else "a voting stream (BENCH_GATHER_ON_VOTING_STREAM=1)" if GATHER_ON_VOTE else "its own stream")
-                              if dist is not None else None),
-            "gather_fallback": gather_fallback,
+            "gather_ms": gather_ms,
             "rccl_ranks_seen": len(seen) if seen else None,
             "rank_devices": [{"rank": r, "local_rank": l, "device": d} for r, l, d in seen] if seen else None,
-            "dtype": "f32 decisions (bf16x3 MFMA products, f32 accumulate; pairs inside the f32 rounding band re-evaluated "
-                     "in the reference's f32 order); refinement f64",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE.json configs[2]: batch=32 synthetic 480x640 fields per GPU, 9 keypoints, "
-                                   "1024 hypotheses, inlier_thresh 0.99, int64 mask, planar strided field",
-                       "batch_per_gpu": BATCH, "global_batch": world * BATCH, "h": H, "w": W, "vn": VN, "hn": HN,
-                       "mask_radius": a.radius, "mean_foreground_px": tn_per_batch / BATCH,
-                       "field": "clean" if a.clean else "noisy (0.05 rad + 10% outliers), N(0,1) background",
-                       "input_sets_cycled": len(sets),
-                       "touched_input_bytes": int(len(sets) * compulsory),
-                       "streams": nstreams, "prewarm_s": a.prewarm_seconds,
-                       "concurrent_hint": "explicit: PVNET_F_CONCURRENT (concurrent=True) on the calls of regions that issue on several "
-                                          "streams, not in single_stream (voting.concurrent_hint consults the stream history only "
-                                          "when a caller passes None); the flag selects a kernel variant -- contiguous item runs + "
-                                          "one accumulator pair -- never a result",
-                       "parallelism": f"images sharded over {world} GPU(s); steps issued round-robin on {nstreams} "
-                                      f"HIP stream(s) per GPU"},
             "roofline": {"kernel": f"{SCORE_KERNEL}<{L.wg_g * L.hpl // 2}, ...>" + (" (score_exact_kernel_both_*: ONE launch for dense and disc-culled work "
                                                                                         "items; on this field K3 culls nothing)" if L.cull else ""),
                          "bound": "mfma",
@@ -967,8 +1042,7 @@ def main(argv=None):
                                      "achieved bandwidth: the path never reads the background of the field.  All three "
                                      "over the multi-stream step time."},
             "stage_ms": stage_ms,
-            "kernel_source_hash": source_hash(),
-        }
+        })
         if not a.no_parity:
             try:
                 res["parity"] = parity_check(sets, rank)
@@ -1002,17 +1076,21 @@ def stub_run(a, dist, world, rank, json_fd):
     gathered = torch.empty((world * BATCH, VN, 2), dtype=torch.float32)
 
     def run(n):
+        out = None
         for i in range(n):
             out = voter(i)
             if dist is not None:
                 dist.all_gather_into_tensor(gathered, out)
         if dist is not None:
             dist.barrier()
+        return out
 
     run(a.warmup)
     t0 = time.perf_counter()
-    run(a.steps)
+    last = run(a.steps)
     dt_local = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last.numpy())
     dt, per_rank = dt_local, [BATCH * a.steps / dt_local]
     if dist is not None:
         t = torch.tensor([dt_local], dtype=torch.float64)

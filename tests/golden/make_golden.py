@@ -18,6 +18,9 @@ G8  reference_callers.json -- how the reference's OWN tools/demo.py and tools/tr
                       both scripts imported UNCHANGED through tools/refshim.py (their five voting-layer imports bind this
                       repository's HIP functions), every EvalWrapper's forward() run with recorders in place of the layer
                       (tools/reference_callers_probe.py): function called, arguments, dtype / shape / strides of the tensors.
+G9  backbone_resnet18_8s.npz -- the reference's OWN Resnet18_8s (lib/networks/model_repository.py, no download): the
+                      shapes of its parameters and buffers in order, and its outputs on a seeded input with the seeded stand-in's
+                      weights copied in (tests/test_backbone_standin.py).
 G3  noisy_oracle.npz -- float64-oracle outputs (key-points, winner indices, winner counts) on seeded noisy
                       synthetic images with the counter-based RNG; guards the oracle itself against drift.
 """
@@ -172,12 +175,48 @@ def make_reference_callers():
     print("wrote reference_callers.json:", list(d["calls"]))
 
 
+BACKBONE_SCRIPT = r"""
+import json, sys, numpy as np, torch
+sys.path.insert(0, %(tools)r); sys.path.insert(0, %(root)r)
+import refshim
+refshim.install(%(ref)r)
+sys.path.insert(0, %(tests)r)
+from test_backbone_standin import seeded_standin
+mine, x = seeded_standin()
+for k in [k for k in sys.modules if k == "lib" or k.startswith("lib.")]:
+    del sys.modules[k]                           # the repo's drop-in overlay package is also called `lib`
+sys.path.insert(0, %(ref)r)
+import lib.networks.resnet as R
+R.model_zoo.load_url = lambda *a, **k: {}        # resnet.py:231 -- no network here
+R.ResNet.load_state_dict = lambda self, sd, *a, **k: None
+from lib.networks.model_repository import Resnet18_8s
+ref = Resnet18_8s(ver_dim=18, seg_dim=2).eval()
+rp, mp = list(ref.parameters()), list(mine.parameters())
+rb, mb = list(ref.buffers()), list(mine.buffers())
+assert [p.shape for p in rp] == [p.shape for p in mp] and [b.shape for b in rb] == [b.shape for b in mb]
+with torch.no_grad():
+    for a, b in zip(rp + rb, mp + mb):
+        a.copy_(b)
+    seg, ver = ref(x)
+np.savez_compressed(%(out)r, param_shapes=np.array(json.dumps([list(p.shape) for p in rp])),
+                    buffer_shapes=np.array(json.dumps([list(b.shape) for b in rb])), x=x.numpy(), seg=seg.numpy(), ver=ver.numpy())
+"""
+
+
+def make_backbone():
+    import subprocess
+    code = BACKBONE_SCRIPT % dict(tools=os.path.join(ROOT, "tools"), root=ROOT, ref=REF, tests=os.path.join(ROOT, "tests"),
+                                  out=os.path.join(OUT, "backbone_resnet18_8s.npz"))
+    subprocess.check_call([sys.executable, "-B", "-c", code], cwd=ROOT)
+
+
 if __name__ == "__main__":
     if os.path.isdir(REF):
         make_reference_callers()
         make_demo()
         make_ref_driver()
         make_ref_siblings()
+        make_backbone()
     else:
         print("no /root/reference: demo and reference-driver fixtures not regenerated")
     make_noisy()

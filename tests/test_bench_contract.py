@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -65,6 +67,62 @@ def test_plain_and_single_rank_launcher_runs_agree_in_shape():
     a = _run_bench("--gpus", "1", "--steps", "10", "--warmup", "1", "--stub")
     assert a["n_gpus"] == 1 and len(a["per_rank_votings_per_s"]) == 1
     assert abs(a["value"] - a["per_rank_votings_per_s"][0]) / a["value"] < 1e-6
+
+
+def test_plain_run_is_one_region_and_full_is_opt_in():
+    bench = importlib.import_module("bench")
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert (a.full, a.regions, a.steps, a.warmup, a.dump_outputs) == (False, 1, 7, 2, None)
+    a = bench.parse(["--full"])
+    assert a.full and a.regions == 15
+    assert bench.parse(["--full", "--regions", "3"]).regions == 3
+
+
+def test_threaded_inputs_equal_make_batch():
+    bench = importlib.import_module("bench")
+    from concurrent.futures import ThreadPoolExecutor
+    from pvnet_amd import synth
+    import numpy as np
+    with ThreadPoolExecutor(max_workers=4) as pool:
+        mask, planar = bench.host_batch(bench.BATCH, 40, True, pool)
+    m2, p2, _ = synth.make_batch(bench.BATCH, first_index=bench.BATCH, h=bench.H, w=bench.W, vn=bench.VN, radius=40,
+                                 noise=True, background="normal")
+    assert mask.dtype == m2.dtype and planar.dtype == p2.dtype
+    assert np.array_equal(mask, m2) and np.array_equal(planar, p2)
+
+
+def test_dump_outputs_writes_the_last_steps_keypoints(tmp_path):
+    import numpy as np
+    r = _run_bench("--gpus", "1", "--steps", "4", "--warmup", "1", "--stub", "--dump-outputs", str(tmp_path / "out"))
+    assert r["steps"] == 4
+    k = np.load(tmp_path / "out" / "keypoints.npy")
+    assert k.dtype == np.float32 and k.shape == (32, 9, 2)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_what_the_path_returned(tmp_path):
+    """a plain run: ONE region of exactly --steps steps, the contract's fields, and DIR/keypoints.npy equal to what the
+    layer returns for the last timed step's inputs and seed (step i: input set i % buffers, seed SEED0 + i)"""
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+    from pvnet_amd import synth, voting
+    steps = 7
+    r = _run_bench("--gpus", "1", "--steps", str(steps), "--warmup", "2", "--dump-outputs", str(tmp_path))
+    assert r["steps"] == steps and r["warmup"] == 2 and r["full"] is False and r["regions"]["runs"] == 1
+    assert r["unit"] == "votings/s" and r["higher_is_better"] is True and r["value"] > 0 and r["dtype"]
+    assert abs(r["value"] - bench.BATCH * 1e3 / r["ms_per_step"]) / r["value"] < 1e-9
+    for k in ("parity", "secondary", "cpu_baseline", "roofline", "single_stream"):
+        assert k not in r
+    got = np.load(tmp_path / "keypoints.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.BATCH, bench.VN, 2)
+    i = steps - 1
+    mask, planar = bench.host_batch((i % 4) * bench.BATCH, 40, True)
+    dev = torch.device("cuda:0")
+    want = voting.ransac_voting_layer_v3(torch.from_numpy(mask).to(dev),
+                                         synth.planar_to_vertex_view(torch.from_numpy(planar).to(dev)), bench.HN,
+                                         inlier_thresh=bench.THRESH, seed=bench.SEED0 + i)
+    np.testing.assert_array_equal(got, want.cpu().numpy())
 
 
 def test_gpus_must_match_world_size():

@@ -1,6 +1,6 @@
 """Same-box A/B of library builds (boxes of the pool differ by +-5 %, so every comparison is made inside ONE gpurun call):
     python tools/ab.py [--rounds 2] name=path/to/lib.so[,ENV=value,...] [name=path ...] [bench.py options]
-runs bench.py (exact mode, no CPU baseline, no parity block) with PVNET_VOTE_LIB pointing at each library in turn, `rounds`
+runs bench.py --full (exact mode, no CPU baseline, no parity block) with PVNET_VOTE_LIB pointing at each library in turn, `rounds`
 times interleaved, and prints the six-stream rate, the single-stream rate and the scoring kernel's own duration."""
 import json
 import os
@@ -25,7 +25,7 @@ res = {n: [] for n, _ in libs}
 for r in range(rounds):
     for n, p in libs:
         env = dict(os.environ, PVNET_VOTE_LIB=p[0], **p[1])
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-parity", "--regions", "7"] + extra,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-parity", "--regions", "7"] + extra,
                              env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

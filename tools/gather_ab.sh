@@ -11,9 +11,9 @@ print(f"{sys.argv[1]:22s} six-stream {d['value'] / 1e3:7.1f} k   ms/step {d['ms_
 PY
 }
 for r in $(seq 1 "$R"); do
-  python bench.py --no-cpu-baseline --no-parity --no-secondary --regions 7 > /tmp/g_plain.json 2>/dev/null; line "round $r plain" /tmp/g_plain.json
+  python bench.py --full --no-cpu-baseline --no-parity --no-secondary --regions 7 > /tmp/g_plain.json 2>/dev/null; line "round $r plain" /tmp/g_plain.json
   for g in rccl torch; do
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $((29500 + r)) bench.py --gpus 1 --gather $g \
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $((29500 + r)) bench.py --full --gpus 1 --gather $g \
       --no-cpu-baseline --no-parity --no-secondary --regions 7 > /tmp/g_$g.json 2>/dev/null; line "round $r torchrun $g" /tmp/g_$g.json
   done
 done

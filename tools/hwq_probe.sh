@@ -1,4 +1,4 @@
-B="python bench.py --no-cpu-baseline --no-parity --regions 5 --steps 200"
+B="python bench.py --full --no-cpu-baseline --no-parity --regions 5 --steps 200"
 show() { python -c "import json,sys;d=json.loads(open('$1').read().strip().splitlines()[-1]);print('$2', round(d['value']/1e3,1),'k six-stream', round(d['single_stream']['value']/1e3,1),'k single')"; }
 for q in default 3 4 5; do
   if [ $q = default ]; then unset GPU_MAX_HW_QUEUES; else export GPU_MAX_HW_QUEUES=$q; fi
