@@ -395,7 +395,12 @@ PV_DEF_SCORE_BOTH(0, 0, 120) PV_DEF_SCORE_BOTH(1, 0, 120) PV_DEF_SCORE_BOTH(0, 1
 #undef PV_DEF_SCORE_BOTH
 constexpr size_t CULL_LDS_BYTES = 9 * TILE_U4 * sizeof(uint4) + 4 * 8 * 64 * sizeof(unsigned) +
                                   32 * CULL_NPX * sizeof(uint8_t) + CULL_NPX * sizeof(float) + 64 * sizeof(int);
-static_assert(4 * (CULL_LDS_BYTES + 64) <= 160 * 1024, "four workgroups of the merged scoring kernel per CU");
+// the merged launch's request covers BOTH bodies: the dense body (256-pixel items, 8 tiles per wave) carves 768 B more than the
+// culling body -- with CULL_LDS_BYTES alone its flagged-cell slots 1856..2047 lay beyond the request
+constexpr size_t DENSE_LDS_BYTES = exact_body_lds_bytes(CULL_NPX, 8);
+constexpr size_t BOTH_LDS_BYTES = CULL_LDS_BYTES > DENSE_LDS_BYTES ? CULL_LDS_BYTES : DENSE_LDS_BYTES;
+static_assert(BOTH_LDS_BYTES >= CULL_LDS_BYTES && BOTH_LDS_BYTES >= DENSE_LDS_BYTES, "the merged request covers both bodies");
+static_assert(4 * (BOTH_LDS_BYTES + 64) <= 160 * 1024, "four workgroups of the merged scoring kernel per CU (+ static LDS)");
 
 
 }  // namespace
@@ -403,11 +408,11 @@ static_assert(4 * (CULL_LDS_BYTES + 64) <= 160 * 1024, "four workgroups of the m
 int launch_score_both(const VoteParams& P, dim3 g, hipStream_t s, bool timed, bool runs) {
     const dim3 t(256);
     if (timed) {
-        if (runs) hipLaunchKernelGGL(score_exact_kernel_both_1_1, g, t, CULL_LDS_BYTES, s, P);
-        else hipLaunchKernelGGL(score_exact_kernel_both_1_0, g, t, CULL_LDS_BYTES, s, P);
+        if (runs) hipLaunchKernelGGL(score_exact_kernel_both_1_1, g, t, BOTH_LDS_BYTES, s, P);
+        else hipLaunchKernelGGL(score_exact_kernel_both_1_0, g, t, BOTH_LDS_BYTES, s, P);
     } else {
-        if (runs) hipLaunchKernelGGL(score_exact_kernel_both_0_1, g, t, CULL_LDS_BYTES, s, P);
-        else hipLaunchKernelGGL(score_exact_kernel_both_0_0, g, t, CULL_LDS_BYTES, s, P);
+        if (runs) hipLaunchKernelGGL(score_exact_kernel_both_0_1, g, t, BOTH_LDS_BYTES, s, P);
+        else hipLaunchKernelGGL(score_exact_kernel_both_0_0, g, t, BOTH_LDS_BYTES, s, P);
     }
     return 0;
 }

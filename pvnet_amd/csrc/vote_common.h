@@ -505,6 +505,14 @@ constexpr int TILE_U4 = 128;  // uint4 per 32-pixel tile: four blocks of 32 x 16
                               // culling kernel's gathered ones.  Now slot = row mod 16: dense reads are conflict-free, gathered ones meet
                               // sixteen slots instead of eight.)
 static_assert(TILE_U4_ == TILE_U4, "the disc-culling body's row addresses (CULL_DEAD, tile = pixel >> 5, row = pixel & 31) follow TILE_U4");
+// dynamic LDS of score_exact_body (k4_exact_body.h) for items of npx pixels and mh hypothesis tiles per wave: its carve from the one
+// base -- A tiles, raw records, the item's 4 * mh * 32 hypotheses, the 4 * mh * 64 flagged-cell slots.  The dense launch and the
+// merged launch (k4_score_cull.hip) both size their request with it: a request short of it leaves the last cell slots outside.
+constexpr size_t exact_body_lds_bytes(int npx, int mh) {
+    return (size_t)(npx / 32) * TILE_U4 * sizeof(uint4) + (size_t)npx * sizeof(float4) + (size_t)4 * mh * 32 * sizeof(float2) +
+           (size_t)4 * mh * 64 * sizeof(unsigned);
+}
+static_assert(exact_body_lds_bytes(CULL_NPX, 8) == 36864, "the dense body's carve at 256-pixel items, 8 tiles per wave");
 
 // v + (the other half-wave's v): lanes l and l ^ 32 hold different pixel rows of one hypothesis column.  gfx950's
 // v_permlane32_swap exchanges the upper row of one operand with the lower row of the other in the VALU -- no trip through

@@ -193,8 +193,7 @@ int launch_all(const VoteParams& P, hipStream_t s, hipEvent_t* ev, int stage_mas
         } else if (P.exact) {
             const int mh = P.wg_g * P.hpl / 2;
             const int npx = P.wg_s * P.chunk;
-            size_t lds = (size_t)(npx / 32) * TILE_U4 * sizeof(uint4) + (size_t)npx * sizeof(float4) +
-                         (size_t)4 * mh * 32 * sizeof(float2) + (size_t)4 * mh * 64 * sizeof(unsigned);
+            size_t lds = exact_body_lds_bytes(npx, mh);
             if (T.score_lds_kb > 0 && T.score_lds_kb <= 64 && lds < (size_t)T.score_lds_kb * 1024) lds = (size_t)T.score_lds_kb * 1024;
             rc = launch_score_exact(P, g, lds, s, timed_score, one_acc, runs);
         } else if (!literal && P.mode) {

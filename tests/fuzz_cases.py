@@ -100,3 +100,129 @@ def run_case(case, dev=None, verbose=False):
     if verbose and not (res["ok_literal"] and res["ok_exact"] and cd <= lim and res["finite"]):
         print("FUZZ MISMATCH", res, flush=True)
     return res
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Knob-free cases on the RELEASE library (tests/test_release_scoring.py).  run_case above writes every PVNET_* knob into the
+# environment, so its cases load the development build, whose PVNET_SCORE_CULL=1 also gives small batches culling layouts the
+# release library never builds.  These cases touch no environment: they reach the shipped kernels -- above all the merged scoring
+# launch (score_exact_kernel_both_*) of the culling-capable layouts -- through the per-call selection flags and through the
+# workspace's history (the batch gate CF_BATCH_OK follows the previous call on the workspace).
+# ------------------------------------------------------------------------------------------------------------------------------
+RELEASE_FIRST = 30000   # seeds no other test uses
+FIELD_KINDS = ("clean", "noisy", "outliers", "unnorm", "far")
+HISTORIES = ("fresh", "after_exact", "after_literal")
+
+
+def release_case_params(case):
+    """the draws of release case `case` -- numpy only, so that tests/test_library_cpu.py can check the layouts they imply without a
+    GPU.  Strata by case % 4: 0 a culling-capable shape (hn in [768, 1024], b * vn >= 64, vn <= 32) with every key-point culled;
+    1 a culling-capable shape under the library's own selection on a fresh workspace, image 0 clean and image 1 noisy (one call,
+    both scoring bodies); 2 a shape the release layout scores densely; 3 any of these, every draw free."""
+    rng = np.random.default_rng(RELEASE_FIRST + case)
+    stratum = case % 4
+    capable = stratum in (0, 1) or (stratum == 3 and bool(rng.integers(0, 2)))
+    if capable:
+        vn = int(rng.integers(2, 33))
+        b = -(-64 // vn) + int(rng.integers(0, 3))
+        hn = int(rng.integers(768, 1025))
+    else:
+        form = int(rng.integers(0, 3))
+        if form == 0:     # too few (image, key-point) pairs for 256-pixel items at a culling hn
+            vn = int(rng.integers(1, 33))
+            b = int(rng.integers(1, 63 // vn + 1))
+            hn = int(rng.integers(768, 1025))
+        elif form == 1:   # hypothesis counts the culling layout does not cover
+            vn = int(rng.integers(2, 33))
+            b = -(-64 // vn) + int(rng.integers(0, 2))
+            hn = int(rng.choice([256, 500, 767, 1025, 2048]))
+        else:             # more key-points than the per-key-point origin handles
+            vn = int(rng.integers(33, 41))
+            b = 2
+            hn = int(rng.integers(768, 1025))
+    h, w = int(rng.integers(40, 121)), int(rng.integers(40, 161))
+    sel = {0: "all", 1: None}.get(stratum, [None, "all", "none"][int(rng.integers(0, 3))])
+    history = "fresh" if stratum == 1 else HISTORIES[int(rng.integers(0, 3))]
+    kinds = [FIELD_KINDS[int(rng.integers(0, len(FIELD_KINDS)))] for _ in range(b)]
+    if stratum == 1:
+        kinds[:2] = ["clean", "noisy"]
+    return dict(case=case, stratum=stratum, b=b, h=h, w=w, vn=vn, hn=hn, radius=int(rng.integers(5, 17)),
+                thresh=float(rng.choice([0.9, 0.99, 0.999, 0.9999])), max_num=int(rng.choice([30000, 30000, 1000, 300, 150])),
+                mdt=str(rng.choice(["int64", "uint8", "int32", "bool"])), concurrent=bool(rng.integers(0, 2)),
+                contiguous=bool(rng.integers(0, 2)), sel=sel, history=history, kinds=kinds, seed=int(rng.integers(0, 2 ** 40)))
+
+
+def release_field(p):
+    """(mask [b,h,w], planar [b,2vn,h,w] float32) of a release case: every image of its own kind"""
+    rng = np.random.default_rng(RELEASE_FIRST + 7919 * p["case"])
+    masks, planes = [], []
+    for i, kind in enumerate(p["kinds"]):
+        index = 40000 + 64 * p["case"] + i
+        mask, planar, _ = synth.make_image(index, h=p["h"], w=p["w"], vn=p["vn"], radius=p["radius"],
+                                           background="zeros" if kind in ("clean", "far") else "normal",
+                                           noise=kind in ("noisy", "outliers", "unnorm"), mask_dtype=np.dtype(p["mdt"]).type,
+                                           outlier_frac=0.4 if kind == "outliers" else 0.10)
+        if kind == "far":   # every key-point 1e6 .. 1e8 px away: near-parallel lines, hypotheses scattered far from the object
+            fg = mask != 0
+            ys, xs = np.nonzero(fg)
+            ang = rng.uniform(0, 2 * np.pi, p["vn"])
+            dist = 10.0 ** rng.uniform(6, 8, p["vn"])
+            kp = np.stack([xs.mean() + dist * np.cos(ang), ys.mean() + dist * np.sin(ang)], axis=1)
+            planar = synth.field_from_keypoints(fg, kp)
+        elif kind == "unnorm":   # a random positive factor per pixel and key-point, some of them ~0 (as run_case)
+            fac = np.exp(rng.normal(0.0, 3.0, size=(p["vn"], 1, p["h"], p["w"]))).astype(np.float32)
+            fac[rng.random(fac.shape) < 0.02] = np.float32(rng.choice([0.0, 1e-7, 1.0000001e-6, 1e-5]))
+            planar = (planar.reshape(p["vn"], 2, p["h"], p["w"]) * fac).reshape(2 * p["vn"], p["h"], p["w"])
+        masks.append(mask)
+        planes.append(planar.astype(np.float32))
+    return np.stack(masks), np.stack(planes)
+
+
+def run_release_case(case, dev=None):
+    """one knob-free case on whatever library the front end loads (the caller checks that it is the release build) ->
+    dict(ok, ..., cull_layout, culled, dense, desc).  The DEFAULT (exact) mode on an explicitly zeroed workspace whose history is
+    drawn -- fresh, behind an exact call, behind a literal call -- against literal mode (hypotheses, counts, winners equal; key-points
+    within 1e-3 px) and literal mode against the C oracle (winners and their counts)."""
+    dev = dev or torch.device("cuda:0")
+    p = release_case_params(case)
+    b, h, w, vn, hn, thresh, max_num, seed = p["b"], p["h"], p["w"], p["vn"], p["hn"], p["thresh"], p["max_num"], p["seed"]
+    mask, planar = release_field(p)
+    m = torch.from_numpy(mask).to(dev)
+    v = synth.planar_to_vertex_view(torch.from_numpy(planar).to(dev))
+    if p["contiguous"]:
+        v = v.contiguous()
+    L = voting.vote_layout(b, h, w, vn, hn, max_num)
+
+    def zeroed():
+        return torch.zeros(L.total_bytes, dtype=torch.uint8, device=dev)
+
+    def call(ws, **kw):
+        return voting.ransac_voting_layer_v3(m, v, hn, inlier_thresh=thresh, max_num=max_num, return_debug=True, workspace=ws, **kw)
+    ws = zeroed()
+    voting.set_cull_selection(p["sel"])
+    try:
+        out_l, dl = call(ws if p["history"] == "after_literal" else zeroed(), seed=seed, literal=True)
+        out_l = out_l.clone()
+        counts_l, win_l, hyp_l = dl["counts"].clone(), dl["win"].clone(), dl["hyp"].cpu().numpy().tobytes()
+        nch = dl["nchunks"].cpu().numpy().copy()
+        if p["history"] == "after_exact":
+            call(ws, seed=seed + 1)   # another draw on the same inputs: what it leaves decides this call's batch gate
+        out_e, de = call(ws, seed=seed, concurrent=p["concurrent"])
+        bits = de["cull_bits"].cpu().numpy().copy()
+        same = (de["mode"] == "exact" and de["hyp"].cpu().numpy().tobytes() == hyp_l and torch.equal(de["counts"], counts_l)
+                and torch.equal(de["win"], win_l))
+        counts_differing = int((de["counts"] != counts_l).sum())
+    finally:
+        voting.set_cull_selection(None)
+    okpx = torch.isfinite(out_l).all(-1) & (out_l.abs() < 1e5).all(-1)
+    px = float((out_e - out_l)[okpx].abs().max()) if okpx.any() else 0.0
+    ok_px = px <= 1e-3 * max(1.0, float(out_l[okpx].abs().max()) / 100 if okpx.any() else 1.0)
+    _, wi, wc = cref.vote_v3(O.foreground(mask), synth.planar_to_vertex_view(planar), hn, thresh, max_num=max_num, seed=seed,
+                             return_winners=True)
+    wl = win_l.cpu().numpy()
+    live = nch > 0
+    ok_literal = np.array_equal(wl[:, :, 0][live], wi[live]) and np.array_equal(wl[:, :, 1][live], wc[live])
+    desc = {k: p[k] for k in ("case", "b", "h", "w", "vn", "hn", "thresh", "max_num", "mdt", "sel", "history", "kinds")}
+    desc.update(counts_differing=counts_differing, px=px, cull_bits=int(bits.sum()))
+    return dict(ok=bool(same and ok_px and ok_literal), ok_exact=bool(same), ok_px=bool(ok_px), ok_literal=bool(ok_literal),
+                cull_layout=int(L.cull), culled=int(bits.sum()), keypoints=b * vn, desc=desc)

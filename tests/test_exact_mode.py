@@ -329,7 +329,8 @@ def test_more_than_32_keypoints_use_the_image_origin():
 def test_many_key_points(vn):
     """the band origin (and the culling selection) is estimated per key-point for up to 32 of them -- eight candidate lanes each, all 256
     threads of a K3 block at vn = 32; beyond that every key-point takes the image's median pixel as origin and nothing is culled.
-    Either way: the reference's integers."""
+    Either way: the reference's integers.  (The same key-point counts at a culling layout of the release library:
+    tests/test_release_scoring.py.)"""
     m, v, _ = batch(3, 910, 120, 160, 15, vn=vn)
     _, lit, _, ex = both_modes(m, v, 256, 0.99)
     assert_same_integers(lit, ex, 3)

@@ -201,15 +201,21 @@ def test_oversized_matrix_pipe_items_are_refused(monkeypatch):
     voting.vote_layout(2, 120, 160, 9, 100, 30000)  # and an environment change alone does nothing until reloaded
 
 
-def test_every_kernel_keeps_a_spare_vgpr_granule(tmp_path):
+@pytest.fixture(scope="module")
+def chk():
+    """tools/check_kernel_resources.py -- its assembly of both builds is compiled once for the tests that read it"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("check_kernel_resources", os.path.join(ROOT, "tools", "check_kernel_resources.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_every_kernel_keeps_a_spare_vgpr_granule(tmp_path, chk):
     """round 2's compaction flake: identical code failed in 98 % of the runs when it used its VGPR allocation to the top
     and never with one granule more (profiles/r02_compaction_flake_investigation.txt).  Every kernel of both sources must
     allocate at least 8 VGPRs beyond the highest one an instruction names (PVNET_SPARE_VGPRS); the checker is checked on
     a hand-made violation."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("check_kernel_resources", os.path.join(ROOT, "tools", "check_kernel_resources.py"))
-    chk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(chk)
     assert chk.main([]) == 0
     body = ("kern:\n\tv_add_u32_e32 v23, v0, v1\n\ts_endpgm\n.Lfunc_end0:\n"
             "\t.amdhsa_kernel kern\n\t\t.amdhsa_next_free_vgpr %d\n\t.end_amdhsa_kernel\n")
@@ -264,3 +270,57 @@ def test_concurrency_hint_follows_stream_alternation(monkeypatch):
     assert voting.F_CONCURRENT == 256
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "pvnet_vote.h")).read()
     assert re.search(r"#define\s+PVNET_F_CONCURRENT\s+256u", hdr)
+
+
+def test_release_kernels_equal_the_development_builds(chk):
+    """the knob tests and the fuzz matrix run the DEVELOPMENT build (a PVNET_* knob loads it): their green speaks for the shipped
+    kernels only if every kernel of the release build is the same-named development kernel -- the same instruction stream (comments
+    stripped, local labels renumbered) and the same descriptor (.amdhsa_* fields).  A `#ifdef PVNET_DEV` inside a kernel body breaks
+    that.  The comparison is checked on hand-made differences."""
+    texts = {}
+    for src, dev, text in chk.assembly():
+        texts.setdefault(src, {})[dev] = text
+    pairs = [(t[False], t[True]) for t in texts.values()]
+    released = [n for rel, _ in pairs for n in chk.kernel_code(rel)]
+    assert len(released) >= 45 and any("score_exact_kernel_both" in n for n in released)
+    assert chk.release_differs_from_dev(pairs) == []
+    rel = next(t[False] for src, t in texts.items() if src.endswith("k4_score_cull.hip"))
+    name = next(n for n in chk.kernel_code(rel) if "score_exact_kernel_both_0_0" in n)
+    i = rel.index("\n" + name + ":")
+    j = rel.index("v_sub_f32_e64", i)
+    k = rel.index(".amdhsa_next_free_sgpr", rel.index(".amdhsa_kernel " + name))
+    one_op = rel[:j] + "v_add_f32_e64" + rel[j + len("v_sub_f32_e64"):]
+    one_field = rel[:k] + ".amdhsa_next_free_sgpr 7\n;" + rel[k:]
+    labels = re.sub(r"\.LBB(\d+)_", r".LBB9\1_", rel)   # other label numbers only
+    assert chk.release_differs_from_dev([(rel, one_op)]) == [name]
+    assert chk.release_differs_from_dev([(rel, one_field)]) == [name]
+    assert chk.release_differs_from_dev([(rel, labels)]) == []
+
+
+def release_layout(b, h, w, vn, hn, max_num=30000):
+    """pvnet_vote_layout of the RELEASE library, whatever the environment holds"""
+    L = voting.Layout()
+    assert C.CDLL(voting.LIB_PATH).pvnet_vote_layout(b, h, w, vn, hn, max_num, C.byref(L)) == 0
+    return L
+
+
+def test_release_layout_gives_the_gpu_tests_their_culling_path(lib):
+    """the release library builds culling buffers (L.cull: the merged scoring launch) only for hn_pad 1 024, 256-pixel items and
+    vn <= 32.  tests/test_release_scoring.py needs that path for its shapes and for half its fuzz cases; a layout change that would
+    turn them into plain dense calls fails here, without a GPU"""
+    from tests import fuzz_cases as F
+    from tests.test_release_scoring import CULLING_SHAPES, MANY_KP_SHAPES, RELEASE_BLOCK, RELEASE_BLOCKS
+    for shape in CULLING_SHAPES:
+        assert release_layout(*shape).cull == 1, shape
+    for shape in [(7, 240, 320, 9, 1024), (1, 240, 320, 32, 1024), (2, 240, 320, 9, 1024),   # b * vn < 64 at hn 1 024
+                  (8, 240, 320, 9, 256), (8, 240, 320, 9, 2048), (8, 240, 320, 9, 767), (8, 240, 320, 9, 1025),
+                  MANY_KP_SHAPES[33], MANY_KP_SHAPES[40]]:
+        assert release_layout(*shape).cull == 0, shape
+    capable = 0
+    for case in range(F.RELEASE_FIRST, F.RELEASE_FIRST + RELEASE_BLOCKS * RELEASE_BLOCK):
+        p = F.release_case_params(case)
+        want = 768 <= p["hn"] <= 1024 and p["b"] * p["vn"] >= 64 and p["vn"] <= 32
+        assert release_layout(p["b"], p["h"], p["w"], p["vn"], p["hn"], p["max_num"]).cull == want, p
+        assert want == (p["stratum"] in (0, 1) or (p["stratum"] == 3 and want))
+        capable += want
+    assert 2 * capable >= RELEASE_BLOCKS * RELEASE_BLOCK

@@ -14,6 +14,10 @@ half their registers: massive spilling.  So for those kernels the allocation mus
 (EXPECTED_ALLOC: not more -- a wave per SIMD lost -- and not less), they must use more than half of it (a halved cap cannot) and
 none of them may spill more than its own few dwords (`.amdhsa_private_segment_fixed_size`, limit per pattern in EXPECTED_ALLOC).
 
+Third (tests/test_library_cpu.py, release_differs_from_dev): every kernel of the release build has the instruction stream and the
+descriptor of the same-named development kernel -- the knob and fuzz tests, which load the development build, speak for the
+shipped kernels only then.
+
 Also reports the waves per SIMD each allocation permits (512 VGPRs per SIMD, granule 8).  Exit status 1 if a kernel lacks
 the slack.  tests/test_library_cpu.py runs it on every build of the CPU suite.
 """
@@ -63,22 +67,62 @@ def short(name):
     return re.sub(r"^_ZN(3pvd)?\d+_GLOBAL__N_1\d+", "", name)[:56]
 
 
-def main(argv):
-    texts = []
-    if argv:
-        texts = [open(a).read() for a in argv]
-    else:
+_ASM = None   # [(translation unit, dev, assembly)] of this process: compiled once, shared by main() and the CPU tests
+
+
+def assembly():
+    """[(translation unit, dev, assembly text)]: the release and development (-DPVNET_DEV) instantiations of every translation unit
+    of libpvnet_vote.so, compiled to assembly with the product's flags (once per process)"""
+    global _ASM
+    if _ASM is None:
         sys.path.insert(0, ROOT)
         from pvnet_amd import build as B
         with tempfile.TemporaryDirectory() as d:
             from concurrent.futures import ThreadPoolExecutor
             jobs = [(src, dev, os.path.join(d, f"k{k}{'d' if dev else ''}.s")) for k, src in enumerate(B.SRC) for dev in (False, True)
-                    if "rccl" not in src]   # release and development (-DPVNET_DEV) instantiations of every translation unit
-            with ThreadPoolExecutor(max_workers=max(1, (os.cpu_count() or 4) - 1)) as ex:
+                    if "rccl" not in src]
+            with ThreadPoolExecutor(max_workers=max(1, min(16, (os.cpu_count() or 4) - 1))) as ex:
                 list(ex.map(lambda j: compile_to_asm(j[0], j[2], j[1]), jobs))
-            for _, _, out in jobs:
-                t = open(out).read()
-                texts.append(t)
+            _ASM = [(src, dev, open(out).read()) for src, dev, out in jobs]
+    return _ASM
+
+
+def kernel_code(text):
+    """{kernel: (instruction stream, .amdhsa_* descriptor fields)} of one assembly file -- comments and directives stripped, local
+    labels (.LBB3_7, .Ltmp12, ...) renamed in order of appearance, so two compilations of one kernel compare equal however the rest of
+    their translation units numbered their labels"""
+    out = {}
+    for m in re.finditer(r"\.amdhsa_kernel (\S+)", text):
+        name = m.group(1)
+        desc = text[m.start():text.index(".end_amdhsa_kernel", m.start())]
+        fields = tuple(l.strip() for l in desc.splitlines() if l.strip().startswith(".amdhsa_"))
+        i = text.index("\n" + name + ":") + 1
+        labels = {}
+        code = []
+        for line in text[i:text.index(".Lfunc_end", i)].splitlines():
+            line = line.split(";")[0].strip()
+            if not line or (line.startswith(".") and not re.match(r"\.L\w+:$", line)):
+                continue
+            code.append(re.sub(r"\.L\w+", lambda lm: labels.setdefault(lm.group(0), f".L{len(labels)}"), line))
+        out[name] = (tuple(code), fields)
+    return out
+
+
+def release_differs_from_dev(pairs):
+    """pairs: [(release assembly, development assembly)] of the same translation units -> the kernels of the release build whose
+    instruction stream or descriptor differs from the same-named kernel of the development build (or that it lacks).  The knob and
+    fuzz tests run the development build: what they show holds for the shipped kernels only while this list is empty."""
+    bad = []
+    for rel, dev in pairs:
+        kd = kernel_code(dev)
+        for name, code in kernel_code(rel).items():
+            if kd.get(name) != code:
+                bad.append(name)
+    return bad
+
+
+def main(argv):
+    texts = [open(a).read() for a in argv] if argv else [t for _, _, t in assembly()]
     bad = 0
     n = 0
     done = set()
