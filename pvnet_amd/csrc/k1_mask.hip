@@ -67,11 +67,15 @@ __global__ __launch_bounds__(64 * K1_WAVES) void mask_bits_kernel(VoteParams P) 
                 off = (int64_t)bi * P.ms0 + (int64_t)y * P.ms1 + (int64_t)x * P.ms2;
             }
             if (DT == PVNET_MASK_LOGITS_F32) {  // fused torch.argmax(seg_pred, 1) (tools/demo.py:52): first maximum wins
+                // torch's rule for NaN: it counts as the maximum -- a NaN replaces a number, a later NaN never an earlier one.
+                // take = x > best || (x is NaN && best is not), as two compares and a select: `||` compiled to a branch per class
                 float best = ld_elem_rt(P.logits_type, P.mask, off);
                 int arg = 0;
                 for (int c = 1; c < P.num_classes; ++c) {
                     const float x = ld_elem_rt(P.logits_type, P.mask, off + (int64_t)c * P.ms_c);
-                    if (x > best) { best = x; arg = c; }
+                    const bool take = (best == best) & !(x <= best);
+                    best = take ? x : best;
+                    arg = take ? c : arg;
                 }
                 v = (arg & 0xFF) != 0;  // then .byte() != 0 (ransac_voting_gpu.py:527)
             } else {

@@ -510,12 +510,20 @@ def ransac_voting_layer_v3_from_logits(seg_pred, vertex, round_hyp_num, inlier_t
                                        out=None, concurrent=None):
     """``ransac_voting_layer_v3(torch.argmax(seg_pred, 1), vertex, ...)`` with the arg-max fused into the first
     kernel: the class logits ``seg_pred [b,C,h,w]`` float32 are read in place and the int64 mask the reference
-    materialises (tools/demo.py:52) never exists.  Same result as the two-step call."""
+    materialises (tools/demo.py:52) never exists.  Same result as the two-step call, NaN logits included (torch counts
+    a NaN as the maximum, the first one wins).
+
+    dtypes: float32 / float16 / bfloat16 logits (any strides) are read in place by the fused kernel; any other dtype
+    (float64, integers) would have to be narrowed to float32 first, which can turn distinct logits into ties, so these
+    take the two-step call itself: ``torch.argmax`` on the original tensor, then ``ransac_voting_layer_v3``."""
     lib = load_library()
     if not seg_pred.is_cuda or seg_pred.dim() != 4:
         raise RuntimeError("seg_pred must be a CUDA tensor [b,C,h,w]")
     if seg_pred.dtype not in _LOGITS_FLAGS:
-        seg_pred = seg_pred.float()
+        return ransac_voting_layer_v3(torch.argmax(seg_pred, 1), vertex, round_hyp_num, inlier_thresh, confidence,
+                                      max_iter, min_num, max_num, idxs=idxs, seed=seed, image_offset=image_offset,
+                                      literal=literal, approx=approx, refine=refine, workspace=workspace, out=out,
+                                      concurrent=concurrent)
     b, nc, h, w = seg_pred.shape
     fake_mask = seg_pred[:, 0]  # shape/device checks only
     _, vertex, b, h, w, vn, hn, max_num, idxs = _prepare(fake_mask, vertex, round_hyp_num, max_num, idxs,
