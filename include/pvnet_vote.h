@@ -296,6 +296,34 @@ int pvnet_voting_for_hypothesis_vanishing_point(const float* direct, const float
                                                 uint8_t* inliers, int tn, int vn, int hn, float inlier_thresh,
                                                 void* stream);
 
+/* The pose solve after voting, on the device (pvnet_amd/csrc/pose_solve.hip): pvnet_pnp_solve of include/pvnet_pnp.h -- DLT start,
+ * then Levenberg-Marquardt on angle-axis + translation in float64, unweighted and, with weights, weighted from the unweighted
+ * optimum -- for n images, one wavefront per image.  Same algorithm and constants as the host library (its oracle); replaces the
+ * per-image cv2.solvePnP / uncertainty_pnp of the reference's evaluation (lib/utils/evaluation_utils.py:19-52,
+ * extend_utils.py:63-114) and the host round trip of pvnet_pnp_solve_batch.
+ *   pts2d        [n,pn,2] key-points, float32 (what pvnet_vote_v3 writes) or float64 (pts2d_f64 != 0), element strides
+ *                pts2d_strides[3] (host array); widened to float64 on read
+ *   pts3d        [pn,3] float64 object points, shared by the images
+ *   weights      PVNET_POSE_W_NONE: ignored; PVNET_POSE_W_EXPLICIT: float64 [n,pn,3] (wxx, wxy, wyy), residual = W d
+ *                (uncertainty_pnp.cpp:29-30); PVNET_POSE_W_COV_F32: float32 [n,pn,2,2] covariances (pvnet_vote_distribution's
+ *                output), turned into weights as Evaluator.evaluate_uncertainty does: zero when cov[0,0] < 1e-6 or an entry is
+ *                NaN, else the inverse matrix square root with every eigenvalue clamped to >= 1e-30
+ *   K            float64 [3,3], or [n,3,3] with k_per_image != 0
+ *   pn           6 .. PVNET_POSE_MAX_PN (else PVNET_E_UNSUPPORTED)
+ *   max_iterations  LM iterations per refinement (> 0; the host solver uses 200)
+ *   rt           NULL or float64 [n,6] angle-axis | translation;  poses  NULL or float64 [n,3,4] (R | t) -- at least one of the two.
+ *                A failed linear start gives zeros in both (a zero rt gives a zero pose, as pvnet_pnp_poses_from_rt).
+ *   status       NULL or int32 [n]: pvnet_pnp_solve's return value -- the LM iterations (>= 0; unweighted + weighted), or -2 when
+ *                the linear start failed (non-invertible K, a non-positive singular value, a non-finite translation)
+ * Arguments are checked before any HIP call.  Only enqueues on `stream`: capturable in a graph with voting. */
+#define PVNET_POSE_W_NONE     0
+#define PVNET_POSE_W_EXPLICIT 1
+#define PVNET_POSE_W_COV_F32  2
+#define PVNET_POSE_MAX_PN     64
+int pvnet_pose_solve(const void* pts2d, int pts2d_f64, const int64_t pts2d_strides[3], const double* pts3d,
+                     const void* weights, int weight_kind, const double* K, int k_per_image, int n, int pn,
+                     int max_iterations, double* rt, double* poses, int32_t* status, void* stream);
+
 /* ABI / build identification (host-only) */
 int pvnet_vote_abi_version(void);
 const char* pvnet_vote_build_info(void);

@@ -255,3 +255,86 @@ def cm_degree_error(pose_pred, pose_target):
     tr = np.linalg.norm(pose_pred[:, 3] - pose_target[:, 3]) * 100
     c = min(np.trace(pose_pred[:, :3] @ pose_target[:, :3].T), 3.0)
     return float(tr), float(np.rad2deg(np.arccos(np.clip((c - 1.) / 2., -1, 1))))
+
+
+# ---- the pose solve on the device (pvnet_amd/csrc/pose_solve.hip, pvnet_pose_solve in include/pvnet_vote.h) ----------------------
+POSE_W_NONE, POSE_W_EXPLICIT, POSE_W_COV_F32 = 0, 1, 2
+POSE_FAILED = -2   # status of an image whose linear start failed (zeros returned), as pvnet_pnp_solve returns it
+
+
+def _device_tensor(x, dev, dtype, name):
+    """a CUDA tensor of ``dtype`` on ``dev`` (uploaded once from numpy / a list; a tensor of the right type is used as it is)"""
+    import torch
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda or x.device != dev:
+            raise RuntimeError(f"{name} must be a CUDA tensor on {dev} (or numpy)")
+        return x.to(dtype=dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64 if dtype == torch.float64 else np.float32)).to(dev)
+
+
+def pnp_batch_device(points_3d, points_2d, camera_matrix, weights_2d=None, covariance=None, max_iterations=200, out=None):
+    """``pnp_batch`` on the device: one wavefront per image solves pvnet_pnp_solve's problem (DLT start + Levenberg-Marquardt in
+    float64, the host library's algorithm and constants), enqueued on the current stream -- no synchronisation, no host copy.
+
+    :param points_3d:     [pn,3] object points (CUDA tensor, or numpy: uploaded here)
+    :param points_2d:     [n,pn,2] float32 or float64 CUDA tensor, any strides (what ``ransac_voting_layer_v3`` returns is read
+                          in place)
+    :param camera_matrix: [3,3] shared, or [n,3,3] per image (CUDA tensor or numpy)
+    :param weights_2d:    None, or [n,pn,3] (wxx, wxy, wyy) per key-point: the uncertainty PnP of ``pnp_batch(weights_2d=...)``
+    :param covariance:    None, or [n,pn,2,2] covariances (``estimate_voting_distribution_with_mean``'s second output), weighted
+                          as ``Evaluator.evaluate_uncertainty`` does (inverse matrix square root; zero below cov[0,0] < 1e-6)
+    :param out:           None, or caller-owned ``(poses [n,3,4] float64, status [n] int32)`` contiguous CUDA tensors (graph capture)
+    :return: ``(poses [n,3,4] float64, status [n] int32)`` on the device: status = LM iterations (>= 0), or ``POSE_FAILED`` (-2)
+             when the linear start failed -- that image's pose is zeros, as ``pnp_batch`` gives it.
+    """
+    import torch
+    from . import voting
+    if not (isinstance(points_2d, torch.Tensor) and points_2d.is_cuda):
+        raise RuntimeError("points_2d must be a CUDA tensor [n,pn,2]")
+    if points_2d.dim() != 3 or points_2d.shape[2] != 2 or points_2d.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"points_2d must be float32 / float64 [n,pn,2], got {points_2d.dtype} {tuple(points_2d.shape)}")
+    if weights_2d is not None and covariance is not None:
+        raise ValueError("give weights_2d or covariance, not both")
+    dev = points_2d.device
+    n, pn = int(points_2d.shape[0]), int(points_2d.shape[1])
+    X = _device_tensor(points_3d, dev, torch.float64, "points_3d")
+    K = _device_tensor(camera_matrix, dev, torch.float64, "camera_matrix")
+    if tuple(X.shape) != (pn, 3):
+        raise RuntimeError(f"points_3d must be [pn,3]={(pn, 3)}, got {tuple(X.shape)}")
+    if tuple(K.shape) == (3, 3):
+        per_image = 0
+    elif tuple(K.shape) == (n, 3, 3):
+        per_image = 1
+    else:
+        raise RuntimeError(f"camera_matrix must be [3,3] or [n,3,3]={(n, 3, 3)}, got {tuple(K.shape)}")
+    kind, W = POSE_W_NONE, None
+    if weights_2d is not None:
+        kind, W = POSE_W_EXPLICIT, _device_tensor(weights_2d, dev, torch.float64, "weights_2d")
+        if tuple(W.shape) != (n, pn, 3):
+            raise RuntimeError(f"weights_2d must be [n,pn,3]={(n, pn, 3)}, got {tuple(W.shape)}")
+    elif covariance is not None:
+        kind, W = POSE_W_COV_F32, _device_tensor(covariance, dev, torch.float32, "covariance")
+        if tuple(W.shape) != (n, pn, 2, 2):
+            raise RuntimeError(f"covariance must be [n,pn,2,2]={(n, pn, 2, 2)}, got {tuple(W.shape)}")
+    if n == 0 and out is None:
+        return torch.empty((0, 3, 4), dtype=torch.float64, device=dev), torch.empty((0,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        if out is None:
+            poses = torch.empty((n, 3, 4), dtype=torch.float64, device=dev)
+            status = torch.empty((n,), dtype=torch.int32, device=dev)
+        else:
+            poses, status = out
+            if not (poses.is_cuda and poses.device == dev and poses.dtype == torch.float64 and poses.is_contiguous() and
+                    tuple(poses.shape) == (n, 3, 4)):
+                raise RuntimeError(f"out[0] must be a contiguous float64 CUDA tensor of shape {(n, 3, 4)} on {dev}")
+            if not (status.is_cuda and status.device == dev and status.dtype == torch.int32 and status.is_contiguous() and
+                    tuple(status.shape) == (n,)):
+                raise RuntimeError(f"out[1] must be a contiguous int32 CUDA tensor of shape {(n,)} on {dev}")
+        if n == 0:
+            return poses, status
+        voting._check(voting.load_library().pvnet_pose_solve(
+            C.c_void_p(points_2d.data_ptr()), int(points_2d.dtype == torch.float64), (C.c_int64 * 3)(*points_2d.stride()),
+            C.c_void_p(X.data_ptr()), C.c_void_p(W.data_ptr()) if W is not None else None, kind, C.c_void_p(K.data_ptr()),
+            per_image, n, pn, int(max_iterations), None, C.c_void_p(poses.data_ptr()), C.c_void_p(status.data_ptr()),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_pose_solve")
+    return poses, status

@@ -123,6 +123,9 @@ def _load(lib_path: str) -> C.CDLL:
     lib.pvnet_vote_band_margin.argtypes = [C.c_float, C.c_void_p] + ws_tail
     lib.pvnet_vote_tuning_reload.restype = None
     lib.pvnet_vote_tuning_reload.argtypes = []
+    lib.pvnet_pose_solve.restype = C.c_int
+    lib.pvnet_pose_solve.argtypes = [C.c_void_p, C.c_int, i64p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if lib.pvnet_vote_abi_version() != 9:
         raise RuntimeError("pvnet_amd: libpvnet_vote.so ABI version mismatch; rebuild it")
     _libs[lib_path] = lib
@@ -569,6 +572,57 @@ class EvalWrapper(torch.nn.Module):
                                                       inlier_thresh=self.inlier_thresh, max_num=self.max_num)
         return ransac_voting_layer_v3(seg_pred, vertex_pred, self.round_hyp_num, inlier_thresh=self.inlier_thresh,
                                       max_num=self.max_num)
+
+
+class PoseEvalWrapper(torch.nn.Module):
+    """Backbone outputs in, poses out, on the device: ``EvalWrapper`` (fused arg-max voting) followed by the device pose solve
+    (``pnp.pnp_batch_device``) on the same stream -- the reference's evaluation loop of tools/train_linemod.py:200-215 (eval_net,
+    then ``Evaluator.evaluate`` per image on the host) without leaving the device.  With ``use_uncertainty`` it is the reference's
+    ``UncertaintyEvalWrapper`` (train_linemod.py:119-130: v3 at ``round_hyp_num``, then ``estimate_voting_distribution_with_mean``)
+    followed by the covariance-weighted solve of ``Evaluator.evaluate_uncertainty``.
+
+    points_3d [pn,3] and K [3,3] are uploaded once per device; ``forward(..., K=Ks)`` takes per-image intrinsics [b,3,3] instead
+    (the reference's ``use_camera_intrinsic`` path).  ``forward`` returns poses [b,3,4] float64; with ``return_all=True``
+    ``(poses, status, kpts, cov)`` -- status as ``pnp_batch_device``, cov None without ``use_uncertainty``."""
+
+    def __init__(self, points_3d, K, round_hyp_num=512, inlier_thresh=0.99, use_uncertainty=False, max_num=30000,
+                 max_iterations=200):
+        super().__init__()
+        import numpy as np
+        self.points_3d = np.ascontiguousarray(points_3d, np.float64)
+        self.K = np.ascontiguousarray(K, np.float64)
+        self.round_hyp_num, self.inlier_thresh, self.max_num = round_hyp_num, inlier_thresh, max_num
+        self.use_uncertainty, self.max_iterations = use_uncertainty, max_iterations
+        self._uploaded = {}
+
+    def _constants(self, dev):
+        if dev not in self._uploaded:
+            self._uploaded[dev] = (torch.from_numpy(self.points_3d).to(dev), torch.from_numpy(self.K).to(dev))
+        return self._uploaded[dev]
+
+    def forward(self, seg_pred, vertex_pred, use_argmax=True, K=None, return_all=False):
+        from . import pnp
+        vertex_pred = vertex_pred.permute(0, 2, 3, 1)
+        b, h, w, vn_2 = vertex_pred.shape
+        vertex_pred = vertex_pred.view(b, h, w, vn_2 // 2, 2)
+        X, K0 = self._constants(vertex_pred.device)
+        K = K0 if K is None else K
+        cov = None
+        if self.use_uncertainty:
+            mask = torch.argmax(seg_pred, 1) if use_argmax else seg_pred
+            kpts = ransac_voting_layer_v3(mask, vertex_pred, self.round_hyp_num, inlier_thresh=self.inlier_thresh,
+                                          max_num=self.max_num)
+            kpts, cov = estimate_voting_distribution_with_mean(mask, vertex_pred, kpts)
+            poses, status = pnp.pnp_batch_device(X, kpts, K, covariance=cov, max_iterations=self.max_iterations)
+        else:
+            if use_argmax:
+                kpts = ransac_voting_layer_v3_from_logits(seg_pred, vertex_pred, self.round_hyp_num,
+                                                          inlier_thresh=self.inlier_thresh, max_num=self.max_num)
+            else:
+                kpts = ransac_voting_layer_v3(seg_pred, vertex_pred, self.round_hyp_num, inlier_thresh=self.inlier_thresh,
+                                              max_num=self.max_num)
+            poses, status = pnp.pnp_batch_device(X, kpts, K, max_iterations=self.max_iterations)
+        return (poses, status, kpts, cov) if return_all else poses
 
 
 def _ws_tail(L: Layout, max_num: int, ws: torch.Tensor):

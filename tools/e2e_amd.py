@@ -4,7 +4,8 @@ random-init backbone for timing" -- exactly that:
 
     image [b,3,480,640] -> stand-in ResNet-18-8s (plain PyTorch-ROCm / MIOpen, RANDOM weights, the reference's tensor
     interface: seg_pred [b,2,h,w], ver_pred [b,18,h,w], lib/networks/model_repository.py:76-78)
-    -> EvalWrapper on the HIP layer (arg-max fused, tools/demo.py:46-55) -> host PnP per image (tools/demo.py:179)
+    -> EvalWrapper on the HIP layer (arg-max fused, tools/demo.py:46-55) -> host PnP per image (tools/demo.py:179),
+    or -> the device pose solve (pnp.pnp_batch_device) on the same stream: the "device pose" column
 
 A random backbone predicts a random mask, so its outputs are replaced (multiplied by zero, then added to) by the
 synthetic ground-truth logits / field of the benchmark: the backbone is timed, the voting layer sees the workload of
@@ -147,11 +148,18 @@ def main():
             t_vote = timed(lambda: head(s, v), steps)
             t_all = timed(lambda: frame(True), steps)
             t_pipe = timed_pipe(steps)
+            X3d, Kd = torch.from_numpy(X3).to(dev), torch.from_numpy(pnp.LINEMOD_K.copy()).to(dev)
+
+            def frame_device():   # the pose solve on the device, on the voting stream: no host sync inside the frame
+                s, v = backbone()
+                return pnp.pnp_batch_device(X3d, head(s, v), Kd)[0]
+            t_dev = timed(frame_device, steps)
             label = "fp32" if amp is None else ("bf16, outputs read in place" if in_place else "bf16 autocast, .float()")
             print(f"b={b:2d} backbone {label:27s}: backbone {t_bb * 1e3:7.2f} ms  voting "
                   f"{t_vote * 1e3:6.3f} ms ({100 * t_vote / (t_bb + t_vote):4.1f} % of backbone+voting)  "
                   f"end to end with host PnP {t_all * 1e3:7.2f} ms = {b / t_all:8.1f} images/s; poses of batch i solved beside the "
-                  f"backbone of batch i + 1: {t_pipe * 1e3:7.2f} ms = {b / t_pipe:8.1f} images/s", flush=True)
+                  f"backbone of batch i + 1: {t_pipe * 1e3:7.2f} ms = {b / t_pipe:8.1f} images/s; device pose: {t_dev * 1e3:7.2f} ms = "
+                  f"{b / t_dev:8.1f} images/s", flush=True)
 
 
 if __name__ == "__main__":
