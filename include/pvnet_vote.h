@@ -324,6 +324,42 @@ int pvnet_pose_solve(const void* pts2d, int pts2d_f64, const int64_t pts2d_strid
                      const void* weights, int weight_kind, const double* K, int k_per_image, int n, int pn,
                      int max_iterations, double* rt, double* poses, int32_t* status, void* stream);
 
+/* The pose metrics after the pose solve, on the device (pvnet_amd/csrc/pose_metrics.hip): what Evaluator._record computes image by
+ * image on the host (pvnet_amd/evaluation.py; the reference's lib/utils/evaluation_utils.py:75-142) -- ADD or, for symmetric
+ * classes, ADD-S; the mean 2-D projection error, or its symmetric form; the 5cm5deg pair -- for n images in one call.
+ *   pose_pred    float64 [n,3,4] (R | t), what pvnet_pose_solve writes
+ *   pose_target  [n,3,4] float32 (target_f64 == 0) or float64, widened on read
+ *   model_pts    float64 [total,3]: the model points of every class, packed; class c owns rows class_offsets[c] ..
+ *                class_offsets[c+1] - 1 (int32 [num_classes+1]); diameters float64 [num_classes]; symmetric uint8 [num_classes],
+ *                1 = ADD-S class.  All on the device.
+ *   max_points   host: the largest class's point count (sizes the grids and the workspace)
+ *   class_ids    NULL (class 0 for every image) or int32 [n] on the device
+ *   K            float64 [3,3], or [n,3,3] with k_per_image != 0; the general matrix (a negative fx is fine)
+ *   flags        0, or PVNET_METRIC_SYM_PROJECTION: the projection error of symmetric classes is the nearest-neighbour one
+ *                (projection_2d_sym, evaluate_uncertainty_v2's choice); ADD-S is used for them in any case
+ *   thresholds   host [4]: projection px (5), ADD fraction of the diameter (0.1), cm (5), degrees (5)
+ *   errors       float64 [n,4]: projection px, ADD(-S) (model units), translation cm, rotation degrees
+ *   passed       uint8 [n,3] (0 / 1): projection < th[0], ADD < diameter * th[1], cm < th[2] && degrees < th[3]
+ *   status       NULL or int32 [n]: 0; -1 for a class id outside 0 .. num_classes-1, -2 for a class whose point count is outside
+ *                1 .. max_points.  Such an image reads nothing of the class table beyond its id: NaN errors, zero flags.
+ *   workspace    device, 8-byte aligned, at least pvnet_pose_metrics_workspace_bytes(n, max_points, flags); may hold garbage
+ *                on entry.  After the call its first n * S * max_points 8-byte words (S = 2 with PVNET_METRIC_SYM_PROJECTION,
+ *                else 1) hold, for the images of symmetric classes, the search's result per target point: (float32 squared
+ *                distance bits << 32) | index of the nearest predicted point, or 0x7F7FFFFFFFFFFFFF when there is no finite
+ *                hit (index 0 is used then); search 0 is the 3-D one, search 1 the projected one.
+ * Float64 with the host's formulas term by term, no FMA contraction; the nearest-neighbour search on the float32 roundings of the
+ * two clouds, the first index winning ties, as pvnet_nearest_point_idx.  Sums are reduced in a fixed order: the outputs are
+ * bitwise reproducible.  Arguments are checked before any HIP call (PVNET_E_BADARG: a null pointer, num_classes or max_points
+ * < 1, n < 0, an unknown flag, a misaligned workspace; PVNET_E_WORKSPACE: too small; PVNET_E_UNSUPPORTED: max_points > 2^24 or
+ * n * S > 65535); n == 0 returns 0.  Nothing is allocated and nothing synchronises: only enqueues on `stream`, capturable. */
+#define PVNET_METRIC_SYM_PROJECTION 1
+size_t pvnet_pose_metrics_workspace_bytes(int n, int max_points, int flags);
+int pvnet_pose_metrics(const double* pose_pred, const void* pose_target, int target_f64, const double* model_pts,
+                       const int32_t* class_offsets, const double* diameters, const uint8_t* symmetric, int num_classes,
+                       int max_points, const int32_t* class_ids, const double* K, int k_per_image, int n, int flags,
+                       const double thresholds[4], double* errors, uint8_t* passed, int32_t* status, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ABI / build identification (host-only) */
 int pvnet_vote_abi_version(void);
 const char* pvnet_vote_build_info(void);

@@ -15,10 +15,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-# one translation unit per stage (the map is at the top of vote_host.hip), then the pose solve after voting (pose_solve.hip);
+# one translation unit per stage (the map is at the top of vote_host.hip), then the pose solve after voting (pose_solve.hip) and
+# the pose metrics after it (pose_metrics.hip);
 # pvnet_rccl.hip is host code only: the RCCL binding
 VOTE_TU = ["k1_mask.hip", "k2_compact.hip", "k3_hypotheses.hip", "k4_score_valu.hip", "k4_score_mfma.hip", "k4_score_exact.hip",
-           "k4_score_cull.hip", "k5_refine.hip", "epilogues.hip", "pose_solve.hip", "vote_host.hip"]
+           "k4_score_cull.hip", "k5_refine.hip", "epilogues.hip", "pose_solve.hip", "pose_metrics.hip", "vote_host.hip"]
 SRC = [os.path.join(CSRC, f) for f in VOTE_TU + ["pvnet_nn.hip", "pvnet_rccl.hip"]]
 DEPS = SRC + [os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "k4_exact_body.h"), os.path.join(CSRC, "pvnet_rng.h"),
               os.path.join(ROOT, "include", "pvnet_vote.h"), os.path.join(ROOT, "include", "pvnet_nn.h")]

@@ -14,6 +14,10 @@ classes (``LineModModelDB``, ``VotingType.get_pts_3d``) -- datasets are out of s
 Evaluator is constructed with them: ``Evaluator(models={cls: points [n,3]}, diameters={cls: d}, points_3d={cls: [pn,3]},
 K=...)``.  PnP is the native host solver of pvnet_amd/pnp.py instead of cv2.solvePnP / Ceres.  No CPU fallback for the
 nearest-neighbour search: without a GPU it raises.
+
+The same metrics for a whole batch on the device (``pose_metrics_device``, ``Evaluator.evaluate_batch``): the class table is
+uploaded once (``DeviceModels``) and ``pvnet_pose_metrics`` (pvnet_amd/csrc/pose_metrics.hip) scores every image on the
+current stream, the symmetric classes' nearest-neighbour search included.
 """
 from __future__ import annotations
 
@@ -88,6 +92,144 @@ def find_nearest_point_distance(pts1, pts2):
     """evaluation_utils.py:54-62: for every point of pts2 its distance to the nearest point of pts1"""
     idxs = find_nearest_point_idx(pts1, pts2)
     return np.linalg.norm(np.asarray(pts1)[idxs] - np.asarray(pts2), 2, 1)
+
+
+def _metrics_lib():
+    from . import voting
+    lib = voting.load_library()
+    if not getattr(lib, "_metrics_ready", False):
+        lib.pvnet_pose_metrics_workspace_bytes.restype = C.c_size_t
+        lib.pvnet_pose_metrics_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.pvnet_pose_metrics.restype = C.c_int
+        lib.pvnet_pose_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]
+        lib._metrics_ready = True
+    return lib
+
+
+METRIC_SYM_PROJECTION = 1               # PVNET_METRIC_SYM_PROJECTION
+METRIC_THRESHOLDS = (5.0, 0.1, 5.0, 5.0)  # projection px, ADD fraction of the diameter, cm, degrees (Evaluator's defaults)
+
+
+class DeviceModels(object):
+    """The class table of the device metrics, uploaded once: ``models`` {class: points [m,3]} packed into one float64 array
+    (float32 points are exact in float64), ``diameters`` {class: d}, and which classes are scored with ADD-S (``symmetric``,
+    by default the reference's eggbox and glue).  Classes keep the order of ``models``; ``index(class_type)`` is a class's id."""
+
+    def __init__(self, models, diameters, device, symmetric=SYMMETRIC_CLASSES):
+        import torch
+        self.classes = list(models)
+        if not self.classes:
+            raise ValueError("DeviceModels: no classes")
+        pts = [np.asarray(models[c], np.float64).reshape(-1, 3) for c in self.classes]
+        counts = [p.shape[0] for p in pts]
+        if min(counts) < 1:
+            raise ValueError("DeviceModels: every class needs at least one model point")
+        self.device = torch.device(device)
+        self.max_points = int(max(counts))
+        self.points = torch.from_numpy(np.ascontiguousarray(np.concatenate(pts, 0))).to(self.device)
+        self.offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(self.device)
+        self.diameters = torch.from_numpy(np.array([float(diameters[c]) for c in self.classes], np.float64)).to(self.device)
+        self.symmetric = torch.from_numpy(np.array([c in symmetric for c in self.classes], np.uint8)).to(self.device)
+
+    def __len__(self):
+        return len(self.classes)
+
+    def index(self, class_type):
+        return self.classes.index(class_type)
+
+
+def pose_metrics_device(pose_pred, pose_targets, K, models, class_ids=None, sym_projection=False, thresholds=METRIC_THRESHOLDS,
+                        out=None, workspace=None):
+    """The metrics of ``Evaluator._record`` for a batch, on the device (``pvnet_pose_metrics``), enqueued on the current stream --
+    no synchronisation, no host copy.
+
+    :param pose_pred:    [n,3,4] CUDA tensor (float64 as ``pnp_batch_device`` writes it; other float dtypes are widened)
+    :param pose_targets: [n,3,4] float32 / float64 CUDA tensor, or numpy (uploaded here)
+    :param K:            [3,3] shared or [n,3,3] per image (CUDA tensor or numpy)
+    :param models:       ``DeviceModels`` on the same device
+    :param class_ids:    None (class 0), a class name or id for every image, or an int32 [n] CUDA tensor of ids
+    :param sym_projection: the projection error of symmetric classes is ``projection_2d_sym``'s (evaluate_uncertainty_v2)
+    :param thresholds:   (px, ADD fraction of the diameter, cm, degrees)
+    :param out:          None, or caller-owned ``(errors [n,4] float64, passed [n,3] bool, status [n] int32)`` (graph capture)
+    :param workspace:    None, or a caller-owned uint8 CUDA tensor of at least ``pose_metrics_workspace_bytes`` bytes
+    :return: ``(errors, passed, status)``: errors = (projection px, ADD(-S), cm, degrees), passed = (projection, ADD, 5cm5deg),
+             status 0, or < 0 for a class id out of range (NaN errors, false flags)."""
+    import torch
+    from . import pnp as _pnp
+    from . import voting
+    if not (isinstance(pose_pred, torch.Tensor) and pose_pred.is_cuda):
+        raise RuntimeError("pose_pred must be a CUDA tensor [n,3,4]")
+    dev = pose_pred.device
+    if not isinstance(models, DeviceModels) or models.device != dev:
+        raise RuntimeError(f"models must be DeviceModels on {dev}")
+    if pose_pred.dim() != 3 or tuple(pose_pred.shape[1:]) != (3, 4):
+        raise RuntimeError(f"pose_pred must be [n,3,4], got {tuple(pose_pred.shape)}")
+    n = int(pose_pred.shape[0])
+    pred = pose_pred.to(torch.float64).contiguous()
+    if isinstance(pose_targets, torch.Tensor):
+        if not pose_targets.is_cuda or pose_targets.device != dev:
+            raise RuntimeError(f"pose_targets must be a CUDA tensor on {dev} (or numpy)")
+        tgt = pose_targets if pose_targets.dtype in (torch.float32, torch.float64) else pose_targets.to(torch.float64)
+        tgt = tgt.contiguous()
+    else:
+        tgt = _pnp._device_tensor(pose_targets, dev, torch.float64, "pose_targets")
+    if tuple(tgt.shape) != (n, 3, 4):
+        raise RuntimeError(f"pose_targets must be [n,3,4]={(n, 3, 4)}, got {tuple(tgt.shape)}")
+    Kd = _pnp._device_tensor(K, dev, torch.float64, "K")
+    if tuple(Kd.shape) == (3, 3):
+        per_image = 0
+    elif tuple(Kd.shape) == (n, 3, 3):
+        per_image = 1
+    else:
+        raise RuntimeError(f"K must be [3,3] or [n,3,3]={(n, 3, 3)}, got {tuple(Kd.shape)}")
+    if class_ids is None:
+        ids = None
+    elif isinstance(class_ids, torch.Tensor):
+        if not class_ids.is_cuda or class_ids.device != dev or tuple(class_ids.shape) != (n,):
+            raise RuntimeError(f"class_ids must be a CUDA tensor [n]={(n,)} on {dev}")
+        ids = class_ids.to(torch.int32).contiguous()
+    else:
+        cid = models.index(class_ids) if isinstance(class_ids, str) else int(class_ids)
+        ids = torch.full((n,), cid, dtype=torch.int32, device=dev)
+    flags = METRIC_SYM_PROJECTION if sym_projection else 0
+    th = (C.c_double * 4)(*[float(x) for x in thresholds])
+    lib = _metrics_lib()
+    with torch.cuda.device(dev):
+        if out is None:
+            errors = torch.empty((n, 4), dtype=torch.float64, device=dev)
+            passed = torch.empty((n, 3), dtype=torch.bool, device=dev)
+            status = torch.empty((n,), dtype=torch.int32, device=dev)
+        else:
+            errors, passed, status = out
+            for t, dt, shape, name in ((errors, torch.float64, (n, 4), "out[0]"), (passed, torch.bool, (n, 3), "out[1]"),
+                                       (status, torch.int32, (n,), "out[2]")):
+                if not (t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise RuntimeError(f"{name} must be a contiguous {dt} CUDA tensor of shape {shape} on {dev}")
+        if n == 0:
+            return errors, passed, status
+        nbytes = lib.pvnet_pose_metrics_workspace_bytes(n, models.max_points, flags)
+        if workspace is None:
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
+            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
+        voting._check(lib.pvnet_pose_metrics(
+            C.c_void_p(pred.data_ptr()), C.c_void_p(tgt.data_ptr()), int(tgt.dtype == torch.float64),
+            C.c_void_p(models.points.data_ptr()), C.c_void_p(models.offsets.data_ptr()), C.c_void_p(models.diameters.data_ptr()),
+            C.c_void_p(models.symmetric.data_ptr()), len(models), models.max_points,
+            C.c_void_p(ids.data_ptr()) if ids is not None else None, C.c_void_p(Kd.data_ptr()), per_image, n, flags, th,
+            C.c_void_p(errors.data_ptr()), C.c_void_p(passed.data_ptr()), C.c_void_p(status.data_ptr()),
+            C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_pose_metrics")
+    return errors, passed, status
+
+
+def pose_metrics_workspace_bytes(n, models, sym_projection=False):
+    """the workspace ``pose_metrics_device`` needs for n images of ``models`` (bytes)"""
+    return int(_metrics_lib().pvnet_pose_metrics_workspace_bytes(n, models.max_points,
+                                                                 METRIC_SYM_PROJECTION if sym_projection else 0))
 
 
 def _transform(model, pose):
@@ -218,6 +360,43 @@ class Evaluator(object):
                                          self.points_3d[class_type], K)
         self._record(pose_pred, np.asarray(pose_targets, np.float64), class_type, K, sym_projection=True)
         return pose_pred
+
+    def device_models(self, device):
+        """the constructor's models / diameters as ``DeviceModels`` on ``device`` (built on first use per device)"""
+        import torch
+        device = torch.device(device)
+        cache = self.__dict__.setdefault("_device_models", {})
+        if device not in cache:
+            cache[device] = DeviceModels(self.models, self.diameters, device)
+        return cache[device]
+
+    def evaluate_batch(self, points_2d, pose_targets, class_type, intri_type="blender", intri_matrix=None, covariance=None,
+                       sym_projection=False):
+        """``evaluate`` (or, with ``covariance``, ``evaluate_uncertainty``) for a batch of images of one class, on the device:
+        poses by ``pnp_batch_device`` from the device key-points ``points_2d`` [n,pn,2], metrics by ``pose_metrics_device``,
+        then ONE device-to-host copy that fills the same recorders ``_record`` fills.  ``intri_matrix`` may be [3,3] or
+        [n,3,3] (per image) with ``intri_type='use_intrinsic'``; ``sym_projection`` as ``evaluate_uncertainty_v2``.
+        Returns the poses [n,3,4] (float64, on the device)."""
+        import torch
+        if not (isinstance(points_2d, torch.Tensor) and points_2d.is_cuda):
+            raise RuntimeError("evaluate_batch: points_2d must be a CUDA tensor [n,pn,2]")
+        dev = points_2d.device
+        if isinstance(intri_matrix, torch.Tensor) and intri_type == "use_intrinsic":
+            K = intri_matrix.to(device=dev, dtype=torch.float64)
+        else:
+            K = self._intrinsics(intri_type, intri_matrix)
+        models = self.device_models(dev)
+        poses, _ = P.pnp_batch_device(self.points_3d[class_type], points_2d, K, covariance=covariance)
+        errors, passed, _ = pose_metrics_device(poses, pose_targets, K, models, class_ids=class_type,
+                                                sym_projection=sym_projection)
+        host = torch.cat([errors, passed.to(torch.float64)], 1).cpu().numpy()   # the one copy (it waits for the stream)
+        for e, ok in zip(host[:, :4], host[:, 4:]):
+            self.add_dists.append(float(e[1]))
+            self.add_recorder.append(bool(ok[1]))
+            self.proj_mean_diffs.append(float(e[0]))
+            self.projection_2d_recorder.append(bool(ok[0]))
+            self.cm_degree_5_recorder.append(bool(ok[2]))
+        return poses
 
     def average_precision(self, verbose=True):
         """:219-226 (the reference also dumps proj_mean_diffs to ./tmp.npy; not reproduced)"""
