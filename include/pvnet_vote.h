@@ -108,7 +108,7 @@ typedef struct PvnetVoteLayout {
                                work item holds wg_g*64*hpl hypotheses = 4 waves x (wg_g*hpl/2) MFMA tiles of 32 */
     int32_t hgroups;        /* hypothesis groups per key-point = ceil(hn / (64*hpl)) rounded up to wg_g     */
     int32_t hn_pad;         /* hgroups * 64 * hpl                                                           */
-    size_t off_ctrl;        /* int32 [b][8]: tn0, tn, status, item_base, nchunks, origin x, origin y, -  ; then [8] global: total items,
+    size_t off_ctrl;        /* int32 [b][8]: tn0, tn, status, item_base, nchunks, origin x, origin y, rho (float bits); then [8] global: total items,
                                (1,7) culling statistics, (2,3) stage-timer ticks, (4,5) band statistics (PVNET_F_BAND_STATS), (6) layout
                                fingerprint; then int32 [b][vn][2] band origins, then int32 [b][vn] 1 = key-point disc-culled */
     size_t off_bits;        /* uint64 [b][words]           foreground bit mask (as the mask has it: before thinning) */

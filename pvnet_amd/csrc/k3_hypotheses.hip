@@ -42,6 +42,8 @@ __device__ __forceinline__ void plan_image(const VoteParams& P, int bi, bool cul
         P.ctrl[bi * CTRL_STRIDE + C_OX] = pm % P.w;
         P.ctrl[bi * CTRL_STRIDE + C_OY] = pm / P.w;
         if (!nch) P.ctrl[bi * CTRL_STRIDE + C_STATUS] |= PVNET_S_SKIPPED;
+        P.ctrl[bi * CTRL_STRIDE + C_RHO] = (int)__float_as_uint(band_rho(tn));   // (the scoring kernels' staging: a scalar load per item instead of a
+                                                                                  //  correctly rounded square root per item and wave)
         if (culled && n > 0) call_flags_ptr(P)[CF_ANY_CULLED] = 1;   // (zeroed by K2; every writer writes the same)
         if (bi == P.b - 1) {
             P.ctrl[P.b * CTRL_STRIDE] = base + n;  // total number of work items
@@ -419,6 +421,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(20))) void hypo
     //  culled call's hypothesis launch -- r07k)
     const bool batch_ok = P.cull == 1 || (P.cull == 2 && call_flags_ptr(P)[CF_BATCH_OK] != 0);
     const bool live = P.ctrl[bi * CTRL_STRIDE + C_TN0] >= P.min_num && tn > 0;  // gates of :531-534
+    // (block-uniform) a key-point's block has work only when its image is culled, which the batch gate must allow first: without it the
+    // block leaves before the preamble it would otherwise repeat for nothing (the noisy benchmark field: every such block)
+    if (!LITERAL && blk > nbd && !batch_ok) return;
     __shared__ KpShared S;
     const bool kp_origin = !LITERAL && P.mode && P.exact && P.vn <= KP_MAX;   // block-uniform
     // the thread's own hypothesis: its two records are requested NOW, so that they travel while the origin is worked out

@@ -208,7 +208,7 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
         if (item_culled(desc.y)) continue;   // (workgroup-uniform) a key-point the disc-culling body scores
         const int bi = desc.x, k = item_kp(desc.y), cg = desc.z, hq = desc.w;
         const int tn = ctrl[bi * CTRL_STRIDE + C_TN];
-        const float rho = band_rho(tn);
+        const float rho = __uint_as_float((unsigned)ctrl[bi * CTRL_STRIDE + C_RHO]);   // band_rho(tn), from the plan block of K3
         const size_t bk = (size_t)bi * P.vn + k;
         const int32_t* const org = band_origin_ptr(P, bk);   // the band's origin for this key-point (hypothesis_kernel)
         const float ox = (float)org[0], oy = (float)org[1];
@@ -284,14 +284,12 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
 #define PV_LO(v, w) v[0], w[0], v[1], w[1], v[2], w[2], v[3], w[3], v[4], w[4], v[5], w[5], v[6], w[6], v[7], w[7]
 #define PV_HI(v, w) v[8], w[8], v[9], w[9], v[10], w[10], v[11], w[11], v[12], w[12], v[13], w[13], v[14], w[14], v[15], w[15]
         if (NACC == 1) {
-            for (int tile = 0; tile < nti; ++tile) {
-                const int nt = tile + 1 < nti ? tile + 1 : tile;
-                const bf16x8 Na = __builtin_bit_cast(bf16x8, lbase[nt * TILE_U4]);
-                const bf16x8 Nb = __builtin_bit_cast(bf16x8, lbase[nt * TILE_U4 + 64]);
+            // one pixel tile against the wave's MH hypothesis tiles
+            auto tile_steps = [&](const bf16x8& Ta, const bf16x8& Tb) __attribute__((always_inline)) {
 #pragma unroll
                 for (int t = 0; t < MH; ++t) {
-                    const f32x16 va = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Aa, B[t], zero, 0, 0, 0);
-                    const f32x16 vb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ab, B[t], zero, 0, 0, 0);
+                    const f32x16 va = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ta, B[t], zero, 0, 0, 0);
+                    const f32x16 vb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Tb, B[t], zero, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     if (FOLD) {   // the previous step's last 15 operations fill the wait for this step's MFMAs
                         vote_slow_close(cnt[(t + MH - 1) % MH], flg[(t + MH - 1) % MH], acc, dmo, PV_XS);
@@ -307,8 +305,20 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                Aa = Na;
-                Ab = Nb;
+            };
+            // Two pixel tiles per trip: the A operand's two register sets swap roles from the first half of the trip to the second.
+            // (One tile per trip ended with four 64-bit moves from the set just read into the set the MFMAs name: 32 vector
+            //  operations per item and wave.)  The tile behind the last one is the last one again, read and not used.
+            for (int tile = 0; tile < nti; tile += 2) {
+                const int n1 = tile + 1 < nti ? tile + 1 : tile;
+                const bf16x8 Na = __builtin_bit_cast(bf16x8, lbase[n1 * TILE_U4]);
+                const bf16x8 Nb = __builtin_bit_cast(bf16x8, lbase[n1 * TILE_U4 + 64]);
+                tile_steps(Aa, Ab);
+                if (tile + 1 >= nti) break;   // (wave-uniform)
+                const int n2 = tile + 2 < nti ? tile + 2 : tile + 1;
+                Aa = __builtin_bit_cast(bf16x8, lbase[n2 * TILE_U4]);
+                Ab = __builtin_bit_cast(bf16x8, lbase[n2 * TILE_U4 + 64]);
+                tile_steps(Na, Nb);
             }
         } else {
         f32x16 va = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Aa, B[0], zero, 0, 0, 0);
@@ -351,8 +361,9 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
         PV_PHASE(1);
         // ---- clean cells: their counts; flagged cells: into the item's list
         const unsigned all_groups = 1u;  // FOLD = 0: the one cell of the item
-        int colx = col;  // opaque copy: keeps the eight per-tile addresses below from being hoisted above the scoring loop,
-        asm volatile("" : "+v"(colx));  // where they would cost 20 VGPRs at the point of highest pressure
+        int lx = lane;   // opaque copy: keeps the eight per-tile addresses below from being hoisted above the scoring loop,
+        asm volatile("" : "+v"(lx));   // where they would cost 20 VGPRs at the point of highest pressure (and the half-wave's bit of
+        const int colx = lx & 31, halfx = lx >> 5;   // the cell word: hoisted, the merged kernel spilled it)
         const bool padded = h0 + MH * 32 > P.hn;  // wave-uniform: only the last slice can hold padding columns
         if (!FOLD) {
 #pragma unroll
@@ -375,7 +386,7 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
             int base = 0;
             if (lane == 0) base = atomicAdd(&s_ncell, ncw);
             base = __builtin_amdgcn_readfirstlane(base);
-            const unsigned cell0 = (unsigned)(wave * MH * 32 + colx) | ((unsigned)half << 10);
+            const unsigned cell0 = (unsigned)(wave * MH * 32 + colx) | ((unsigned)halfx << 10);
 #pragma unroll
             for (int t = 0; t < MH; ++t) {
                 if (bal[t]) {  // wave-uniform
@@ -411,10 +422,10 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                         ++ntests;
                     }
                 }
-                votes += __shfl_xor(votes, 8, 64);
-                votes += __shfl_xor(votes, 4, 64);
-                votes += __shfl_xor(votes, 2, 64);
-                votes += __shfl_xor(votes, 1, 64);
+                votes += (int)lane_xor((uint32_t)votes, 8);   // (DPP / ds_swizzle: no lane index, no address operand)
+                votes += (int)lane_xor((uint32_t)votes, 4);
+                votes += (int)lane_xor((uint32_t)votes, 2);
+                votes += (int)lane_xor((uint32_t)votes, 1);
                 if (q == 0 && votes > 0) atomicAdd(P.counts + bk * P.hn_pad + hslice + hl, votes);
             }
             if (P.flags & PVNET_F_BAND_STATS) {  // development aid: how much was re-evaluated (tools/exact_probe.py)

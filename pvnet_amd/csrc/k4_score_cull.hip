@@ -34,12 +34,16 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
     constexpr int MH = 8;
     // the merged kernel's allocation is the dense kernel's of the same item mapping: 136 VGPRs for contiguous runs (batches in flight: what
     // is left of the SIMD's 512 holds other streams' small stages -- at 144 the six-stream rate fell 2.8 %, r06g), 128 for a batch
-    // alone (four waves per SIMD, four workgroups of 40 KB per CU).  This body spills a few per-item constants to fit.
+    // alone (four waves per SIMD, four workgroups of 40 KB per CU).  What this body keeps across its item loop is made per use where the allocator would otherwise spill it.
     if (WIDE) PVNET_SPARE_VGPRS(135); else PVNET_SPARE_VGPRS(127);
     unsigned long long* __restrict__ stamps = reinterpret_cast<unsigned long long*>(P.pix);
     if (TIMED && !TAIL && threadIdx.x == 0) stamps[2 * blockIdx.x] = (unsigned long long)wall_clock64();
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
+    // (TAIL: an opaque copy of the thread index -- what this body derives from it is worked out here, behind the dense body, instead of
+    //  being kept for it in registers the dense body's loop needs: the merged kernel spilled them)
+    int tx0 = threadIdx.x;
+    if (TAIL) asm volatile("" : "+v"(tx0));
+    const int lane = tx0 & 63, col = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     uint4* s_t = reinterpret_cast<uint4*>(smem);                                  // 8 A tiles + the dead row's tile: 9 x 2 KB
     unsigned* s_cells = reinterpret_cast<unsigned*>(s_t + 9 * TILE_U4);           // flagged cells of this item (4 * MH * 64 slots)
@@ -101,7 +105,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
         if (!item_culled(desc.y)) continue;   // (workgroup-uniform) a key-point the full exact kernel scores
         const int bi = desc.x, k = item_kp(desc.y), cg = desc.z, hq = desc.w;
         const int tn = ctrl[bi * CTRL_STRIDE + C_TN];
-        const float rho = band_rho(tn);
+        const float rho = __uint_as_float((unsigned)ctrl[bi * CTRL_STRIDE + C_RHO]);   // band_rho(tn), from the plan block of K3
         const size_t bk = (size_t)bi * P.vn + k;
         const int32_t* const org = band_origin_ptr(P, bk);
         const float ox = (float)org[0], oy = (float)org[1];
@@ -145,14 +149,18 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             s_sig[i] = 1.f - mu;
             if (i == 0) {   // the dead row the lists are padded with: dt' = -4, cr' = 0 -- no vote, no flag
                 s_t[CULL_DEAD] = make_uint4(0u, 0u, 0u, 0u);
-                s_t[CULL_DEAD + 32] = make_uint4(0u, 0u, 0u, pk(0u, 0xC080u));
+                unsigned never = pk(0u, 0xC080u);
+                asm volatile("" : "+s"(never));   // (made here: as a loop invariant the row took four VGPRs across every item)
+                s_t[CULL_DEAD + 32] = make_uint4(0u, 0u, 0u, never);
                 s_t[CULL_DEAD + 64] = make_uint4(0u, 0u, 0u, 0u);
                 s_t[CULL_DEAD + 96] = make_uint4(0u, 0u, 0u, 0u);
             }
         }
         lds_barrier();
         PV_PHASE(0);
-        if (item + ir.step < ir.end) {   // the next item's record for this thread, if the next item is one of this kernel's
+        // (WIDE only: in 128 VGPRs the four registers did not survive the fine pass -- the record was waited for at once and spilled to
+        //  scratch, a prefetch in name only)
+        if (WIDE && item + ir.step < ir.end) {   // the next item's record for this thread, if the next item is one of this kernel's
             const int4 nd = P.items[item + ir.step];
             if (item_culled(nd.y)) {     // (workgroup-uniform)
                 const int ntn = ctrl[nd.x * CTRL_STRIDE + C_TN];
@@ -207,7 +215,9 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             if (nv) atomicAdd(&s_cv[col], nv);
             if (um) {
                 int at = atomicAdd(&s_nu[col], __popc(um));
-                uint8_t* const dst = s_list + col * CULL_NPX;
+                int colu = col;
+                asm volatile("" : "+v"(colu));   // (the list's address per use, not a register across the item loop)
+                uint8_t* const dst = s_list + colu * CULL_NPX;
                 while (um) {
                     const int r = __ffs((int)um) - 1;
                     um &= um - 1u;
@@ -298,8 +308,9 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
 #undef PV_LO
 #undef PV_HI
         PV_PHASE(2);
-        int colx = col;
-        asm volatile("" : "+v"(colx));
+        int lx = lane;
+        asm volatile("" : "+v"(lx));
+        const int colx = lx & 31, halfx = lx >> 5;
         const bool padded = h0 + MH * 32 > P.hn;
         flush_counts(bk, h0);
         unsigned long long bal[MH];   // (one slot reservation per wave and item, as in the dense body)
@@ -314,7 +325,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             int base = 0;
             if (lane == 0) base = atomicAdd(&s_ncell, ncw);
             base = __builtin_amdgcn_readfirstlane(base);
-            const unsigned cell0 = (unsigned)(wave * MH * 32 + colx) | ((unsigned)half << 10);
+            const unsigned cell0 = (unsigned)(wave * MH * 32 + colx) | ((unsigned)halfx << 10);
 #pragma unroll
             for (int t = 0; t < MH; ++t) {
                 if (bal[t]) {  // wave-uniform
@@ -352,10 +363,10 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
                         ++ntests;
                     }
                 }
-                votes += __shfl_xor(votes, 8, 64);
-                votes += __shfl_xor(votes, 4, 64);
-                votes += __shfl_xor(votes, 2, 64);
-                votes += __shfl_xor(votes, 1, 64);
+                votes += (int)lane_xor((uint32_t)votes, 8);   // (DPP / ds_swizzle: no lane index, no address operand -- __shfl_xor's was
+                votes += (int)lane_xor((uint32_t)votes, 4);   //  kept in a register across the whole item loop)
+                votes += (int)lane_xor((uint32_t)votes, 2);
+                votes += (int)lane_xor((uint32_t)votes, 1);
                 if (q == 0 && votes > 0) atomicAdd(P.cnts + bk * P.hn_pad + hslice + hl, votes);
             }
             if (P.flags & PVNET_F_BAND_STATS) {

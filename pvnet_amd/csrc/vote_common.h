@@ -18,7 +18,8 @@ namespace pvd {
 __device__ constexpr float kF1e6 = 0x1.0c6f7ap-20f;
 
 constexpr int CTRL_STRIDE = 8;
-enum { C_TN0 = 0, C_TN = 1, C_STATUS = 2, C_ITEM_BASE = 3, C_NCHUNKS = 4, C_OX = 5, C_OY = 6 };
+enum { C_TN0 = 0, C_TN = 1, C_STATUS = 2, C_ITEM_BASE = 3, C_NCHUNKS = 4, C_OX = 5, C_OY = 6,
+       C_RHO = 7 };   // band_rho(tn) as float bits: worked out once per image by the plan block, read by every scoring work item
 
 constexpr int SEG_WORDS = 64;          // a segment = 64 words = 4096 pixels: the unit of K1 / K2 workgroups
 #ifndef PVNET_K1_WAVES
