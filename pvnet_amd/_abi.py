@@ -1,0 +1,151 @@
+"""The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h).
+
+Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
+and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
+``PvnetVoteLayout``, the error codes and the header's constants.  ``voting``, ``pnp``, ``evaluation`` and ``distributed`` take them from
+here; tests/test_abi_mirror.py holds every row against the two headers.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libpvnet_vote.so")          # release build: the tuning knobs are constants
+DEV_LIB_PATH = os.path.join(_HERE, "libpvnet_vote_dev.so")  # development build (-DPVNET_DEV): PVNET_* environment knobs + every kernel variant
+# the knobs of the development build (vote_host.hip, load_tuning): with one of them in the environment the Python front end loads
+# libpvnet_vote_dev.so instead of the release library -- the knob tests, the fuzz matrix and the tuning tools work through that
+TUNING_KNOBS = ("PVNET_SCORE_MODE", "PVNET_SCORE_WGS_PER_CU", "PVNET_SCORE_HPL", "PVNET_SCORE_CHUNK", "PVNET_COMPACT_KG",
+                "PVNET_SCORE_XCD", "PVNET_SCORE_ATOMIC", "PVNET_SCORE_LDS_KB", "PVNET_SCORE_ACC", "PVNET_EXACT_FOLD",
+                "PVNET_SCORE_RUNS", "PVNET_SCORE_CULL", "PVNET_CULL_Q_MILLI", "PVNET_DEV_STAGES")
+
+# ---- the header's constants (PVNET_<name>; PVNET_VOTE_ABI_VERSION is ABI_VERSION) --------------------------------------------------
+ABI_VERSION = 9
+E_BADARG, E_WORKSPACE, E_UNSUPPORTED = -1, -2, -3
+MASK_U8, MASK_I16, MASK_I32, MASK_I64, MASK_F32, MASK_LOGITS_F32 = 0, 1, 2, 3, 4, 5
+F_LITERAL = 1
+F_NO_REFINE = 2
+F_VERTEX_F16, F_VERTEX_BF16, F_LOGITS_F16, F_LOGITS_BF16 = 4, 8, 16, 32
+F_APPROX = 64        # the round-1/2 "fast" mode: matrix-pipe scoring without the rounding-band re-evaluation
+F_BAND_STATS = 128   # development aid: count the re-evaluated cells / literal tests (exact mode)
+F_CONCURRENT = 256   # hint: other batches are in flight on other streams (see voting.concurrent_hint)
+F_CULL_ALL, F_CULL_NONE = 512, 1024   # exact mode: disc-cull every key-point / none (default: K3 selects per image on the device)
+S_SKIPPED, S_SINGULAR, S_NO_INLIER, S_OVERFLOW = 1, 2, 4, 8
+NUM_STAGES = 6
+STAGE_NAMES = ("mask_bits", "subsample", "compact", "hypotheses", "score", "select_refine")
+POSE_W_NONE, POSE_W_EXPLICIT, POSE_W_COV_F32 = 0, 1, 2
+METRIC_SYM_PROJECTION = 1
+
+
+class Layout(C.Structure):
+    """ctypes image of ``PvnetVoteLayout`` (include/pvnet_vote.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("b", "h", "w", "vn", "hn", "cap", "words", "chunk", "max_chunks", "hpl",
+                                          "hgroups", "hn_pad")] + \
+               [(n, C.c_size_t) for n in ("off_ctrl", "off_bits", "off_pix", "off_rec", "off_hyp",
+                                          "off_partial", "off_counts", "off_win", "off_seg", "off_items", "off_hypb",
+                                          "total_bytes")] + \
+               [("nseg", C.c_int32), ("wg_g", C.c_int32), ("wg_s", C.c_int32), ("reserved_", C.c_int32), ("cull", C.c_int32)] + \
+               [(n, C.c_size_t) for n in ("off_perm", "off_hyps", "off_cnts", "off_hypc")]
+
+
+# ---- the prototype of every function the two headers declare: name -> (restype, argtypes) -------------------------------------------
+_int, _size, _ptr, _f32 = C.c_int, C.c_size_t, C.c_void_p, C.c_float
+_i64p = C.POINTER(C.c_int64)   # stride arrays
+# the 22 arguments of pvnet_vote_v3: mask part (3), field part (2), sizes (5), thresholds (3), seed, image offset, idxs, flags, out,
+# status, workspace + bytes, stream
+_V3 = [_ptr, _int, _i64p, _ptr, _i64p] + [_int] * 5 + [_f32, _int, _int, C.c_uint64, _int, _ptr, C.c_uint32, _ptr, _ptr, _ptr, _size,
+                                                        _ptr]
+_WS_TAIL = [_int] * 6 + [_ptr, _size, _ptr]   # b, h, w, vn, hn, max_num, workspace, bytes, stream (the epilogues of a completed call)
+_OP_GENERATE = [_ptr, _ptr, _ptr, _ptr, _int, _int, _int, _ptr]
+_OP_VOTE = [_ptr, _ptr, _ptr, _ptr, _int, _int, _int, _f32, _ptr]
+PROTOTYPES = {
+    "pvnet_vote_abi_version": (_int, []),
+    "pvnet_vote_build_info": (C.c_char_p, []),
+    "pvnet_vote_tuning_reload": (None, []),
+    "pvnet_vote_layout": (_int, [_int] * 6 + [C.POINTER(Layout)]),
+    "pvnet_vote_workspace_bytes": (_size, [_int] * 6),
+    "pvnet_vote_v3": (_int, _V3),
+    "pvnet_vote_v3_logits": (_int, [_ptr, _i64p, _int, _ptr, _i64p] + _V3[5:]),
+    "pvnet_vote_v3_profiled": (_int, _V3 + [C.POINTER(_f32)]),
+    "pvnet_vote_v3_stage_repeat": (_int, _V3 + [_int, _int, C.POINTER(_f32)]),
+    "pvnet_vote_band_margin": (_int, [_f32, _ptr] + _WS_TAIL),
+    "pvnet_vote_confidence": (_int, [_ptr, _f32, _ptr, C.c_uint32] + _WS_TAIL),
+    "pvnet_vote_distribution": (_int, [_ptr, _ptr] + _WS_TAIL),
+    "pvnet_motion_workspace_bytes": (_size, [_int] * 4),
+    "pvnet_motion_voting": (_int, [_ptr, _int, _i64p, _ptr, _i64p] + [_int] * 4 + [_ptr, _ptr, _size, _ptr]),
+    "pvnet_motion_voting_typed": (_int, [_ptr, _int, _i64p, _ptr, _i64p] + [_int] * 4 + [C.c_uint32, _ptr, _ptr, _size, _ptr]),
+    "pvnet_generate_hypothesis": (_int, _OP_GENERATE),
+    "pvnet_voting_for_hypothesis": (_int, _OP_VOTE),
+    "pvnet_generate_hypothesis_vanishing_point": (_int, _OP_GENERATE),
+    "pvnet_voting_for_hypothesis_vanishing_point": (_int, _OP_VOTE),
+    "pvnet_pose_solve": (_int, [_ptr, _int, _i64p, _ptr, _ptr, _int, _ptr] + [_int] * 4 + [_ptr] * 4),
+    "pvnet_pose_metrics_workspace_bytes": (_size, [_int] * 3),
+    "pvnet_pose_metrics": (_int, [_ptr, _ptr, _int] + [_ptr] * 4 + [_int, _int, _ptr, _ptr, _int, _int, _int, C.POINTER(C.c_double)] +
+                           [_ptr] * 4 + [_size, _ptr]),
+    "pvnet_nearest_workspace_bytes": (_size, [_int, _int]),
+    "pvnet_nearest_point_idx": (_int, [_ptr, _ptr, _ptr] + [_int] * 5 + [_ptr, _size, _ptr]),
+    "pvnet_rccl_load": (_int, [C.c_char_p]),
+    "pvnet_rccl_unique_id": (_int, [_ptr]),
+    "pvnet_rccl_comm_init": (_int, [C.POINTER(_ptr), _int, _ptr, _int]),
+    "pvnet_rccl_comm_ranks": (_int, [_ptr, C.POINTER(_int)]),
+    "pvnet_rccl_comm_destroy": (_int, [_ptr]),
+    "pvnet_vote_allgather": (_int, [_ptr, _ptr, _size, _ptr, _ptr]),
+}
+
+_lib = None
+_libs = {}   # path -> loaded library
+
+
+def _wanted_library() -> str:
+    if os.environ.get("PVNET_VOTE_LIB"):   # development aid: an experimental build of the same ABI
+        return os.environ["PVNET_VOTE_LIB"]
+    return DEV_LIB_PATH if any(os.environ.get(k) not in (None, "") for k in TUNING_KNOBS) else LIB_PATH
+
+
+def load_library() -> C.CDLL:
+    """dlopen the in-tree HIP library; loud failure if it has not been built (python -m pvnet_amd.build).  The release library unless
+    a tuning knob is set in the environment (see TUNING_KNOBS; `reload_tuning()` re-decides after the environment changed)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    _lib = _load(_wanted_library())
+    return _lib
+
+
+def _load(lib_path: str) -> C.CDLL:
+    if lib_path in _libs:
+        return _libs[lib_path]
+    if not os.path.exists(lib_path):
+        raise RuntimeError(f"pvnet_amd: HIP library {lib_path} is missing -- build it with "
+                           f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
+    lib = C.CDLL(lib_path)
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    if lib.pvnet_vote_abi_version() != ABI_VERSION:
+        raise RuntimeError("pvnet_amd: libpvnet_vote.so ABI version mismatch; rebuild it")
+    _libs[lib_path] = lib
+    return lib
+
+
+def reload_tuning():
+    """the PVNET_* tuning environment changed: pick the library again (release without knobs, the development build with) and have
+    the development build re-read them (it reads them once, at its first call; the release build's knobs are constants)."""
+    global _lib
+    _lib = _load(_wanted_library())
+    _lib.pvnet_vote_tuning_reload()
+
+
+_ERROR_NAMES = {E_BADARG: "PVNET_E_BADARG", E_WORKSPACE: "PVNET_E_WORKSPACE", E_UNSUPPORTED: "PVNET_E_UNSUPPORTED"}
+
+
+def _check(rc: int, what: str):
+    if rc == 0:
+        return
+    raise RuntimeError(f"{what} failed: {_ERROR_NAMES.get(rc, 'hipError_t ' + str(rc))}")
+
+
+def vote_layout(b, h, w, vn, hn, max_num) -> Layout:
+    L = Layout()
+    _check(load_library().pvnet_vote_layout(b, h, w, vn, hn, max_num, C.byref(L)), "pvnet_vote_layout")
+    return L

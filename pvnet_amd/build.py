@@ -69,7 +69,7 @@ def compile_link(out: str, dev: bool, verbose: bool = False) -> None:
     # vote_host.hip last: pvnet_vote_build_info() reports how many kernels the library holds, counted in the other objects
     # (kernel descriptor symbols `<name>.kd` of their device code)
     jobs = [(src, obj) for src, obj in zip(SRC, objs) if not src.endswith("vote_host.hip")]
-    with ThreadPoolExecutor(max_workers=min(len(jobs), max(1, (os.cpu_count() or 4) - 1))) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(jobs), 16, max(1, (os.cpu_count() or 4) - 1))) as ex:
         list(ex.map(one, jobs))
     names = set()
     for _, obj in jobs:

@@ -14,78 +14,46 @@ namespace {
 // tile, two accumulator pairs) and, at 8 tiles per wave, one accumulator pair with strided items (a batch alone) or contiguous runs
 // (batches in flight), each also with the clock stamps of the profiling entry.  Cells of a whole work item (PVNET_EXACT_FOLD=0), two
 // accumulator pairs at 8 tiles (PVNET_SCORE_ACC=2) and the stamped forms of the small shapes are development builds (-DPVNET_DEV).
-template <int MH, int FOLD, bool TIMED, int NACC, bool RUNS> struct ScoreExact;
+// The set of built (MH, FOLD, TIMED, NACC, RUNS) variants with their register budgets is PV_SCORE_EXACT_SET, stated once: the kernels
+// are defined from it and launch_score_exact dispatches over it, so a combination outside it is PVNET_E_UNSUPPORTED in that library.
+#define PV_SCORE_EXACT4(X, MH_, NACC_, RUNS_, NVGPR_)                                                                    \
+    X(MH_, 0, 0, NACC_, RUNS_, NVGPR_) X(MH_, 0, 1, NACC_, RUNS_, NVGPR_)                                                \
+    X(MH_, 1, 0, NACC_, RUNS_, NVGPR_) X(MH_, 1, 1, NACC_, RUNS_, NVGPR_)
+#ifdef PVNET_DEV
+#define PV_SCORE_EXACT_SET(X)                                                                                            \
+    PV_SCORE_EXACT4(X, 1, 2, 0, 104) PV_SCORE_EXACT4(X, 2, 2, 0, 104) PV_SCORE_EXACT4(X, 4, 2, 0, 136)                   \
+    PV_SCORE_EXACT4(X, 8, 1, 0, 120) PV_SCORE_EXACT4(X, 8, 2, 0, 160)                                                    \
+    PV_SCORE_EXACT4(X, 8, 1, 1, 128) PV_SCORE_EXACT4(X, 8, 2, 1, 160)
+#else
+#define PV_SCORE_EXACT_SET(X)                                                                                            \
+    X(1, 1, 0, 2, 0, 104) X(2, 1, 0, 2, 0, 104) X(4, 1, 0, 2, 0, 136)                                                    \
+    X(8, 1, 0, 1, 0, 120) X(8, 1, 1, 1, 0, 120)                                                                          \
+    X(8, 1, 0, 1, 1, 128) X(8, 1, 1, 1, 1, 128)
+#endif
 #define PV_DEF_SCORE_EXACT(MH_, FOLD_, TIMED_, NACC_, RUNS_, NVGPR_)                                                     \
     __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8), amdgpu_num_vgpr(NVGPR_ / 2))) void       \
         score_exact_kernel_##MH_##_##FOLD_##_##TIMED_##_##NACC_##_##RUNS_(VoteParams P) {                                \
         score_exact_body<MH_, FOLD_, TIMED_ != 0, NACC_, RUNS_ != 0>(P);                                                 \
-    }                                                                                                                    \
-    template <> struct ScoreExact<MH_, FOLD_, TIMED_ != 0, NACC_, RUNS_ != 0> {                                          \
-        static constexpr void (*kernel)(VoteParams) = score_exact_kernel_##MH_##_##FOLD_##_##TIMED_##_##NACC_##_##RUNS_; \
-    };
-#define PV_DEF_SCORE_EXACT4(MH_, NACC_, RUNS_, NVGPR_)                                                                   \
-    PV_DEF_SCORE_EXACT(MH_, 0, 0, NACC_, RUNS_, NVGPR_) PV_DEF_SCORE_EXACT(MH_, 0, 1, NACC_, RUNS_, NVGPR_)              \
-    PV_DEF_SCORE_EXACT(MH_, 1, 0, NACC_, RUNS_, NVGPR_) PV_DEF_SCORE_EXACT(MH_, 1, 1, NACC_, RUNS_, NVGPR_)
-#ifdef PVNET_DEV
-PV_DEF_SCORE_EXACT4(1, 2, 0, 104) PV_DEF_SCORE_EXACT4(2, 2, 0, 104) PV_DEF_SCORE_EXACT4(4, 2, 0, 136)
-PV_DEF_SCORE_EXACT4(8, 1, 0, 120) PV_DEF_SCORE_EXACT4(8, 2, 0, 160)
-PV_DEF_SCORE_EXACT4(8, 1, 1, 128) PV_DEF_SCORE_EXACT4(8, 2, 1, 160)
-#else
-PV_DEF_SCORE_EXACT(1, 1, 0, 2, 0, 104) PV_DEF_SCORE_EXACT(2, 1, 0, 2, 0, 104) PV_DEF_SCORE_EXACT(4, 1, 0, 2, 0, 136)
-PV_DEF_SCORE_EXACT(8, 1, 0, 1, 0, 120) PV_DEF_SCORE_EXACT(8, 1, 1, 1, 0, 120)
-PV_DEF_SCORE_EXACT(8, 1, 0, 1, 1, 128) PV_DEF_SCORE_EXACT(8, 1, 1, 1, 1, 128)
-#endif
-#undef PV_DEF_SCORE_EXACT4
+    }
+PV_SCORE_EXACT_SET(PV_DEF_SCORE_EXACT)
 #undef PV_DEF_SCORE_EXACT
 
 }  // namespace
 
-// one_acc / runs: one accumulator pair / contiguous item runs (8 tiles per wave only); cells: P.fold1
+// one_acc / runs: one accumulator pair / contiguous item runs (8 tiles per wave only: fewer tiles have two pairs, strided items);
+// cells: P.fold1
 int launch_score_exact(const VoteParams& P, dim3 g, size_t lds, hipStream_t s, bool timed, bool one_acc, bool runs) {
     const int mh = P.wg_g * P.hpl / 2;
-    const dim3 t(256);
-#ifdef PVNET_DEV
-    const int fold = P.fold1;
-#define PV_EXACT3(MH_, NACC_, RUNS_)                                                                                \
-    do {                                                                                                            \
-        if (timed) {                                                                                                \
-            if (fold == 1) hipLaunchKernelGGL((ScoreExact<MH_, 1, true, NACC_, RUNS_>::kernel), g, t, lds, s, P);   \
-            else hipLaunchKernelGGL((ScoreExact<MH_, 0, true, NACC_, RUNS_>::kernel), g, t, lds, s, P);             \
-        } else {                                                                                                    \
-            if (fold == 1) hipLaunchKernelGGL((ScoreExact<MH_, 1, false, NACC_, RUNS_>::kernel), g, t, lds, s, P);  \
-            else hipLaunchKernelGGL((ScoreExact<MH_, 0, false, NACC_, RUNS_>::kernel), g, t, lds, s, P);            \
-        }                                                                                                           \
-    } while (0)
-    switch (mh) {
-        case 1: PV_EXACT3(1, 2, false); break;
-        case 2: PV_EXACT3(2, 2, false); break;
-        case 4: PV_EXACT3(4, 2, false); break;
-        case 8:
-            if (runs) { if (one_acc) PV_EXACT3(8, 1, true); else PV_EXACT3(8, 2, true); }
-            else { if (one_acc) PV_EXACT3(8, 1, false); else PV_EXACT3(8, 2, false); }
-            break;
-        default: return PVNET_E_UNSUPPORTED;
+    const int fold = P.fold1 ? 1 : 0, nacc = (mh == 8 && one_acc) ? 1 : 2;
+    const bool r = mh == 8 && runs;
+#define PV_TRY_SCORE_EXACT(MH_, FOLD_, TIMED_, NACC_, RUNS_, NVGPR_)                                                     \
+    if (mh == MH_ && fold == FOLD_ && timed == (TIMED_ != 0) && nacc == NACC_ && r == (RUNS_ != 0)) {                    \
+        hipLaunchKernelGGL(score_exact_kernel_##MH_##_##FOLD_##_##TIMED_##_##NACC_##_##RUNS_, g, dim3(256), lds, s, P);  \
+        return 0;                                                                                                        \
     }
-#undef PV_EXACT3
-#else
-    if (!P.fold1 || (mh == 8 && !one_acc) || (timed && mh != 8)) return PVNET_E_UNSUPPORTED;   // development-build variants
-    switch (mh) {
-        case 1: hipLaunchKernelGGL((ScoreExact<1, 1, false, 2, false>::kernel), g, t, lds, s, P); break;
-        case 2: hipLaunchKernelGGL((ScoreExact<2, 1, false, 2, false>::kernel), g, t, lds, s, P); break;
-        case 4: hipLaunchKernelGGL((ScoreExact<4, 1, false, 2, false>::kernel), g, t, lds, s, P); break;
-        case 8:
-            if (runs) {
-                if (timed) hipLaunchKernelGGL((ScoreExact<8, 1, true, 1, true>::kernel), g, t, lds, s, P);
-                else hipLaunchKernelGGL((ScoreExact<8, 1, false, 1, true>::kernel), g, t, lds, s, P);
-            } else {
-                if (timed) hipLaunchKernelGGL((ScoreExact<8, 1, true, 1, false>::kernel), g, t, lds, s, P);
-                else hipLaunchKernelGGL((ScoreExact<8, 1, false, 1, false>::kernel), g, t, lds, s, P);
-            }
-            break;
-        default: return PVNET_E_UNSUPPORTED;
-    }
-#endif
-    return 0;
+    PV_SCORE_EXACT_SET(PV_TRY_SCORE_EXACT)
+#undef PV_TRY_SCORE_EXACT
+    return PVNET_E_UNSUPPORTED;   // not built in this library (release: a development variant), or no such tile count
 }
 
 }  // namespace pvd

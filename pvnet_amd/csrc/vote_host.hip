@@ -48,7 +48,8 @@
 //   k4_score_valu.hip    K4 literal mode       k4_score_mfma.hip  K4 approximate mode
 //   k4_exact_body.h / k4_score_exact.hip   K4 exact mode, dense        k4_score_cull.hip  K4 exact mode, dense + disc-culled items in one launch
 //   k5_refine.hip        K5    epilogues.hip   confidence / distribution / motion voting / the four ops / band margin + their C entries
-//   vote_host.hip        this file: rounding-band constant, tuning, layout, parameter block, the launch sequence, the C ABI of the layer
+//   vote_host.hip        this file: rounding-band constant, tuning, layout, parameter block, the scoring-launch plan (plan_score), the
+//                        launch sequence, the C ABI of the layer (its four voting entries share PV_V3_PROLOGUE)
 //   pvnet_nn.hip, pvnet_rccl.hip   nearest-neighbour search (ADD-S), the library's own RCCL all-gather
 #include "vote_common.h"
 
@@ -139,9 +140,59 @@ void load_tuning(Tuning& t) {
         n = 256;
     t.cus = n;
 }
+// PVNET_SCORE_CULL with its default resolved: 0 = never, 1 = every key-point, 2 = the key-points K3 selects
+int cull_knob_of(const Tuning& t) { return t.score_cull >= 0 ? t.score_cull : PVNET_CULL_DEFAULT; }
 Tuning& tuning() {
     static Tuning t = [] { Tuning x; load_tuning(x); return x; }();  // thread-safe one-time initialisation
     return t;
+}
+
+// Scoring workgroups per CU when PVNET_SCORE_WGS_PER_CU is not set: 8; 12 for an exact-mode batch alone at 8 tiles per wave (the
+// four-waves-per-SIMD kernel: three rounds of four resident workgroups; measured with it only).  WGS_PER_CU_LARGEST is the bound
+// pvnet_vote_v3_stage_repeat puts on ANY call's grid when it decides whether the clock stamps fit.
+constexpr int WGS_PER_CU_DEFAULT = 8, WGS_PER_CU_ALONE8 = 12;
+constexpr int WGS_PER_CU_LARGEST = WGS_PER_CU_ALONE8 > WGS_PER_CU_DEFAULT ? WGS_PER_CU_ALONE8 : WGS_PER_CU_DEFAULT;
+// workgroups of the persistent scoring grid before the clamp to the call's work items (a knob of 0: one workgroup per item = `unbounded`)
+long long score_wgs(const Tuning& T, int dflt_per_cu, long long unbounded) {
+    const int per_cu = T.wgs_per_cu >= 0 ? T.wgs_per_cu : dflt_per_cu;
+    return per_cu > 0 ? (long long)T.cus * per_cu : unbounded;
+}
+
+// What the scoring launch (K4) of a call is: which kernel family, its grid, its dynamic LDS, the exact mode's variant.
+struct ScorePlan {
+    enum Family { BOTH, EXACT, MFMA, VALU } family;   // dense + disc-culled items in one launch / dense exact / approximate / VALU
+    unsigned grid;
+    size_t lds;      // EXACT and MFMA (the other two launchers size their own)
+    bool one_acc;    // exact mode, 8 tiles per wave: one accumulator pair
+    bool runs;       //                              contiguous item runs per workgroup
+};
+ScorePlan plan_score(const VoteParams& P, const Tuning& T) {
+    ScorePlan sp;
+    const bool literal = (P.flags & PVNET_F_LITERAL) != 0;
+    const bool conc = (P.flags & PVNET_F_CONCURRENT) != 0;
+    const int mh = P.wg_g * P.hpl / 2;   // hypothesis tiles per wave
+    const long long max_items =
+        (long long)P.b * P.vn * (P.hgroups / P.wg_g) * ((P.max_chunks + P.wg_s - 1) / P.wg_s);
+    const bool alone8 = P.exact && mh == 8 && !conc && T.score_acc != 2 && T.score_runs != 1;
+    long long wgs = score_wgs(T, alone8 ? WGS_PER_CU_ALONE8 : WGS_PER_CU_DEFAULT, max_items);
+    if (wgs > max_items) wgs = max_items;
+    if (wgs < 1) wgs = 1;
+    sp.grid = (unsigned)wgs;
+    // exact mode, 8 tiles per wave -- calls flagged PVNET_F_CONCURRENT (other batches in flight): contiguous runs, one accumulator
+    // pair, three waves per SIMD (136 VGPRs; four cost 6 % there: profiles/r04_ab_runs.txt); a batch alone: strided items, one pair
+    // in 128 VGPRs = four waves per SIMD (kernel -2 %), 12 workgroups per CU.  Development builds: PVNET_SCORE_ACC=2 /
+    // PVNET_SCORE_RUNS force the round-3 form (two pairs, 168 VGPRs) / either mapping; runs need cells of one pixel tile.
+    sp.one_acc = T.score_acc == 1 || T.score_acc < 0;
+    sp.runs = T.score_runs == 1 || (T.score_runs < 0 && conc);  // (cells of a whole item: the same 136-VGPR kernel, strided items)
+    // key-points may be disc-culled (K3 decides per image; PVNET_F_CULL_ALL: all of them): ONE launch scores both kinds of
+    // item (score_exact_kernel_both_*), with the dense kernel's registers, LDS and grid
+    sp.family = (P.exact && P.cull) ? ScorePlan::BOTH : P.exact ? ScorePlan::EXACT : (!literal && P.mode) ? ScorePlan::MFMA : ScorePlan::VALU;
+    sp.lds = sp.family == ScorePlan::EXACT  ? exact_body_lds_bytes(P.wg_s * P.chunk, mh)
+             : sp.family == ScorePlan::MFMA ? (size_t)(P.wg_s * P.chunk / 32) * TILE_U4 * sizeof(uint4)
+                                            : 0;
+    const size_t floor = (size_t)T.score_lds_kb * 1024;   // PVNET_SCORE_LDS_KB (development builds)
+    if (sp.lds && T.score_lds_kb > 0 && T.score_lds_kb <= 64 && sp.lds < floor) sp.lds = floor;
+    return sp;
 }
 
 int launch_all(const VoteParams& P, hipStream_t s, hipEvent_t* ev, int stage_mask = -1, bool timed_score = false,
@@ -169,39 +220,14 @@ int launch_all(const VoteParams& P, hipStream_t s, hipEvent_t* ev, int stage_mas
     PV_LAUNCH_CHECK();
     PV_HIP(mark(4));
     if (stages & 16) {   // K4: persistent grid, work items strided over its waves
-        const long long max_items =
-            (long long)P.b * P.vn * (P.hgroups / P.wg_g) * ((P.max_chunks + P.wg_s - 1) / P.wg_s);
-        // (12: the four-waves-per-SIMD scoring kernel of a batch alone, three rounds of four resident workgroups; measured with it only)
-        const bool conc = (P.flags & PVNET_F_CONCURRENT) != 0;
-        const bool alone8 = P.exact && P.wg_g * P.hpl / 2 == 8 && !conc && T.score_acc != 2 && T.score_runs != 1;
-        const int wgs_per_cu = T.wgs_per_cu >= 0 ? T.wgs_per_cu : (alone8 ? 12 : 8);
-        long long wgs = wgs_per_cu > 0 ? (long long)T.cus * wgs_per_cu : max_items;  // 0: one workgroup per item
-        if (wgs > max_items) wgs = max_items;
-        if (wgs < 1) wgs = 1;
-        if (score_grid) *score_grid = (int)wgs;
-        const dim3 g((unsigned)wgs);
-        // exact mode, 8 tiles per wave -- calls flagged PVNET_F_CONCURRENT (other batches in flight): contiguous runs, one accumulator
-        // pair, three waves per SIMD (136 VGPRs; four cost 6 % there: profiles/r04_ab_runs.txt); a batch alone: strided items, one pair
-        // in 128 VGPRs = four waves per SIMD (kernel -2 %), 12 workgroups per CU.  Development builds: PVNET_SCORE_ACC=2 /
-        // PVNET_SCORE_RUNS force the round-3 form (two pairs, 168 VGPRs) / either mapping; runs need cells of one pixel tile.
-        const bool one_acc = T.score_acc == 1 || T.score_acc < 0;
-        const bool runs = T.score_runs == 1 || (T.score_runs < 0 && conc);  // (cells of a whole item: the same 136-VGPR kernel, strided items)
-        if (P.exact && P.cull) {
-            // key-points may be disc-culled (K3 decides per image; PVNET_F_CULL_ALL: all of them): ONE launch scores both kinds of
-            // item (score_exact_kernel_both_*), with the dense kernel's registers, LDS and grid
-            rc = launch_score_both(P, g, s, timed_score, runs);
-        } else if (P.exact) {
-            const int mh = P.wg_g * P.hpl / 2;
-            const int npx = P.wg_s * P.chunk;
-            size_t lds = exact_body_lds_bytes(npx, mh);
-            if (T.score_lds_kb > 0 && T.score_lds_kb <= 64 && lds < (size_t)T.score_lds_kb * 1024) lds = (size_t)T.score_lds_kb * 1024;
-            rc = launch_score_exact(P, g, lds, s, timed_score, one_acc, runs);
-        } else if (!literal && P.mode) {
-            size_t lds = (size_t)(P.wg_s * P.chunk / 32) * TILE_U4 * sizeof(uint4);
-            if (T.score_lds_kb > 0 && T.score_lds_kb <= 64 && lds < (size_t)T.score_lds_kb * 1024) lds = (size_t)T.score_lds_kb * 1024;
-            rc = launch_score_mfma(P, g, lds, s, timed_score);
-        } else {
-            rc = launch_score_valu(P, g, s, literal);
+        const ScorePlan sp = plan_score(P, T);
+        if (score_grid) *score_grid = (int)sp.grid;
+        const dim3 g(sp.grid);
+        switch (sp.family) {
+            case ScorePlan::BOTH: rc = launch_score_both(P, g, s, timed_score, sp.runs); break;
+            case ScorePlan::EXACT: rc = launch_score_exact(P, g, sp.lds, s, timed_score, sp.one_acc, sp.runs); break;
+            case ScorePlan::MFMA: rc = launch_score_mfma(P, g, sp.lds, s, timed_score); break;
+            case ScorePlan::VALU: rc = launch_score_valu(P, g, s, literal); break;
         }
         if (rc) return rc;
         PV_LAUNCH_CHECK();
@@ -281,7 +307,7 @@ int fill_params(VoteParams& P, const void* mask, int mask_dtype, const int64_t* 
     // (PVNET_SCORE_CULL=1) or the ones K3 selects (2: the default)
     // (development builds: PVNET_SCORE_CULL = 0 / 1 / 2 also shapes the layout); PVNET_F_CULL_ALL / PVNET_F_CULL_NONE override the
     // selection per call where the layout has the buffers -- every choice gives the same counts
-    const int cull_knob = tuning().score_cull >= 0 ? tuning().score_cull : PVNET_CULL_DEFAULT;
+    const int cull_knob = cull_knob_of(tuning());
     if ((flags & PVNET_F_CULL_ALL) && (flags & PVNET_F_CULL_NONE)) return PVNET_E_BADARG;
     P.cull = (L.cull && P.exact && P.fold1 && vn <= KP_MAX) ? ((cull_knob == 1 || (flags & PVNET_F_CULL_ALL)) ? 1 : 2) : 0;
     if (flags & PVNET_F_CULL_NONE) P.cull = 0;
@@ -348,7 +374,7 @@ int pvnet_vote_layout(int b, int h, int w, int vn, int hn, int max_num, PvnetVot
     int chunk = units >= 128 ? 128 : 64;
     // disc culling works on 256-pixel items (two chunks of 128); PVNET_SCORE_CULL=1 (every key-point culled: tests, probes) gives
     // small batches that shape too, the default (2: K3 selects) leaves their layout alone
-    const int cull_knob = T.score_cull >= 0 ? T.score_cull : PVNET_CULL_DEFAULT;
+    const int cull_knob = cull_knob_of(T);
     if (cull_knob == 1 && mode && T.score_atomic && wg_g * hpl / 2 == 8 && hgroups * 64 * hpl == CULL_HN) chunk = CULL_NPX / (4 / wg_g);
     if (T.chunk >= 0) chunk = T.chunk;
     if (chunk < PAD || chunk % PAD != 0 || chunk > 1024) return PVNET_E_UNSUPPORTED;  // LDS: 4 * 1024 * 32 B
@@ -404,16 +430,22 @@ size_t pvnet_vote_workspace_bytes(int b, int h, int w, int vn, int hn, int max_n
     return pvnet_vote_layout(b, h, w, vn, hn, max_num, &L) == 0 ? L.total_bytes : 0;
 }
 
+// The prologue of the four pvnet_vote_v3* entries: their common arguments (named as in include/pvnet_vote.h, identically in all
+// four) -> the parameter block `P`, the stream `s` and `rc`; returns the entry's error code where the arguments are refused.
+#define PV_V3_PROLOGUE(mask_, mask_dtype_, mask_strides_)                                                                 \
+    VoteParams P;                                                                                                         \
+    int rc = fill_params(P, mask_, mask_dtype_, mask_strides_, vertex, vertex_strides, b, h, w, vn, hn, inlier_thresh,    \
+                         min_num, max_num, seed, image_base, idxs, flags, out_kpts, out_status, workspace,                \
+                         workspace_bytes);                                                                                \
+    if (rc) return rc;                                                                                                    \
+    hipStream_t s = static_cast<hipStream_t>(stream)
+
 int pvnet_vote_v3(const void* mask, int mask_dtype, const int64_t mask_strides[3], const float* vertex,
                   const int64_t vertex_strides[5], int b, int h, int w, int vn, int hn, float inlier_thresh,
                   int min_num, int max_num, uint64_t seed, int image_base, const int32_t* idxs, uint32_t flags,
                   float* out_kpts, int32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
-    VoteParams P;
-    int rc = fill_params(P, mask, mask_dtype, mask_strides, vertex, vertex_strides, b, h, w, vn, hn, inlier_thresh,
-                         min_num, max_num, seed, image_base, idxs, flags, out_kpts, out_status, workspace,
-                         workspace_bytes);
-    if (rc) return rc;
-    return launch_all(P, static_cast<hipStream_t>(stream), nullptr);
+    PV_V3_PROLOGUE(mask, mask_dtype, mask_strides);
+    return launch_all(P, s, nullptr);
 }
 
 int pvnet_vote_v3_logits(const float* seg_pred, const int64_t seg_strides[4], int num_classes, const float* vertex,
@@ -423,14 +455,10 @@ int pvnet_vote_v3_logits(const float* seg_pred, const int64_t seg_strides[4], in
                          void* stream) {
     if (!seg_strides || num_classes < 1) return PVNET_E_BADARG;
     const int64_t ms[3] = {seg_strides[0], seg_strides[2], seg_strides[3]};  // (b, y, x); class stride separately
-    VoteParams P;
-    int rc = fill_params(P, seg_pred, PVNET_MASK_LOGITS_F32, ms, vertex, vertex_strides, b, h, w, vn, hn,
-                         inlier_thresh, min_num, max_num, seed, image_base, idxs, flags, out_kpts, out_status,
-                         workspace, workspace_bytes);
-    if (rc) return rc;
+    PV_V3_PROLOGUE(seg_pred, PVNET_MASK_LOGITS_F32, ms);
     P.ms_c = seg_strides[1];
     P.num_classes = num_classes;
-    return launch_all(P, static_cast<hipStream_t>(stream), nullptr);
+    return launch_all(P, s, nullptr);
 }
 
 int pvnet_vote_v3_profiled(const void* mask, int mask_dtype, const int64_t mask_strides[3], const float* vertex,
@@ -439,12 +467,7 @@ int pvnet_vote_v3_profiled(const void* mask, int mask_dtype, const int64_t mask_
                            const int32_t* idxs, uint32_t flags, float* out_kpts, int32_t* out_status,
                            void* workspace, size_t workspace_bytes, void* stream, float* stage_ms) {
     if (!stage_ms) return PVNET_E_BADARG;
-    VoteParams P;
-    int rc = fill_params(P, mask, mask_dtype, mask_strides, vertex, vertex_strides, b, h, w, vn, hn, inlier_thresh,
-                         min_num, max_num, seed, image_base, idxs, flags, out_kpts, out_status, workspace,
-                         workspace_bytes);
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    PV_V3_PROLOGUE(mask, mask_dtype, mask_strides);
     hipEvent_t ev[PVNET_NUM_STAGES + 1];
     int created = 0;
     for (; created <= PVNET_NUM_STAGES; ++created)
@@ -474,12 +497,7 @@ int pvnet_vote_v3_stage_repeat(const void* mask, int mask_dtype, const int64_t m
                                void* workspace, size_t workspace_bytes, void* stream, int stage, int repeats,
                                float* avg_ms) {
     if (!avg_ms || stage < 0 || stage >= PVNET_NUM_STAGES || repeats < 1) return PVNET_E_BADARG;
-    VoteParams P;
-    int rc = fill_params(P, mask, mask_dtype, mask_strides, vertex, vertex_strides, b, h, w, vn, hn, inlier_thresh,
-                         min_num, max_num, seed, image_base, idxs, flags, out_kpts, out_status, workspace,
-                         workspace_bytes);
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    PV_V3_PROLOGUE(mask, mask_dtype, mask_strides);
     hipEvent_t ev[2];
     if (hipEventCreate(&ev[0]) != hipSuccess) return (int)hipErrorOutOfMemory;
     if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); return (int)hipErrorOutOfMemory; }
@@ -490,10 +508,10 @@ int pvnet_vote_v3_stage_repeat(const void* mask, int mask_dtype, const int64_t m
     // the matrix-pipe scoring kernel once more, `repeats` times, stamping the device clock itself (fast mode only)
     // ticks accumulate in the spare words of ctrl's global row; the stamps live in `pix` (consumed by K3 only; a later
     // complete call rewrites it), when the scoring grid's slots fit there
-    const int wgs_cu = tuning().wgs_per_cu >= 0 ? tuning().wgs_per_cu : 12;
-    const long long score_wgs = wgs_cu > 0 ? (long long)tuning().cus * wgs_cu : (1ll << 40);
+    // (an upper bound on the grid of plan_score: the largest default per CU, not the call's own figure)
+    const long long wgs_bound = score_wgs(tuning(), WGS_PER_CU_LARGEST, 1ll << 40);
     const bool device_clock = stage == PVNET_STAGE_SCORE && !(P.flags & PVNET_F_LITERAL) && P.mode &&
-                              score_wgs * 48 <= (long long)sizeof(int32_t) * P.b * P.cap;
+                              wgs_bound * 48 <= (long long)sizeof(int32_t) * P.b * P.cap;
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(P.ctrl + P.b * CTRL_STRIDE + 2);
     if (rc == 0 && device_clock) {
         for (int i = 0; rc == 0 && i < repeats; ++i) {
@@ -525,5 +543,6 @@ int pvnet_vote_v3_stage_repeat(const void* mask, int mask_dtype, const int64_t m
     (void)hipEventDestroy(ev[1]);
     return rc;
 }
+#undef PV_V3_PROLOGUE
 
 }  // extern "C"

@@ -17,6 +17,8 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from . import _abi
+
 
 def shard_range(total: int, world: int, rank: int) -> Tuple[int, int]:
     """contiguous block of images owned by ``rank`` (blocks differ by at most one image)."""
@@ -37,20 +39,7 @@ class RcclGather:
     """
 
     def __init__(self, device, group=None, lib_path: Optional[str] = None):
-        from . import voting
-        self.lib = voting.load_library()
-        self.lib.pvnet_rccl_load.restype = C.c_int
-        self.lib.pvnet_rccl_load.argtypes = [C.c_char_p]
-        self.lib.pvnet_rccl_unique_id.restype = C.c_int
-        self.lib.pvnet_rccl_unique_id.argtypes = [C.c_void_p]
-        self.lib.pvnet_rccl_comm_init.restype = C.c_int
-        self.lib.pvnet_rccl_comm_init.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int]
-        self.lib.pvnet_rccl_comm_ranks.restype = C.c_int
-        self.lib.pvnet_rccl_comm_ranks.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-        self.lib.pvnet_rccl_comm_destroy.restype = C.c_int
-        self.lib.pvnet_rccl_comm_destroy.argtypes = [C.c_void_p]
-        self.lib.pvnet_vote_allgather.restype = C.c_int
-        self.lib.pvnet_vote_allgather.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        self.lib = _abi.load_library()
         self.device = torch.device(device)
         if lib_path is None:  # the librccl the process already has (PyTorch-ROCm ships one), else the system's
             cand = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")
@@ -62,7 +51,7 @@ class RcclGather:
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         uid = torch.zeros(128, dtype=torch.uint8)
         if self.rank == 0:
-            voting._check(self.lib.pvnet_rccl_unique_id(C.c_void_p(uid.data_ptr())), "pvnet_rccl_unique_id")
+            _abi._check(self.lib.pvnet_rccl_unique_id(C.c_void_p(uid.data_ptr())), "pvnet_rccl_unique_id")
         if self.world > 1:
             on_dev = dist.get_backend(group) == "nccl"
             t = uid.to(self.device) if on_dev else uid
@@ -70,13 +59,12 @@ class RcclGather:
             uid = t.cpu()
         self.comm = C.c_void_p()
         with torch.cuda.device(self.device):
-            voting._check(self.lib.pvnet_rccl_comm_init(C.byref(self.comm), self.world, C.c_void_p(uid.data_ptr()), self.rank),
+            _abi._check(self.lib.pvnet_rccl_comm_init(C.byref(self.comm), self.world, C.c_void_p(uid.data_ptr()), self.rank),
                           "pvnet_rccl_comm_init")
 
     def ranks(self) -> int:
         n = C.c_int(0)
-        from . import voting
-        voting._check(self.lib.pvnet_rccl_comm_ranks(self.comm, C.byref(n)), "pvnet_rccl_comm_ranks")
+        _abi._check(self.lib.pvnet_rccl_comm_ranks(self.comm, C.byref(n)), "pvnet_rccl_comm_ranks")
         return int(n.value)
 
     def all_gather(self, out: torch.Tensor, local: torch.Tensor) -> torch.Tensor:

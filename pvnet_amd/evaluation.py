@@ -27,21 +27,9 @@ import time
 import numpy as np
 
 from . import pnp as P
+from ._abi import METRIC_SYM_PROJECTION, _check, load_library
 
 SYMMETRIC_CLASSES = ("eggbox", "glue")  # evaluation_utils.py:153,196,215
-
-
-def _nn_lib():
-    from . import voting
-    lib = voting.load_library()
-    if not getattr(lib, "_nn_ready", False):
-        lib.pvnet_nearest_workspace_bytes.restype = C.c_size_t
-        lib.pvnet_nearest_workspace_bytes.argtypes = [C.c_int, C.c_int]
-        lib.pvnet_nearest_point_idx.restype = C.c_int
-        lib.pvnet_nearest_point_idx.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib._nn_ready = True
-    return lib
 
 
 def nearest_point_idx(ref_pts, que_pts, exclude_self=False):
@@ -49,8 +37,7 @@ def nearest_point_idx(ref_pts, que_pts, exclude_self=False):
     for every query the index of the nearest reference point (float32 squared distance, first index on ties).
     Enqueues on the current stream; nothing is copied to the host."""
     import torch
-    from .voting import _check
-    lib = _nn_lib()
+    lib = load_library()
     squeeze = ref_pts.dim() == 2
     if squeeze:
         ref_pts, que_pts = ref_pts[None], que_pts[None]
@@ -94,22 +81,6 @@ def find_nearest_point_distance(pts1, pts2):
     return np.linalg.norm(np.asarray(pts1)[idxs] - np.asarray(pts2), 2, 1)
 
 
-def _metrics_lib():
-    from . import voting
-    lib = voting.load_library()
-    if not getattr(lib, "_metrics_ready", False):
-        lib.pvnet_pose_metrics_workspace_bytes.restype = C.c_size_t
-        lib.pvnet_pose_metrics_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-        lib.pvnet_pose_metrics.restype = C.c_int
-        lib.pvnet_pose_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                           C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                           C.c_void_p]
-        lib._metrics_ready = True
-    return lib
-
-
-METRIC_SYM_PROJECTION = 1               # PVNET_METRIC_SYM_PROJECTION
 METRIC_THRESHOLDS = (5.0, 0.1, 5.0, 5.0)  # projection px, ADD fraction of the diameter, cm, degrees (Evaluator's defaults)
 
 
@@ -159,7 +130,6 @@ def pose_metrics_device(pose_pred, pose_targets, K, models, class_ids=None, sym_
              status 0, or < 0 for a class id out of range (NaN errors, false flags)."""
     import torch
     from . import pnp as _pnp
-    from . import voting
     if not (isinstance(pose_pred, torch.Tensor) and pose_pred.is_cuda):
         raise RuntimeError("pose_pred must be a CUDA tensor [n,3,4]")
     dev = pose_pred.device
@@ -196,7 +166,7 @@ def pose_metrics_device(pose_pred, pose_targets, K, models, class_ids=None, sym_
         ids = torch.full((n,), cid, dtype=torch.int32, device=dev)
     flags = METRIC_SYM_PROJECTION if sym_projection else 0
     th = (C.c_double * 4)(*[float(x) for x in thresholds])
-    lib = _metrics_lib()
+    lib = load_library()
     with torch.cuda.device(dev):
         if out is None:
             errors = torch.empty((n, 4), dtype=torch.float64, device=dev)
@@ -215,7 +185,7 @@ def pose_metrics_device(pose_pred, pose_targets, K, models, class_ids=None, sym_
             workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
             raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
-        voting._check(lib.pvnet_pose_metrics(
+        _check(lib.pvnet_pose_metrics(
             C.c_void_p(pred.data_ptr()), C.c_void_p(tgt.data_ptr()), int(tgt.dtype == torch.float64),
             C.c_void_p(models.points.data_ptr()), C.c_void_p(models.offsets.data_ptr()), C.c_void_p(models.diameters.data_ptr()),
             C.c_void_p(models.symmetric.data_ptr()), len(models), models.max_points,
@@ -228,7 +198,7 @@ def pose_metrics_device(pose_pred, pose_targets, K, models, class_ids=None, sym_
 
 def pose_metrics_workspace_bytes(n, models, sym_projection=False):
     """the workspace ``pose_metrics_device`` needs for n images of ``models`` (bytes)"""
-    return int(_metrics_lib().pvnet_pose_metrics_workspace_bytes(n, models.max_points,
+    return int(load_library().pvnet_pose_metrics_workspace_bytes(n, models.max_points,
                                                                  METRIC_SYM_PROJECTION if sym_projection else 0))
 
 

@@ -18,6 +18,8 @@ import os
 
 import numpy as np
 
+from ._abi import POSE_W_COV_F32, POSE_W_EXPLICIT, POSE_W_NONE, _check, load_library
+
 _PNP_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpvnet_pnp.so")
 _pnp_lib = None
 
@@ -258,7 +260,6 @@ def cm_degree_error(pose_pred, pose_target):
 
 
 # ---- the pose solve on the device (pvnet_amd/csrc/pose_solve.hip, pvnet_pose_solve in include/pvnet_vote.h) ----------------------
-POSE_W_NONE, POSE_W_EXPLICIT, POSE_W_COV_F32 = 0, 1, 2
 POSE_FAILED = -2   # status of an image whose linear start failed (zeros returned), as pvnet_pnp_solve returns it
 
 
@@ -288,7 +289,6 @@ def pnp_batch_device(points_3d, points_2d, camera_matrix, weights_2d=None, covar
              when the linear start failed -- that image's pose is zeros, as ``pnp_batch`` gives it.
     """
     import torch
-    from . import voting
     if not (isinstance(points_2d, torch.Tensor) and points_2d.is_cuda):
         raise RuntimeError("points_2d must be a CUDA tensor [n,pn,2]")
     if points_2d.dim() != 3 or points_2d.shape[2] != 2 or points_2d.dtype not in (torch.float32, torch.float64):
@@ -332,7 +332,7 @@ def pnp_batch_device(points_3d, points_2d, camera_matrix, weights_2d=None, covar
                 raise RuntimeError(f"out[1] must be a contiguous int32 CUDA tensor of shape {(n,)} on {dev}")
         if n == 0:
             return poses, status
-        voting._check(voting.load_library().pvnet_pose_solve(
+        _check(load_library().pvnet_pose_solve(
             C.c_void_p(points_2d.data_ptr()), int(points_2d.dtype == torch.float64), (C.c_int64 * 3)(*points_2d.stride()),
             C.c_void_p(X.data_ptr()), C.c_void_p(W.data_ptr()) if W is not None else None, kind, C.c_void_p(K.data_ptr()),
             per_image, n, pn, int(max_iterations), None, C.c_void_p(poses.data_ptr()), C.c_void_p(status.data_ptr()),

@@ -16,147 +16,26 @@ from __future__ import annotations
 
 import ctypes as C
 import struct
-import os
 from typing import Optional
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpvnet_vote.so")          # release build: the tuning knobs are constants
-DEV_LIB_PATH = os.path.join(_HERE, "libpvnet_vote_dev.so")  # development build (-DPVNET_DEV): PVNET_* environment knobs + every kernel variant
-# the knobs of the development build (vote_host.hip, load_tuning): with one of them in the environment the Python front end loads
-# libpvnet_vote_dev.so instead of the release library -- the knob tests, the fuzz matrix and the tuning tools work through that
-TUNING_KNOBS = ("PVNET_SCORE_MODE", "PVNET_SCORE_WGS_PER_CU", "PVNET_SCORE_HPL", "PVNET_SCORE_CHUNK", "PVNET_COMPACT_KG",
-                "PVNET_SCORE_XCD", "PVNET_SCORE_ATOMIC", "PVNET_SCORE_LDS_KB", "PVNET_SCORE_ACC", "PVNET_EXACT_FOLD",
-                "PVNET_SCORE_RUNS", "PVNET_SCORE_CULL", "PVNET_CULL_Q_MILLI", "PVNET_DEV_STAGES")
-
-F_LITERAL = 1
-F_NO_REFINE = 2
-F_VERTEX_F16, F_VERTEX_BF16, F_LOGITS_F16, F_LOGITS_BF16 = 4, 8, 16, 32
-F_APPROX = 64        # the round-1/2 "fast" mode: matrix-pipe scoring without the rounding-band re-evaluation
-F_BAND_STATS = 128   # development aid: count the re-evaluated cells / literal tests (exact mode)
-F_CONCURRENT = 256   # hint: other batches are in flight on other streams (see concurrent_hint)
-F_CULL_ALL, F_CULL_NONE = 512, 1024   # exact mode: disc-cull every key-point / none (default: K3 selects per image on the device)
-S_SKIPPED, S_SINGULAR, S_NO_INLIER, S_OVERFLOW = 1, 2, 4, 8
-NUM_STAGES = 6
-STAGE_NAMES = ("mask_bits", "subsample", "compact", "hypotheses", "score", "select_refine")
-
-
-class Layout(C.Structure):
-    """ctypes image of ``PvnetVoteLayout`` (include/pvnet_vote.h)."""
-    _fields_ = [(n, C.c_int32) for n in ("b", "h", "w", "vn", "hn", "cap", "words", "chunk", "max_chunks", "hpl",
-                                          "hgroups", "hn_pad")] + \
-               [(n, C.c_size_t) for n in ("off_ctrl", "off_bits", "off_pix", "off_rec", "off_hyp",
-                                          "off_partial", "off_counts", "off_win", "off_seg", "off_items", "off_hypb",
-                                          "total_bytes")] + \
-               [("nseg", C.c_int32), ("wg_g", C.c_int32), ("wg_s", C.c_int32), ("reserved_", C.c_int32), ("cull", C.c_int32)] + \
-               [(n, C.c_size_t) for n in ("off_perm", "off_hyps", "off_cnts", "off_hypc")]
-
-
-_lib = None
-_libs = {}   # path -> loaded library
-
-
-def _wanted_library() -> str:
-    if os.environ.get("PVNET_VOTE_LIB"):   # development aid: an experimental build of the same ABI
-        return os.environ["PVNET_VOTE_LIB"]
-    return DEV_LIB_PATH if any(os.environ.get(k) not in (None, "") for k in TUNING_KNOBS) else LIB_PATH
-
-
-def load_library() -> C.CDLL:
-    """dlopen the in-tree HIP library; loud failure if it has not been built (python -m pvnet_amd.build).  The release library unless
-    a tuning knob is set in the environment (see TUNING_KNOBS; `reload_tuning()` re-decides after the environment changed)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    _lib = _load(_wanted_library())
-    return _lib
-
-
-def _load(lib_path: str) -> C.CDLL:
-    if lib_path in _libs:
-        return _libs[lib_path]
-    if not os.path.exists(lib_path):
-        raise RuntimeError(f"pvnet_amd: HIP library {lib_path} is missing -- build it with "
-                           f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
-    lib = C.CDLL(lib_path)
-    i64p, f32p, i32p, u8p = C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p
-    lib.pvnet_vote_abi_version.restype = C.c_int
-    lib.pvnet_vote_build_info.restype = C.c_char_p
-    lib.pvnet_vote_layout.restype = C.c_int
-    lib.pvnet_vote_layout.argtypes = [C.c_int] * 6 + [C.POINTER(Layout)]
-    lib.pvnet_vote_workspace_bytes.restype = C.c_size_t
-    lib.pvnet_vote_workspace_bytes.argtypes = [C.c_int] * 6
-    v3_args = [C.c_void_p, C.c_int, i64p, f32p, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-               C.c_int, C.c_int, C.c_uint64, C.c_int, i32p, C.c_uint32, f32p, i32p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.pvnet_vote_v3.restype = C.c_int
-    lib.pvnet_vote_v3.argtypes = v3_args
-    lib.pvnet_vote_v3_logits.restype = C.c_int
-    lib.pvnet_vote_v3_logits.argtypes = [f32p, i64p, C.c_int, f32p, i64p] + v3_args[5:]
-    lib.pvnet_vote_v3_profiled.restype = C.c_int
-    lib.pvnet_vote_v3_profiled.argtypes = v3_args + [C.POINTER(C.c_float)]
-    lib.pvnet_vote_v3_stage_repeat.restype = C.c_int
-    lib.pvnet_vote_v3_stage_repeat.argtypes = v3_args + [C.c_int, C.c_int, C.POINTER(C.c_float)]
-    lib.pvnet_generate_hypothesis.restype = C.c_int
-    lib.pvnet_generate_hypothesis.argtypes = [f32p, f32p, i32p, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.pvnet_voting_for_hypothesis.restype = C.c_int
-    lib.pvnet_voting_for_hypothesis.argtypes = [f32p, f32p, f32p, u8p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                                C.c_void_p]
-    lib.pvnet_generate_hypothesis_vanishing_point.restype = C.c_int
-    lib.pvnet_generate_hypothesis_vanishing_point.argtypes = lib.pvnet_generate_hypothesis.argtypes
-    lib.pvnet_voting_for_hypothesis_vanishing_point.restype = C.c_int
-    lib.pvnet_voting_for_hypothesis_vanishing_point.argtypes = lib.pvnet_voting_for_hypothesis.argtypes
-    ws_tail = [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.pvnet_motion_workspace_bytes.restype = C.c_size_t
-    lib.pvnet_motion_workspace_bytes.argtypes = [C.c_int] * 4
-    lib.pvnet_motion_voting.restype = C.c_int
-    lib.pvnet_motion_voting.argtypes = [C.c_void_p, C.c_int, i64p, f32p, i64p, C.c_int, C.c_int, C.c_int, C.c_int, f32p,
-                                        C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.pvnet_motion_voting_typed.restype = C.c_int
-    lib.pvnet_motion_voting_typed.argtypes = [C.c_void_p, C.c_int, i64p, C.c_void_p, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              C.c_uint32, f32p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.pvnet_vote_confidence.restype = C.c_int
-    lib.pvnet_vote_confidence.argtypes = [f32p, C.c_float, f32p, C.c_uint32] + ws_tail
-    lib.pvnet_vote_distribution.restype = C.c_int
-    lib.pvnet_vote_distribution.argtypes = [f32p, f32p] + ws_tail
-    lib.pvnet_vote_band_margin.restype = C.c_int
-    lib.pvnet_vote_band_margin.argtypes = [C.c_float, C.c_void_p] + ws_tail
-    lib.pvnet_vote_tuning_reload.restype = None
-    lib.pvnet_vote_tuning_reload.argtypes = []
-    lib.pvnet_pose_solve.restype = C.c_int
-    lib.pvnet_pose_solve.argtypes = [C.c_void_p, C.c_int, i64p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if lib.pvnet_vote_abi_version() != 9:
-        raise RuntimeError("pvnet_amd: libpvnet_vote.so ABI version mismatch; rebuild it")
-    _libs[lib_path] = lib
-    return lib
-
-
-def reload_tuning():
-    """the PVNET_* tuning environment changed: pick the library again (release without knobs, the development build with) and have
-    the development build re-read them (it reads them once, at its first call; the release build's knobs are constants)."""
-    global _lib
-    _lib = _load(_wanted_library())
-    _lib.pvnet_vote_tuning_reload()
-
-
-def _check(rc: int, what: str):
-    if rc == 0:
-        return
-    names = {-1: "PVNET_E_BADARG", -2: "PVNET_E_WORKSPACE", -3: "PVNET_E_UNSUPPORTED"}
-    raise RuntimeError(f"{what} failed: {names.get(rc, 'hipError_t ' + str(rc))}")
-
+# the C ABI -- library paths, loading, prototypes, PvnetVoteLayout, error codes, the header's constants -- is bound in _abi.py; the names
+# below stay reachable as voting.<name> (bench.py, tools/, the tests)
+from ._abi import (DEV_LIB_PATH, LIB_PATH, TUNING_KNOBS, Layout, _check, _wanted_library, load_library,  # noqa: F401
+                   reload_tuning, vote_layout)
+from ._abi import (F_APPROX, F_BAND_STATS, F_CONCURRENT, F_CULL_ALL, F_CULL_NONE, F_LITERAL, F_LOGITS_BF16,  # noqa: F401
+                   F_LOGITS_F16, F_NO_REFINE, F_VERTEX_BF16, F_VERTEX_F16, MASK_F32, MASK_I16, MASK_I32, MASK_I64, MASK_U8,
+                   NUM_STAGES, S_NO_INLIER, S_OVERFLOW, S_SINGULAR, S_SKIPPED, STAGE_NAMES)
 
 _FIELD_FLAGS = {torch.float32: 0, torch.float16: F_VERTEX_F16, torch.bfloat16: F_VERTEX_BF16}
 _LOGITS_FLAGS = {torch.float32: 0, torch.float16: F_LOGITS_F16, torch.bfloat16: F_LOGITS_BF16}
-_MASK_CODES = {torch.uint8: 0, torch.int8: 0, torch.bool: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3,
-               torch.float32: 4}
+_MASK_CODES = {torch.uint8: MASK_U8, torch.int8: MASK_U8, torch.bool: MASK_U8, torch.int16: MASK_I16, torch.int32: MASK_I32,
+               torch.int64: MASK_I64, torch.float32: MASK_F32}
 
 
-def vote_layout(b, h, w, vn, hn, max_num) -> Layout:
-    L = Layout()
-    _check(load_library().pvnet_vote_layout(b, h, w, vn, hn, max_num, C.byref(L)), "pvnet_vote_layout")
-    return L
+def _clamp_max_num(max_num) -> int:
+    return int(min(max(int(max_num), 0), 2 ** 31 - 1))
 
 
 def _prepare(mask, vertex, round_hyp_num, max_num, idxs, convert_mask=True):
@@ -180,7 +59,7 @@ def _prepare(mask, vertex, round_hyp_num, max_num, idxs, convert_mask=True):
     hn = int(round_hyp_num)
     if hn <= 0:
         raise RuntimeError("round_hyp_num must be positive")
-    max_num = int(min(max(int(max_num), 0), 2 ** 31 - 1))
+    max_num = _clamp_max_num(max_num)
     if idxs is not None:
         if not idxs.is_cuda or idxs.device != vertex.device:
             raise RuntimeError("idxs must be a CUDA tensor on the inputs' device")
@@ -194,6 +73,35 @@ def _prepare(mask, vertex, round_hyp_num, max_num, idxs, convert_mask=True):
 
 def _strides(t, n):
     return (C.c_int64 * n)(*[int(s) for s in t.stride()])
+
+
+def _draw_seed(seed: Optional[int]) -> int:
+    """the caller's seed, or one drawn from torch's CPU generator (``torch.manual_seed`` makes runs repeatable)"""
+    return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else seed
+
+
+def _out_tensor(out, b, vn, dev) -> torch.Tensor:
+    """the key-point output [b,vn,2]: a fresh tensor, or the caller's checked"""
+    if out is None:
+        return torch.empty((b, vn, 2), dtype=torch.float32, device=dev)
+    if not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and
+            tuple(out.shape) == (b, vn, 2)):
+        raise RuntimeError(f"out must be a contiguous float32 CUDA tensor of shape {(b, vn, 2)} on {dev}")
+    return out
+
+
+def _mask_part(mask):
+    return (C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, 3))
+
+
+def _v3_args(mask_part, vertex, sizes, inlier_thresh, min_num, max_num, seed, image_offset, idxs, flags, out, status, ws,
+             total_bytes, stream) -> list:
+    """the 22-argument block of ``pvnet_vote_v3`` (and the head of ``_profiled`` / ``_stage_repeat``): ``mask_part`` = its first three
+    (``_mask_part``; the logits entry puts pointer, strides and class count there), ``sizes`` = (b, h, w, vn, hn)"""
+    return [*mask_part, C.c_void_p(vertex.data_ptr()), _strides(vertex, 5), *sizes, C.c_float(inlier_thresh), int(min_num), max_num,
+            C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(image_offset), C.c_void_p(idxs.data_ptr()) if idxs is not None else None,
+            flags, C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()) if status is not None else None,
+            C.c_void_p(ws.data_ptr()), C.c_size_t(total_bytes), C.c_void_p(stream)]
 
 
 class _DebugViews(dict):
@@ -354,8 +262,7 @@ def ransac_voting_layer_v3(mask, vertex, round_hyp_num, inlier_thresh=0.999, con
     lib = load_library()
     mask, vertex, b, h, w, vn, hn, max_num, idxs = _prepare(mask, vertex, round_hyp_num, max_num, idxs)
     dev = vertex.device
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    seed = _draw_seed(seed)
     literal = effective_literal(literal, inlier_thresh)
     flags = mode_flags(literal, approx, inlier_thresh) | (0 if refine else F_NO_REFINE) | _FIELD_FLAGS[vertex.dtype] | \
         (F_BAND_STATS if band_stats else 0)
@@ -363,19 +270,10 @@ def ransac_voting_layer_v3(mask, vertex, round_hyp_num, inlier_thresh=0.999, con
     with torch.cuda.device(dev):
         flags |= concurrent_hint(dev, concurrent)
         ws = _workspace(workspace, L, dev)
-        if out is None:
-            out = torch.empty((b, vn, 2), dtype=torch.float32, device=dev)
-        elif not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and
-                  tuple(out.shape) == (b, vn, 2)):
-            raise RuntimeError(f"out must be a contiguous float32 CUDA tensor of shape {(b, vn, 2)} on {dev}")
+        out = _out_tensor(out, b, vn, dev)
         status = torch.empty((b, vn), dtype=torch.int32, device=dev) if (return_status or return_debug) else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        args = [C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, 3),
-                C.c_void_p(vertex.data_ptr()), _strides(vertex, 5), b, h, w, vn, hn, C.c_float(inlier_thresh),
-                int(min_num), max_num, C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(image_offset),
-                C.c_void_p(idxs.data_ptr()) if idxs is not None else None, flags, C.c_void_p(out.data_ptr()),
-                C.c_void_p(status.data_ptr()) if status is not None else None, C.c_void_p(ws.data_ptr()),
-                C.c_size_t(L.total_bytes), C.c_void_p(stream)]
+        args = _v3_args(_mask_part(mask), vertex, (b, h, w, vn, hn), inlier_thresh, min_num, max_num, seed, image_offset, idxs,
+                        flags, out, status, ws, L.total_bytes, torch.cuda.current_stream(dev).cuda_stream)
         times = None
         if stage_times:
             ms = (C.c_float * NUM_STAGES)()
@@ -447,12 +345,9 @@ def stage_repeat_ms(mask, vertex, round_hyp_num, inlier_thresh=0.999, min_num=5,
         out = torch.empty((b, vn, 2), dtype=torch.float32, device=dev)
         ms = (C.c_float * 2)()
         _check(lib.pvnet_vote_v3_stage_repeat(
-            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, 3), C.c_void_p(vertex.data_ptr()),
-            _strides(vertex, 5), b, h, w, vn, hn, C.c_float(inlier_thresh), int(min_num), max_num,
-            C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(image_offset), None, flags, C.c_void_p(out.data_ptr()), None,
-            C.c_void_p(ws.data_ptr()), C.c_size_t(L.total_bytes),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), STAGE_NAMES.index(stage), int(repeats),
-            ms), "pvnet_vote_v3_stage_repeat")
+            *_v3_args(_mask_part(mask), vertex, (b, h, w, vn, hn), inlier_thresh, min_num, max_num, seed, image_offset, None, flags,
+                      out, None, ws, L.total_bytes, torch.cuda.current_stream(dev).cuda_stream),
+            STAGE_NAMES.index(stage), int(repeats), ms), "pvnet_vote_v3_stage_repeat")
     return (float(ms[0]), float(ms[1])) if both else float(ms[0])
 
 
@@ -482,11 +377,11 @@ class VotePlan:
         with torch.cuda.device(self.dev):
             self.workspace = torch.empty(self.layout.total_bytes, dtype=torch.uint8, device=self.dev)
             self.out = torch.empty((b, vn, 2), dtype=torch.float32, device=self.dev)
-        self._ms, self._vs = _strides(mask, 3), _strides(vertex, 5)
-        self._head = (_MASK_CODES[mask.dtype], self._ms)
-        self._mid = (self._vs, b, h, w, vn, hn, C.c_float(inlier_thresh), int(min_num), max_num)
-        self._tail = (None, flags, C.c_void_p(self.out.data_ptr()), None, C.c_void_p(self.workspace.data_ptr()),
-                      C.c_size_t(self.layout.total_bytes))
+        # the argument block once, with placeholders where __call__ splices the per-call values: mask pointer [0], field pointer [3],
+        # seed and image offset [13:15], stream [21]
+        args = _v3_args(_mask_part(mask), vertex, (b, h, w, vn, hn), inlier_thresh, min_num, max_num, 0, 0, None, flags, self.out,
+                        None, self.workspace, self.layout.total_bytes, None)
+        self._head, self._mid, self._tail = tuple(args[1:3]), tuple(args[4:13]), tuple(args[15:21])
 
     def __call__(self, mask, vertex, seed: int = 0, image_offset: int = 0) -> torch.Tensor:
         if (mask.dtype, tuple(mask.shape), tuple(mask.stride()), vertex.dtype, tuple(vertex.shape),
@@ -532,27 +427,26 @@ def ransac_voting_layer_v3_from_logits(seg_pred, vertex, round_hyp_num, inlier_t
     _, vertex, b, h, w, vn, hn, max_num, idxs = _prepare(fake_mask, vertex, round_hyp_num, max_num, idxs,
                                                          convert_mask=False)
     dev = vertex.device
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    seed = _draw_seed(seed)
     flags = mode_flags(literal, approx, inlier_thresh) | (0 if refine else F_NO_REFINE) | \
         _FIELD_FLAGS[vertex.dtype] | _LOGITS_FLAGS[seg_pred.dtype]
     L = vote_layout(b, h, w, vn, hn, max_num)
     with torch.cuda.device(dev):
         flags |= concurrent_hint(dev, concurrent)
         ws = _workspace(workspace, L, dev)  # caller-owned (reused across calls) or a fresh 171 MB at batch 32
-        if out is None:
-            out = torch.empty((b, vn, 2), dtype=torch.float32, device=dev)
-        elif not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and
-                  tuple(out.shape) == (b, vn, 2)):
-            raise RuntimeError(f"out must be a contiguous float32 CUDA tensor of shape {(b, vn, 2)} on {dev}")
+        out = _out_tensor(out, b, vn, dev)
         _check(lib.pvnet_vote_v3_logits(
-            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, 4), nc, C.c_void_p(vertex.data_ptr()),
-            _strides(vertex, 5), b, h, w, vn, hn, C.c_float(inlier_thresh), int(min_num), max_num,
-            C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(image_offset),
-            C.c_void_p(idxs.data_ptr()) if idxs is not None else None, flags, C.c_void_p(out.data_ptr()), None,
-            C.c_void_p(ws.data_ptr()), C.c_size_t(L.total_bytes),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_vote_v3_logits")
+            *_v3_args((C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, 4), nc), vertex, (b, h, w, vn, hn), inlier_thresh, min_num,
+                      max_num, seed, image_offset, idxs, flags, out, None, ws, L.total_bytes,
+                      torch.cuda.current_stream(dev).cuda_stream)), "pvnet_vote_v3_logits")
     return out
+
+
+def _field_view(vertex_pred):
+    """the backbone's field [b,2vn,h,w] as the voting layer's [b,h,w,vn,2] (a view: tools/demo.py:48-50)"""
+    vertex_pred = vertex_pred.permute(0, 2, 3, 1)
+    b, h, w, vn_2 = vertex_pred.shape
+    return vertex_pred.view(b, h, w, vn_2 // 2, 2)
 
 
 class EvalWrapper(torch.nn.Module):
@@ -564,9 +458,7 @@ class EvalWrapper(torch.nn.Module):
         self.round_hyp_num, self.inlier_thresh, self.max_num = round_hyp_num, inlier_thresh, max_num
 
     def forward(self, seg_pred, vertex_pred, use_argmax=True):
-        vertex_pred = vertex_pred.permute(0, 2, 3, 1)
-        b, h, w, vn_2 = vertex_pred.shape
-        vertex_pred = vertex_pred.view(b, h, w, vn_2 // 2, 2)
+        vertex_pred = _field_view(vertex_pred)
         if use_argmax:
             return ransac_voting_layer_v3_from_logits(seg_pred, vertex_pred, self.round_hyp_num,
                                                       inlier_thresh=self.inlier_thresh, max_num=self.max_num)
@@ -602,9 +494,7 @@ class PoseEvalWrapper(torch.nn.Module):
 
     def forward(self, seg_pred, vertex_pred, use_argmax=True, K=None, return_all=False):
         from . import pnp
-        vertex_pred = vertex_pred.permute(0, 2, 3, 1)
-        b, h, w, vn_2 = vertex_pred.shape
-        vertex_pred = vertex_pred.view(b, h, w, vn_2 // 2, 2)
+        vertex_pred = _field_view(vertex_pred)
         X, K0 = self._constants(vertex_pred.device)
         K = K0 if K is None else K
         cov = None
@@ -635,7 +525,7 @@ def ransac_voting_layer_v5(mask, vertex, round_hyp_num, inlier_thresh=0.999, con
     """Drop-in for the reference's ``ransac_voting_layer_v5`` (ransac_voting_gpu.py:763-858): v3 plus a per-key-point
     confidence = fraction of the (sub-sampled) foreground pixels voting for the refined point at 0.999 (:846-850).
     :return: ([b,vn,2], [b,vn]) float32"""
-    max_num = int(min(max(int(max_num), 0), 2 ** 31 - 1))
+    max_num = _clamp_max_num(max_num)
     out, dbg = ransac_voting_layer_v3(mask, vertex, round_hyp_num, inlier_thresh, confidence, max_iter, min_num,
                                       max_num, return_debug=True, **_strip_return_kw(kw))
     return out, vote_confidence(dbg, out, conf_thresh)
@@ -666,7 +556,7 @@ def estimate_voting_distribution_with_mean(mask, vertex, mean, round_hyp_num=256
     covariance about ``mean`` [b,vn,2].  Returns ``(mean, cov [b,vn,2,2])``.  ``topk`` is unused upstream too.
     (The reference selects ``mask == 1`` here rather than ``mask.byte() != 0``; identical for 0/1 masks.)"""
     hn = -(-int(min_hyp_num) // int(round_hyp_num)) * int(round_hyp_num)
-    max_num = int(min(max(int(max_num), 0), 2 ** 31 - 1))
+    max_num = _clamp_max_num(max_num)
     _, dbg = ransac_voting_layer_v3(mask, vertex, hn, inlier_thresh, min_num=min_num, max_num=max_num, refine=False,
                                     return_debug=True, **_strip_return_kw(kw))
     L, ws = dbg["layout"], dbg["workspace"]
@@ -722,76 +612,59 @@ def _check_input(x, name, dtype):
         raise RuntimeError(f"{name} must be {dtype}")  # implicit in .data<T>() of the reference
 
 
-def generate_hypothesis(direct, coords, idxs):
-    """direct [tn,vn,2] f32, coords [tn,2] f32, idxs [hn,vn,2] i32 -> new [hn,vn,2] f32 (ransac_voting.cpp:20-31)."""
+def _op_generate(name, width, direct, coords, idxs):
+    """``pvnet_<name>``: hypotheses of ``width`` coordinates from pixel pairs"""
     _check_input(direct, "direct", torch.float32)
     _check_input(coords, "coords", torch.float32)
     _check_input(idxs, "idxs", torch.int32)
     tn, vn, _ = direct.shape
     hn = idxs.shape[0]
     if coords.shape != (tn, 2) or idxs.shape != (hn, vn, 2) or direct.shape[2] != 2:
-        raise RuntimeError("generate_hypothesis: shape mismatch")
-    out = torch.empty((hn, vn, 2), dtype=torch.float32, device=direct.device)
+        raise RuntimeError(f"{name}: shape mismatch")
+    out = torch.empty((hn, vn, width), dtype=torch.float32, device=direct.device)
     with torch.cuda.device(direct.device):
-        _check(load_library().pvnet_generate_hypothesis(
+        _check(getattr(load_library(), "pvnet_" + name)(
             C.c_void_p(direct.data_ptr()), C.c_void_p(coords.data_ptr()), C.c_void_p(idxs.data_ptr()),
-            C.c_void_p(out.data_ptr()), tn, vn, hn, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-            "pvnet_generate_hypothesis")
+            C.c_void_p(out.data_ptr()), tn, vn, hn, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pvnet_" + name)
     return out
 
 
-def voting_for_hypothesis(direct, coords, hypo_pts, inliers, inlier_thresh):
-    """in place: inliers [hn,vn,tn] uint8 gets a 1 wherever the pixel votes (ransac_voting.cpp:41-55)."""
+def _op_vote(name, width, direct, coords, hypo_pts, inliers, inlier_thresh):
+    """``pvnet_<name>``: the votes of every pixel for hypotheses of ``width`` coordinates, in place"""
     _check_input(direct, "direct", torch.float32)
     _check_input(coords, "coords", torch.float32)
     _check_input(hypo_pts, "hypo_pts", torch.float32)
     _check_input(inliers, "inliers", torch.uint8)
     tn, vn, _ = direct.shape
     hn = hypo_pts.shape[0]
-    if coords.shape != (tn, 2) or hypo_pts.shape != (hn, vn, 2) or inliers.shape != (hn, vn, tn):
-        raise RuntimeError("voting_for_hypothesis: shape mismatch")
+    if coords.shape != (tn, 2) or hypo_pts.shape != (hn, vn, width) or inliers.shape != (hn, vn, tn):
+        raise RuntimeError(f"{name}: shape mismatch")
     with torch.cuda.device(direct.device):
-        _check(load_library().pvnet_voting_for_hypothesis(
+        _check(getattr(load_library(), "pvnet_" + name)(
             C.c_void_p(direct.data_ptr()), C.c_void_p(coords.data_ptr()), C.c_void_p(hypo_pts.data_ptr()),
             C.c_void_p(inliers.data_ptr()), tn, vn, hn, C.c_float(inlier_thresh),
-            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pvnet_voting_for_hypothesis")
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pvnet_" + name)
     return None
+
+
+def generate_hypothesis(direct, coords, idxs):
+    """direct [tn,vn,2] f32, coords [tn,2] f32, idxs [hn,vn,2] i32 -> new [hn,vn,2] f32 (ransac_voting.cpp:20-31)."""
+    return _op_generate("generate_hypothesis", 2, direct, coords, idxs)
+
+
+def voting_for_hypothesis(direct, coords, hypo_pts, inliers, inlier_thresh):
+    """in place: inliers [hn,vn,tn] uint8 gets a 1 wherever the pixel votes (ransac_voting.cpp:41-55)."""
+    return _op_vote("voting_for_hypothesis", 2, direct, coords, hypo_pts, inliers, inlier_thresh)
 
 
 def generate_hypothesis_vanishing_point(direct, coords, idxs):
     """direct [tn,vn,2] f32, coords [tn,2] f32, idxs [hn,vn,2] i32 -> new [hn,vn,3] f32: homogeneous intersections
     (x, y, z) of the two pixels' rays; z = 0 for parallel rays, (0, 0, 0) where the rays do not meet
     (ransac_voting.cpp:57-75 -> ransac_voting_kernel.cu:170-266)."""
-    _check_input(direct, "direct", torch.float32)
-    _check_input(coords, "coords", torch.float32)
-    _check_input(idxs, "idxs", torch.int32)
-    tn, vn, _ = direct.shape
-    hn = idxs.shape[0]
-    if coords.shape != (tn, 2) or idxs.shape != (hn, vn, 2) or direct.shape[2] != 2:
-        raise RuntimeError("generate_hypothesis_vanishing_point: shape mismatch")
-    out = torch.empty((hn, vn, 3), dtype=torch.float32, device=direct.device)
-    with torch.cuda.device(direct.device):
-        _check(load_library().pvnet_generate_hypothesis_vanishing_point(
-            C.c_void_p(direct.data_ptr()), C.c_void_p(coords.data_ptr()), C.c_void_p(idxs.data_ptr()),
-            C.c_void_p(out.data_ptr()), tn, vn, hn, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-            "pvnet_generate_hypothesis_vanishing_point")
-    return out
+    return _op_generate("generate_hypothesis_vanishing_point", 3, direct, coords, idxs)
 
 
 def voting_for_hypothesis_vanishing_point(direct, coords, hypo_pts, inliers, inlier_thresh):
     """in place: inliers [hn,vn,tn] uint8 gets a 1 wherever the pixel votes for the homogeneous hypothesis
     hypo_pts [hn,vn,3] (ransac_voting.cpp:84-99 -> ransac_voting_kernel.cu:268-351)."""
-    _check_input(direct, "direct", torch.float32)
-    _check_input(coords, "coords", torch.float32)
-    _check_input(hypo_pts, "hypo_pts", torch.float32)
-    _check_input(inliers, "inliers", torch.uint8)
-    tn, vn, _ = direct.shape
-    hn = hypo_pts.shape[0]
-    if coords.shape != (tn, 2) or hypo_pts.shape != (hn, vn, 3) or inliers.shape != (hn, vn, tn):
-        raise RuntimeError("voting_for_hypothesis_vanishing_point: shape mismatch")
-    with torch.cuda.device(direct.device):
-        _check(load_library().pvnet_voting_for_hypothesis_vanishing_point(
-            C.c_void_p(direct.data_ptr()), C.c_void_p(coords.data_ptr()), C.c_void_p(hypo_pts.data_ptr()),
-            C.c_void_p(inliers.data_ptr()), tn, vn, hn, C.c_float(inlier_thresh),
-            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pvnet_voting_for_hypothesis_vanishing_point")
-    return None
+    return _op_vote("voting_for_hypothesis_vanishing_point", 3, direct, coords, hypo_pts, inliers, inlier_thresh)
