@@ -1,4 +1,5 @@
-"""The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h).
+"""The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h) and of libpvnet_head.so
+(include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``).
 
 Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
 and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
@@ -92,8 +93,24 @@ PROTOTYPES = {
     "pvnet_vote_allgather": (_int, [_ptr, _ptr, _size, _ptr, _ptr]),
 }
 
+# ---- libpvnet_head.so (include/pvnet_head.h): a library and a table of its own, bound once like the one above ----------------------
+HEAD_LIB_PATH = os.path.join(_HERE, "libpvnet_head.so")
+HEAD_ABI_VERSION = 1
+HEAD_F_VERTEX_F16, HEAD_F_VERTEX_BF16, HEAD_F_LOGITS_F16, HEAD_F_LOGITS_BF16 = 1, 2, 4, 8
+HEAD_F_NT_NONE, HEAD_F_NT_ALL = 16, 32   # measurement aids: which loads are non-temporal (default: targets, weights and mask)
+HEAD_S_BAD_LABEL = 1
+HEAD_PROTOTYPES = {
+    "pvnet_head_abi_version": (_int, []),
+    "pvnet_head_metrics_workspace_bytes": (_size, [_int] * 3),
+    # seg_pred + strides + classes, vertex_pred + strides, target + strides, weights + strides, mask + dtype + strides, b, h, w, vn,
+    # sigma, flags, losses, counts, status, workspace + bytes, stream
+    "pvnet_head_metrics": (_int, [_ptr, _i64p, _int, _ptr, _i64p, _ptr, _i64p, _ptr, _i64p, _ptr, _int, _i64p] + [_int] * 4 +
+                           [C.c_double, C.c_uint32, _ptr, _ptr, _ptr, _ptr, _size, _ptr]),
+}
+
 _lib = None
 _libs = {}   # path -> loaded library
+_head_lib = None
 
 
 def _wanted_library() -> str:
@@ -126,6 +143,23 @@ def _load(lib_path: str) -> C.CDLL:
         raise RuntimeError("pvnet_amd: libpvnet_vote.so ABI version mismatch; rebuild it")
     _libs[lib_path] = lib
     return lib
+
+
+def load_head_library() -> C.CDLL:
+    """dlopen libpvnet_head.so (the head metrics); loud failure if it has not been built.  There is no CPU fallback."""
+    global _head_lib
+    if _head_lib is None:
+        if not os.path.exists(HEAD_LIB_PATH):
+            raise RuntimeError(f"pvnet_amd: HIP library {HEAD_LIB_PATH} is missing -- build it with "
+                               f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
+        lib = C.CDLL(HEAD_LIB_PATH)
+        for name, (restype, argtypes) in HEAD_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if lib.pvnet_head_abi_version() != HEAD_ABI_VERSION:
+            raise RuntimeError("pvnet_amd: libpvnet_head.so ABI version mismatch; rebuild it")
+        _head_lib = lib
+    return _head_lib
 
 
 def reload_tuning():

@@ -1,4 +1,5 @@
-"""Builds libpvnet_vote.so (the C-ABI HIP library) in-tree for gfx950 with hipcc.
+"""Builds libpvnet_vote.so (the C-ABI HIP library) and libpvnet_head.so (the head metrics, a library of its own) in-tree for gfx950
+with hipcc.
 
     python -m pvnet_amd.build            # build if sources are newer than the library
     python -m pvnet_amd.build --force
@@ -27,6 +28,13 @@ LIB = os.path.join(HERE, "libpvnet_vote.so")          # release: the knobs are c
 DEV_LIB = os.path.join(HERE, "libpvnet_vote_dev.so")  # -DPVNET_DEV: environment knobs + every kernel variant (knob tests, fuzz, tuning tools)
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
+# the network-head metrics of a validation step (include/pvnet_head.h): one translation unit, a library of its own -- libpvnet_vote.so
+# and its ABI stay as they are
+HEAD_TU = ["head_metrics.hip"]
+HEAD_SRC = [os.path.join(CSRC, f) for f in HEAD_TU]
+HEAD_DEPS = HEAD_SRC + [os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_head.h"),
+                        os.path.join(ROOT, "include", "pvnet_vote.h")]
+HEAD_LIB = os.path.join(HERE, "libpvnet_head.so")
 # host-side pose refinement (plain C++, g++): include/pvnet_pnp.h
 PNP_SRC = os.path.join(HERE, "csrc", "pvnet_pnp.cpp")
 PNP_DEPS = [PNP_SRC, os.path.join(ROOT, "include", "pvnet_pnp.h")]
@@ -96,6 +104,24 @@ def build_pnp(force: bool = False, verbose: bool = False) -> str:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
     return PNP_LIB
+
+
+def build_head(force: bool = False, verbose: bool = False) -> str:
+    """hipcc -> libpvnet_head.so; like the vote library it replaces the previous one only after the register check passed"""
+    if not force and os.path.exists(HEAD_LIB) and all(os.path.getmtime(HEAD_LIB) >= os.path.getmtime(d) for d in HEAD_DEPS):
+        return HEAD_LIB
+    tmp = HEAD_LIB + ".new"
+    try:
+        cmd = [hipcc_path()] + flags() + HEAD_SRC + ["-o", tmp]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        check_resources(("check_kernel_resources.py",), ["--head"])
+        os.replace(tmp, HEAD_LIB)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return HEAD_LIB
 
 
 # the reference's compiled extension module `ransac_voting` (src/ransac_voting.cpp) on this library: host-only C++ against
@@ -168,7 +194,7 @@ def build_canary(force: bool = False, verbose: bool = False):
     return CANARY_BINS
 
 
-def check_resources() -> None:
+def check_resources(tools=("check_kernel_resources.py", "check_mfma_hazard.py"), args=()) -> None:
     """the spare-VGPR-granule rule is enforced AT BUILD TIME, not only by a CPU test that needs hipcc: a library
     whose kernels use their allocation to the last granule is not produced (tools/check_kernel_resources.py; the same for
     the hand-placed MFMA epilogues, tools/check_mfma_hazard.py).  The checkers compile the sources to assembly themselves;
@@ -177,8 +203,8 @@ def check_resources() -> None:
     if os.environ.get("PVNET_BUILD_UNCHECKED") == "1":
         print("pvnet_amd.build: PVNET_BUILD_UNCHECKED=1 -- register / MFMA-hazard checks SKIPPED (experiment build)", file=sys.stderr)
         return
-    for tool in ("check_kernel_resources.py", "check_mfma_hazard.py"):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool)], capture_output=True, text=True)
+    for tool in tools:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool)] + list(args), capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"pvnet_amd.build: tools/{tool} rejects this build (the previous library, if any, is kept):\n"
                                + r.stdout[-3000:] + r.stderr[-1000:])
@@ -204,6 +230,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         finally:
             if os.path.exists(tmp):
                 os.remove(tmp)
+    build_head(force, verbose)
     build_ext(force, verbose)
     build_canary(force, verbose)
     return LIB

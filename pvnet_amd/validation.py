@@ -1,0 +1,165 @@
+"""The validation step behind the backbone, on the device (reference: tools/train_linemod.py:177-253).
+
+* ``head_metrics_device`` / ``HeadMetrics`` -- what the reference's ``NetWrapper.forward`` computes after the two predictions
+  (train_linemod.py:85-91): the per-image cross-entropy of ``seg_pred`` against the mask, the weighted smooth-L1 loss of
+  ``vertex_pred`` (lib/utils/net_utils.py:54-79) and the segmentation precision and recall (net_utils.py:329-348), in ONE fused
+  pass over the inputs (``pvnet_head_metrics``, pvnet_amd/csrc/head_metrics.hip, libpvnet_head.so; C ABI include/pvnet_head.h):
+  every input byte is read once, in place, whatever its strides; float64 arithmetic; bitwise reproducible.
+* ``ValStep`` -- the whole step on the current stream: head metrics, then ``voting.PoseEvalWrapper`` (fused arg-max voting and the
+  pose solve), then the pose metrics ``Evaluator.evaluate_batch`` records (``evaluation.pose_metrics_device``); one host copy at the
+  end.  ``enqueue`` is the part a graph captures.
+
+PyTorch is plumbing only.  There is NO CPU fallback: without the library, or with CPU tensors, these raise ``RuntimeError``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from ._abi import (HEAD_F_LOGITS_BF16, HEAD_F_LOGITS_F16, HEAD_F_NT_ALL, HEAD_F_NT_NONE, HEAD_F_VERTEX_BF16,  # noqa: F401
+                   HEAD_F_VERTEX_F16, HEAD_S_BAD_LABEL, MASK_I32, MASK_I64, MASK_U8, _check, load_head_library)
+
+_VERTEX_FLAGS = {torch.float32: 0, torch.float16: HEAD_F_VERTEX_F16, torch.bfloat16: HEAD_F_VERTEX_BF16}
+_LOGITS_FLAGS = {torch.float32: 0, torch.float16: HEAD_F_LOGITS_F16, torch.bfloat16: HEAD_F_LOGITS_BF16}
+_MASK_CODES = {torch.uint8: MASK_U8, torch.bool: MASK_U8, torch.int32: MASK_I32, torch.int64: MASK_I64}
+
+
+def _strides(t, dims):
+    return (C.c_int64 * len(dims))(*[int(t.stride(d)) for d in dims])
+
+
+def head_metrics_workspace_bytes(b, h, w):
+    """the workspace ``head_metrics_device`` needs for b images of h x w pixels (bytes)"""
+    return int(load_head_library().pvnet_head_metrics_workspace_bytes(int(b), int(h), int(w)))
+
+
+def head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=1.0, out=None, workspace=None, flags=0):
+    """The head metrics of a batch, enqueued on the current stream -- no synchronisation, no host copy.
+
+    :param seg_pred:       [b,C,h,w] class logits, float32 / float16 / bfloat16 CUDA tensor, any strides (read in place)
+    :param vertex_pred:    [b,2vn,h,w] predicted field, float32 / float16 / bfloat16, any strides (read in place)
+    :param mask:           [b,h,w] labels, uint8 / bool / int32 / int64, any strides
+    :param vertex:         [b,2vn,h,w] float32 target field, any strides
+    :param vertex_weights: [b,1,h,w] float32 weights, any strides
+    :param sigma:          the smooth-L1 knee (``smooth_l1_loss``'s default 1)
+    :param out:            None, or caller-owned contiguous ``(losses [b,4] float64, counts [b,3] int64, status [b] int32)``
+    :param workspace:      None, or a caller-owned uint8 CUDA tensor of at least ``head_metrics_workspace_bytes`` bytes
+    :param flags:          ``HEAD_F_NT_NONE`` / ``HEAD_F_NT_ALL`` (measurement aids; the results do not depend on them)
+    :return: ``(losses, counts, status)`` on the device: losses = (loss_seg, loss_vertex, precision, recall) per image, counts =
+             (tp, fp, fn), status 0 or ``HEAD_S_BAD_LABEL`` (a label outside 0..C-1: that image's loss_seg is NaN)."""
+    lib = load_head_library()
+    tensors = (("seg_pred", seg_pred), ("vertex_pred", vertex_pred), ("mask", mask), ("vertex", vertex),
+               ("vertex_weights", vertex_weights))
+    for name, t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name} must be a CUDA tensor (there is no CPU fallback)")
+    dev = seg_pred.device
+    if any(t.device != dev for _, t in tensors):
+        raise RuntimeError("seg_pred, vertex_pred, mask, vertex and vertex_weights must live on the same device")
+    if seg_pred.dim() != 4 or seg_pred.shape[1] < 2:
+        raise RuntimeError(f"seg_pred must be [b,C,h,w] with C >= 2, got {tuple(seg_pred.shape)}")
+    b, nc, h, w = (int(x) for x in seg_pred.shape)
+    if vertex_pred.dim() != 4 or vertex_pred.shape[1] % 2 or vertex_pred.shape[1] == 0 or \
+            (vertex_pred.shape[0], vertex_pred.shape[2], vertex_pred.shape[3]) != (b, h, w):
+        raise RuntimeError(f"vertex_pred must be [b,2vn,h,w] with (b,h,w)={(b, h, w)}, got {tuple(vertex_pred.shape)}")
+    planes = int(vertex_pred.shape[1])
+    if tuple(vertex.shape) != (b, planes, h, w):
+        raise RuntimeError(f"vertex must be [b,2vn,h,w]={(b, planes, h, w)}, got {tuple(vertex.shape)}")
+    if tuple(vertex_weights.shape) != (b, 1, h, w):
+        raise RuntimeError(f"vertex_weights must be [b,1,h,w]={(b, 1, h, w)}, got {tuple(vertex_weights.shape)}")
+    if tuple(mask.shape) != (b, h, w):
+        raise RuntimeError(f"mask must be [b,h,w]={(b, h, w)}, got {tuple(mask.shape)}")
+    if seg_pred.dtype not in _LOGITS_FLAGS or vertex_pred.dtype not in _VERTEX_FLAGS:
+        raise RuntimeError("seg_pred and vertex_pred must be float32, float16 or bfloat16")
+    if vertex.dtype != torch.float32 or vertex_weights.dtype != torch.float32:
+        raise RuntimeError("vertex and vertex_weights must be float32")
+    if mask.dtype not in _MASK_CODES:
+        raise RuntimeError("mask must be uint8, bool, int32 or int64")
+    flags = int(flags) | _LOGITS_FLAGS[seg_pred.dtype] | _VERTEX_FLAGS[vertex_pred.dtype]
+    with torch.cuda.device(dev):
+        if out is None:
+            losses = torch.empty((b, 4), dtype=torch.float64, device=dev)
+            counts = torch.empty((b, 3), dtype=torch.int64, device=dev)
+            status = torch.empty((b,), dtype=torch.int32, device=dev)
+        else:
+            losses, counts, status = out
+            for t, dt, shape, name in ((losses, torch.float64, (b, 4), "out[0]"), (counts, torch.int64, (b, 3), "out[1]"),
+                                       (status, torch.int32, (b,), "out[2]")):
+                if not (t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise RuntimeError(f"{name} must be a contiguous {dt} CUDA tensor of shape {shape} on {dev}")
+        if b == 0:
+            return losses, counts, status
+        nbytes = lib.pvnet_head_metrics_workspace_bytes(b, h, w)
+        if workspace is None:
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
+            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
+        _check(lib.pvnet_head_metrics(
+            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
+            C.c_void_p(vertex.data_ptr()), _strides(vertex, (0, 1, 2, 3)),
+            C.c_void_p(vertex_weights.data_ptr()), _strides(vertex_weights, (0, 2, 3)),
+            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
+            b, h, w, planes // 2, float(sigma), flags,
+            C.c_void_p(losses.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(status.data_ptr()),
+            C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_metrics")
+    return losses, counts, status
+
+
+class HeadMetrics(torch.nn.Module):
+    """What the reference's ``NetWrapper.forward`` returns after the two predictions (tools/train_linemod.py:87-91):
+    ``forward(seg_pred, vertex_pred, mask, vertex, vertex_weights) -> (loss_seg, loss_vertex, precision, recall)``, float32 [b]
+    each -- the float64 results of ``head_metrics_device`` rounded once.  Validation only: nothing here is differentiable."""
+
+    def __init__(self, sigma=1.0):
+        super().__init__()
+        self.sigma = float(sigma)
+
+    def forward(self, seg_pred, vertex_pred, mask, vertex, vertex_weights):
+        losses, _, _ = head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=self.sigma)
+        return tuple(losses.to(torch.float32).unbind(1))
+
+
+class ValStep(object):
+    """One validation step behind the backbone (tools/train_linemod.py:200-215), composed of what exists, all on the current
+    stream: ``head_metrics_device``, ``voting.PoseEvalWrapper`` (fused arg-max voting, pose solve), ``pose_metrics_device`` with the
+    evaluator's class table -- the device part of ``Evaluator.evaluate_batch``.
+
+    ``enqueue(...)`` returns device tensors ``(losses [b,4], counts [b,3], head_status [b], poses [b,3,4], pose_status [b],
+    errors [b,4], passed [b,3], metric_status [b])`` without synchronising: it is what ``torch.cuda.graph`` captures (for repeatable votes seed torch's
+    CPU generator, ``torch.default_generator.manual_seed``, before each call: the vote draws its seed there).  ``__call__`` is ``enqueue`` plus ONE
+    device-to-host copy; it fills the evaluator's recorders as ``evaluate_batch`` does and returns the head metrics as a dict of
+    numpy arrays (``loss_seg``, ``loss_vertex``, ``precision``, ``recall``, float32 as the reference's) and the poses."""
+
+    def __init__(self, evaluator, class_type, K=None, intri_type="blender", round_hyp_num=512, inlier_thresh=0.99, max_num=30000,
+                 sigma=1.0, sym_projection=False):
+        from .voting import PoseEvalWrapper
+        self.evaluator, self.class_type = evaluator, class_type
+        self.K = evaluator._intrinsics(intri_type) if K is None else K
+        self.sigma, self.sym_projection = float(sigma), bool(sym_projection)
+        self.eval_net = PoseEvalWrapper(evaluator.points_3d[class_type], self.K, round_hyp_num=round_hyp_num,
+                                        inlier_thresh=inlier_thresh, max_num=max_num)
+
+    def enqueue(self, seg_pred, vertex_pred, mask, vertex, vertex_weights, pose_targets):
+        from .evaluation import pose_metrics_device
+        losses, counts, hstatus = head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=self.sigma)
+        poses, pstatus, _, _ = self.eval_net(seg_pred, vertex_pred, return_all=True)
+        _, Kd = self.eval_net._constants(poses.device)
+        errors, passed, mstatus = pose_metrics_device(poses, pose_targets, Kd, self.evaluator.device_models(poses.device),
+                                                      class_ids=self.class_type, sym_projection=self.sym_projection)
+        return losses, counts, hstatus, poses, pstatus, errors, passed, mstatus
+
+    def __call__(self, seg_pred, vertex_pred, mask, vertex, vertex_weights, pose_targets):
+        losses, _, _, poses, _, errors, passed, _ = self.enqueue(seg_pred, vertex_pred, mask, vertex, vertex_weights, pose_targets)
+        host = torch.cat([losses, errors, passed.to(torch.float64)], 1).cpu().numpy()   # the one copy (it waits for the stream)
+        ev = self.evaluator
+        for e, ok in zip(host[:, 4:8], host[:, 8:]):
+            ev.add_dists.append(float(e[1]))
+            ev.add_recorder.append(bool(ok[1]))
+            ev.proj_mean_diffs.append(float(e[0]))
+            ev.projection_2d_recorder.append(bool(ok[0]))
+            ev.cm_degree_5_recorder.append(bool(ok[2]))
+        head = {k: host[:, i].astype("float32") for i, k in enumerate(("loss_seg", "loss_vertex", "precision", "recall"))}
+        return head, poses

@@ -2,9 +2,13 @@
 // 8-byte vs 16-byte loads per lane, loads in flight per lane, workgroup size.  Two buffers alternate (> 256 MiB apart in
 // total) so that the Infinity Cache does not serve the reads.
 // hipcc --offload-arch=gfx950 -O3 tools/ubench_hbm_read.hip -o tools/ubench_hbm_read.bin
+// With arguments -- ubench_hbm_read.bin BYTES [BYTES ...] -- it times only the best bare read (16 B/lane, 8 loads in flight, 256
+// lanes) of each byte count instead, cold (enough buffers cycled to exceed the Infinity Cache), one line per count: the ceiling
+// tools/head_metrics_probe.py holds the fused head-metrics pass against.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 template <int VEC, int ILP>
 __global__ void rd(const uint64_t* __restrict__ p, size_t n, unsigned long long* out) {
@@ -109,7 +113,48 @@ __global__ void k1_like3(const uint64_t* __restrict__ p, size_t n, unsigned long
     if (lane == 0) seg[blockIdx.x * WAVES + wave] = cnt;
 }
 
-int main() {
+static int bare_read_of(size_t bytes) {
+    const size_t n = (bytes + 15) / 16 * 2;   // uint64 elements
+    const int nbuf = (int)((size_t)320 * 1024 * 1024 / (n * 8)) + 2;   // more than 256 MiB between two reads of a buffer
+    uint64_t** buf = (uint64_t**)malloc(nbuf * sizeof(uint64_t*));
+    for (int i = 0; i < nbuf; ++i) {
+        if (hipMalloc(&buf[i], n * 8) != hipSuccess) return 1;
+        hipMemset(buf[i], 0, n * 8);
+    }
+    unsigned long long* out;
+    const int per_block = 256 * 16, blocks = (int)((n + per_block - 1) / per_block);
+    if (hipMalloc(&out, (size_t)blocks * 8) != hipSuccess) return 1;
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    for (int w = 0; w < nbuf; ++w) hipLaunchKernelGGL((rd<2, 8>), dim3(blocks), dim3(256), 0, 0, buf[w], n, out);
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    const int reps = 40;
+    float best = 1e9f, sum = 0;
+    for (int r = 0; r < reps; ++r) {
+        hipEventRecord(e0);
+        hipLaunchKernelGGL((rd<2, 8>), dim3(blocks), dim3(256), 0, 0, buf[r % nbuf], n, out);
+        hipEventRecord(e1);
+        hipEventSynchronize(e1);
+        float ms;
+        hipEventElapsedTime(&ms, e0, e1);
+        best = ms < best ? ms : best;
+        sum += ms;
+    }
+    printf("bare_read bytes %zu buffers %d avg_us %.2f best_us %.2f avg_GBps %.1f\n", n * 8, nbuf, sum / reps * 1e3, best * 1e3,
+           n * 8 / (sum / reps * 1e-3) / 1e9);
+    for (int i = 0; i < nbuf; ++i) hipFree(buf[i]);
+    hipFree(out);
+    free(buf);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) {
+        for (int i = 1; i < argc; ++i)
+            if (bare_read_of((size_t)strtoull(argv[i], nullptr, 10))) return 1;
+        return 0;
+    }
     const size_t n = (size_t)32 * 480 * 640;  // int64 elements of one batch of masks: 78.6 MB
     const int NBUF = 5;                       // 393 MB cycled: beyond the 256 MiB Infinity Cache
     uint64_t* buf[NBUF];
