@@ -1,5 +1,6 @@
-"""The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h) and of libpvnet_head.so
-(include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``).
+"""The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h), of libpvnet_head.so
+(include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``) and of libpvnet_train.so (include/pvnet_train.h:
+``TRAIN_PROTOTYPES``, ``load_train_library``).
 
 Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
 and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
@@ -108,9 +109,21 @@ HEAD_PROTOTYPES = {
                            [C.c_double, C.c_uint32, _ptr, _ptr, _ptr, _ptr, _size, _ptr]),
 }
 
+# ---- libpvnet_train.so (include/pvnet_train.h): the head losses' backward; it takes the HEAD_F_* flags and HEAD_S_* bits above -----
+TRAIN_LIB_PATH = os.path.join(_HERE, "libpvnet_train.so")
+TRAIN_ABI_VERSION = 1
+TRAIN_PROTOTYPES = {
+    "pvnet_train_abi_version": (_int, []),
+    "pvnet_head_grad_workspace_bytes": (_size, [_int] * 3),
+    # the forward's inputs as pvnet_head_metrics takes them (through flags), then upstream, grad_seg + strides, grad_vertex + strides,
+    # status, workspace + bytes, stream
+    "pvnet_head_grad": (_int, HEAD_PROTOTYPES["pvnet_head_metrics"][1][:18] + [_ptr, _ptr, _i64p, _ptr, _i64p, _ptr, _ptr, _size, _ptr]),
+}
+
 _lib = None
 _libs = {}   # path -> loaded library
 _head_lib = None
+_train_lib = None
 
 
 def _wanted_library() -> str:
@@ -160,6 +173,23 @@ def load_head_library() -> C.CDLL:
             raise RuntimeError("pvnet_amd: libpvnet_head.so ABI version mismatch; rebuild it")
         _head_lib = lib
     return _head_lib
+
+
+def load_train_library() -> C.CDLL:
+    """dlopen libpvnet_train.so (the head losses' backward); loud failure if it has not been built.  There is no CPU fallback."""
+    global _train_lib
+    if _train_lib is None:
+        if not os.path.exists(TRAIN_LIB_PATH):
+            raise RuntimeError(f"pvnet_amd: HIP library {TRAIN_LIB_PATH} is missing -- build it with "
+                               f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
+        lib = C.CDLL(TRAIN_LIB_PATH)
+        for name, (restype, argtypes) in TRAIN_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if lib.pvnet_train_abi_version() != TRAIN_ABI_VERSION:
+            raise RuntimeError("pvnet_amd: libpvnet_train.so ABI version mismatch; rebuild it")
+        _train_lib = lib
+    return _train_lib
 
 
 def reload_tuning():

@@ -1,5 +1,5 @@
-"""Builds libpvnet_vote.so (the C-ABI HIP library) and libpvnet_head.so (the head metrics, a library of its own) in-tree for gfx950
-with hipcc.
+"""Builds libpvnet_vote.so (the C-ABI HIP library), libpvnet_head.so (the head metrics, a library of its own) and libpvnet_train.so
+(the head losses' backward, likewise) in-tree for gfx950 with hipcc.
 
     python -m pvnet_amd.build            # build if sources are newer than the library
     python -m pvnet_amd.build --force
@@ -35,6 +35,13 @@ HEAD_SRC = [os.path.join(CSRC, f) for f in HEAD_TU]
 HEAD_DEPS = HEAD_SRC + [os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_head.h"),
                         os.path.join(ROOT, "include", "pvnet_vote.h")]
 HEAD_LIB = os.path.join(HERE, "libpvnet_head.so")
+# the backward of the head losses of a training step (include/pvnet_train.h): one translation unit, a library of its own again --
+# libpvnet_head.so and its ABI stay as they are
+TRAIN_TU = ["head_grad.hip"]
+TRAIN_SRC = [os.path.join(CSRC, f) for f in TRAIN_TU]
+TRAIN_DEPS = TRAIN_SRC + [os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_train.h"),
+                          os.path.join(ROOT, "include", "pvnet_head.h"), os.path.join(ROOT, "include", "pvnet_vote.h")]
+TRAIN_LIB = os.path.join(HERE, "libpvnet_train.so")
 # host-side pose refinement (plain C++, g++): include/pvnet_pnp.h
 PNP_SRC = os.path.join(HERE, "csrc", "pvnet_pnp.cpp")
 PNP_DEPS = [PNP_SRC, os.path.join(ROOT, "include", "pvnet_pnp.h")]
@@ -122,6 +129,24 @@ def build_head(force: bool = False, verbose: bool = False) -> str:
         if os.path.exists(tmp):
             os.remove(tmp)
     return HEAD_LIB
+
+
+def build_train(force: bool = False, verbose: bool = False) -> str:
+    """hipcc -> libpvnet_train.so; like build_head it replaces the previous library only after the register check passed"""
+    if not force and os.path.exists(TRAIN_LIB) and all(os.path.getmtime(TRAIN_LIB) >= os.path.getmtime(d) for d in TRAIN_DEPS):
+        return TRAIN_LIB
+    tmp = TRAIN_LIB + ".new"
+    try:
+        cmd = [hipcc_path()] + flags() + TRAIN_SRC + ["-o", tmp]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        check_resources(("check_kernel_resources.py",), ["--train"])
+        os.replace(tmp, TRAIN_LIB)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return TRAIN_LIB
 
 
 # the reference's compiled extension module `ransac_voting` (src/ransac_voting.cpp) on this library: host-only C++ against
@@ -231,6 +256,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             if os.path.exists(tmp):
                 os.remove(tmp)
     build_head(force, verbose)
+    build_train(force, verbose)
     build_ext(force, verbose)
     build_canary(force, verbose)
     return LIB

@@ -5,6 +5,9 @@
   ``vertex_pred`` (lib/utils/net_utils.py:54-79) and the segmentation precision and recall (net_utils.py:329-348), in ONE fused
   pass over the inputs (``pvnet_head_metrics``, pvnet_amd/csrc/head_metrics.hip, libpvnet_head.so; C ABI include/pvnet_head.h):
   every input byte is read once, in place, whatever its strides; float64 arithmetic; bitwise reproducible.
+* ``head_grad_device`` / ``HeadLoss`` -- the same four lines as the loss of the reference's TRAINING loop (train_linemod.py:146-153):
+  ``HeadLoss`` is ``HeadMetrics`` with a backward, ONE fused pass that reads the forward's inputs again and writes both gradients
+  (``pvnet_head_grad``, pvnet_amd/csrc/head_grad.hip, libpvnet_train.so; C ABI and the formulas: include/pvnet_train.h).
 * ``ValStep`` -- the whole step on the current stream: head metrics, then ``voting.PoseEvalWrapper`` (fused arg-max voting and the
   pose solve), then the pose metrics ``Evaluator.evaluate_batch`` records (``evaluation.pose_metrics_device``); one host copy at the
   end.  ``enqueue`` is the part a graph captures.
@@ -18,7 +21,7 @@ import ctypes as C
 import torch
 
 from ._abi import (HEAD_F_LOGITS_BF16, HEAD_F_LOGITS_F16, HEAD_F_NT_ALL, HEAD_F_NT_NONE, HEAD_F_VERTEX_BF16,  # noqa: F401
-                   HEAD_F_VERTEX_F16, HEAD_S_BAD_LABEL, MASK_I32, MASK_I64, MASK_U8, _check, load_head_library)
+                   HEAD_F_VERTEX_F16, HEAD_S_BAD_LABEL, MASK_I32, MASK_I64, MASK_U8, _check, load_head_library, load_train_library)
 
 _VERTEX_FLAGS = {torch.float32: 0, torch.float16: HEAD_F_VERTEX_F16, torch.bfloat16: HEAD_F_VERTEX_BF16}
 _LOGITS_FLAGS = {torch.float32: 0, torch.float16: HEAD_F_LOGITS_F16, torch.bfloat16: HEAD_F_LOGITS_BF16}
@@ -29,26 +32,8 @@ def _strides(t, dims):
     return (C.c_int64 * len(dims))(*[int(t.stride(d)) for d in dims])
 
 
-def head_metrics_workspace_bytes(b, h, w):
-    """the workspace ``head_metrics_device`` needs for b images of h x w pixels (bytes)"""
-    return int(load_head_library().pvnet_head_metrics_workspace_bytes(int(b), int(h), int(w)))
-
-
-def head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=1.0, out=None, workspace=None, flags=0):
-    """The head metrics of a batch, enqueued on the current stream -- no synchronisation, no host copy.
-
-    :param seg_pred:       [b,C,h,w] class logits, float32 / float16 / bfloat16 CUDA tensor, any strides (read in place)
-    :param vertex_pred:    [b,2vn,h,w] predicted field, float32 / float16 / bfloat16, any strides (read in place)
-    :param mask:           [b,h,w] labels, uint8 / bool / int32 / int64, any strides
-    :param vertex:         [b,2vn,h,w] float32 target field, any strides
-    :param vertex_weights: [b,1,h,w] float32 weights, any strides
-    :param sigma:          the smooth-L1 knee (``smooth_l1_loss``'s default 1)
-    :param out:            None, or caller-owned contiguous ``(losses [b,4] float64, counts [b,3] int64, status [b] int32)``
-    :param workspace:      None, or a caller-owned uint8 CUDA tensor of at least ``head_metrics_workspace_bytes`` bytes
-    :param flags:          ``HEAD_F_NT_NONE`` / ``HEAD_F_NT_ALL`` (measurement aids; the results do not depend on them)
-    :return: ``(losses, counts, status)`` on the device: losses = (loss_seg, loss_vertex, precision, recall) per image, counts =
-             (tp, fp, fn), status 0 or ``HEAD_S_BAD_LABEL`` (a label outside 0..C-1: that image's loss_seg is NaN)."""
-    lib = load_head_library()
+def _head_inputs(seg_pred, vertex_pred, mask, vertex, vertex_weights, flags):
+    """the checks ``head_metrics_device`` and ``head_grad_device`` share -> (device, b, C, h, w, 2vn, flags with the element types)"""
     tensors = (("seg_pred", seg_pred), ("vertex_pred", vertex_pred), ("mask", mask), ("vertex", vertex),
                ("vertex_weights", vertex_weights))
     for name, t in tensors:
@@ -77,6 +62,30 @@ def head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sig
     if mask.dtype not in _MASK_CODES:
         raise RuntimeError("mask must be uint8, bool, int32 or int64")
     flags = int(flags) | _LOGITS_FLAGS[seg_pred.dtype] | _VERTEX_FLAGS[vertex_pred.dtype]
+    return dev, b, nc, h, w, planes, flags
+
+
+def head_metrics_workspace_bytes(b, h, w):
+    """the workspace ``head_metrics_device`` needs for b images of h x w pixels (bytes)"""
+    return int(load_head_library().pvnet_head_metrics_workspace_bytes(int(b), int(h), int(w)))
+
+
+def head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=1.0, out=None, workspace=None, flags=0):
+    """The head metrics of a batch, enqueued on the current stream -- no synchronisation, no host copy.
+
+    :param seg_pred:       [b,C,h,w] class logits, float32 / float16 / bfloat16 CUDA tensor, any strides (read in place)
+    :param vertex_pred:    [b,2vn,h,w] predicted field, float32 / float16 / bfloat16, any strides (read in place)
+    :param mask:           [b,h,w] labels, uint8 / bool / int32 / int64, any strides
+    :param vertex:         [b,2vn,h,w] float32 target field, any strides
+    :param vertex_weights: [b,1,h,w] float32 weights, any strides
+    :param sigma:          the smooth-L1 knee (``smooth_l1_loss``'s default 1)
+    :param out:            None, or caller-owned contiguous ``(losses [b,4] float64, counts [b,3] int64, status [b] int32)``
+    :param workspace:      None, or a caller-owned uint8 CUDA tensor of at least ``head_metrics_workspace_bytes`` bytes
+    :param flags:          ``HEAD_F_NT_NONE`` / ``HEAD_F_NT_ALL`` (measurement aids; the results do not depend on them)
+    :return: ``(losses, counts, status)`` on the device: losses = (loss_seg, loss_vertex, precision, recall) per image, counts =
+             (tp, fp, fn), status 0 or ``HEAD_S_BAD_LABEL`` (a label outside 0..C-1: that image's loss_seg is NaN)."""
+    lib = load_head_library()
+    dev, b, nc, h, w, planes, flags = _head_inputs(seg_pred, vertex_pred, mask, vertex, vertex_weights, flags)
     with torch.cuda.device(dev):
         if out is None:
             losses = torch.empty((b, 4), dtype=torch.float64, device=dev)
@@ -120,6 +129,156 @@ class HeadMetrics(torch.nn.Module):
     def forward(self, seg_pred, vertex_pred, mask, vertex, vertex_weights):
         losses, _, _ = head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=self.sigma)
         return tuple(losses.to(torch.float32).unbind(1))
+
+
+def head_grad_workspace_bytes(b, h, w):
+    """the workspace ``head_grad_device`` needs for b images of h x w pixels (bytes)"""
+    return int(load_train_library().pvnet_head_grad_workspace_bytes(int(b), int(h), int(w)))
+
+
+def head_grad_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, upstream, sigma=1.0, need=(True, True), out=None,
+                     workspace=None, flags=0):
+    """The gradients of the two head losses with respect to the two predictions, enqueued on the current stream -- no
+    synchronisation, no host copy, nothing saved from a forward (the formulas: include/pvnet_train.h).
+
+    The first five arguments and ``sigma`` are those of ``head_metrics_device``, read in place.
+
+    :param upstream:  [b,2] float64 contiguous CUDA tensor: dL/dloss_seg and dL/dloss_vertex per image
+    :param need:      ``(grad_seg wanted, grad_vertex wanted)``; a half that is not wanted is skipped, its loads included
+    :param out:       None, or caller-owned ``(grad_seg, grad_vertex)`` (``None`` for a half that is not wanted): the shape, dtype and
+                      device of their prediction, ANY strides -- channels-last, or channel slices of one wider tensor
+    :param workspace: None, or a caller-owned uint8 CUDA tensor of at least ``head_grad_workspace_bytes`` bytes
+    :param flags:     ``HEAD_F_NT_NONE`` / ``HEAD_F_NT_ALL`` (measurement aids; the results do not depend on them)
+    :return: ``(grad_seg, grad_vertex, status)``: each gradient in its prediction's dtype (``torch.empty_like`` unless ``out`` is
+             given), None for a half that is not wanted; status [b] int32, 0 or ``HEAD_S_BAD_LABEL`` (a label outside 0..C-1: that
+             pixel's C gradients are NaN; 0 when grad_seg is not wanted -- the mask is not read then)."""
+    lib = load_train_library()
+    dev, b, nc, h, w, planes, flags = _head_inputs(seg_pred, vertex_pred, mask, vertex, vertex_weights, flags)
+    need = (bool(need[0]), bool(need[1]))
+    if not any(need):
+        raise RuntimeError("need: at least one of the two gradients must be wanted")
+    if not (isinstance(upstream, torch.Tensor) and upstream.is_cuda):
+        raise RuntimeError("upstream must be a CUDA tensor (there is no CPU fallback)")
+    if not (upstream.device == dev and upstream.dtype == torch.float64 and tuple(upstream.shape) == (b, 2) and upstream.is_contiguous()):
+        raise RuntimeError(f"upstream must be a contiguous float64 CUDA tensor of shape {(b, 2)} on {dev}")
+    with torch.cuda.device(dev):
+        grads = []
+        for k, (pred, name) in enumerate(((seg_pred, "out[0]"), (vertex_pred, "out[1]"))):
+            g = None if out is None else out[k]
+            if not need[k]:
+                g = None
+            elif g is None:
+                g = torch.empty_like(pred)
+            elif not (isinstance(g, torch.Tensor) and g.is_cuda and g.device == dev and g.dtype == pred.dtype and g.shape == pred.shape):
+                raise RuntimeError(f"{name} must be a {pred.dtype} CUDA tensor of shape {tuple(pred.shape)} on {dev}")
+            grads.append(g)
+        grad_seg, grad_vertex = grads
+        status = torch.empty((b,), dtype=torch.int32, device=dev)
+        if b == 0:
+            return grad_seg, grad_vertex, status
+        nbytes = lib.pvnet_head_grad_workspace_bytes(b, h, w)
+        if workspace is None:
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
+            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
+        _check(lib.pvnet_head_grad(
+            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
+            C.c_void_p(vertex.data_ptr()), _strides(vertex, (0, 1, 2, 3)),
+            C.c_void_p(vertex_weights.data_ptr()), _strides(vertex_weights, (0, 2, 3)),
+            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
+            b, h, w, planes // 2, float(sigma), flags, C.c_void_p(upstream.data_ptr()),
+            None if grad_seg is None else C.c_void_p(grad_seg.data_ptr()), None if grad_seg is None else _strides(grad_seg, (0, 1, 2, 3)),
+            None if grad_vertex is None else C.c_void_p(grad_vertex.data_ptr()),
+            None if grad_vertex is None else _strides(grad_vertex, (0, 1, 2, 3)),
+            C.c_void_p(status.data_ptr()), C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_grad")
+    return grad_seg, grad_vertex, status
+
+
+def _upstream(grad_seg_loss, grad_vertex_loss, b, dev):
+    """[b,2] float64 from the two incoming gradients of a backward; a missing one is zeros"""
+    cols = [torch.zeros((b,), dtype=torch.float64, device=dev) if g is None else g.to(torch.float64) for g in (grad_seg_loss, grad_vertex_loss)]
+    return torch.stack(cols, 1)
+
+
+def _float32_columns(losses):
+    return tuple(losses.to(torch.float32).unbind(1))
+
+
+class _HeadLossFn(torch.autograd.Function):
+    """forward: ``head_metrics_device``; backward: ONE ``head_grad_device`` on the saved inputs"""
+
+    @staticmethod
+    def forward(ctx, seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma):
+        losses, _, _ = head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=sigma)
+        ctx.save_for_backward(seg_pred, vertex_pred, mask, vertex, vertex_weights)
+        ctx.sigma = sigma
+        loss_seg, loss_vertex, precision, recall = _float32_columns(losses)
+        ctx.mark_non_differentiable(precision, recall)
+        return loss_seg, loss_vertex, precision, recall
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_seg, g_vertex, _g_precision, _g_recall):
+        seg_pred, vertex_pred, mask, vertex, vertex_weights = ctx.saved_tensors
+        need = ctx.needs_input_grad[:2]
+        if not any(need):
+            return (None,) * 6
+        upstream = _upstream(g_seg, g_vertex, seg_pred.shape[0], seg_pred.device)
+        grad_seg, grad_vertex, _ = head_grad_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, upstream, sigma=ctx.sigma, need=need)
+        return grad_seg, grad_vertex, None, None, None, None
+
+
+class _PackedHeadLossFn(torch.autograd.Function):
+    """the same on the two channel slices of ONE tensor; backward writes both halves into one gradient tensor of its shape"""
+
+    @staticmethod
+    def forward(ctx, head_out, seg_dim, mask, vertex, vertex_weights, sigma):
+        losses, _, _ = head_metrics_device(head_out[:, :seg_dim], head_out[:, seg_dim:], mask, vertex, vertex_weights, sigma=sigma)
+        ctx.save_for_backward(head_out, mask, vertex, vertex_weights)
+        ctx.sigma, ctx.seg_dim = sigma, seg_dim
+        loss_seg, loss_vertex, precision, recall = _float32_columns(losses)
+        ctx.mark_non_differentiable(precision, recall)
+        return loss_seg, loss_vertex, precision, recall
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_seg, g_vertex, _g_precision, _g_recall):
+        head_out, mask, vertex, vertex_weights = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        k = ctx.seg_dim
+        upstream = _upstream(g_seg, g_vertex, head_out.shape[0], head_out.device)
+        grad = torch.empty_like(head_out)
+        head_grad_device(head_out[:, :k], head_out[:, k:], mask, vertex, vertex_weights, upstream, sigma=ctx.sigma,
+                         out=(grad[:, :k], grad[:, k:]))
+        return grad, None, None, None, None, None
+
+
+class HeadLoss(torch.nn.Module):
+    """The four loss lines of the reference's ``NetWrapper.forward`` (tools/train_linemod.py:87-91) as a differentiable module:
+    ``forward(seg_pred, vertex_pred, mask, vertex, vertex_weights) -> (loss_seg, loss_vertex, precision, recall)``, float32 [b] each,
+    bit for bit the values of ``HeadMetrics``.  ``loss_seg`` and ``loss_vertex`` carry a ``grad_fn``; ``precision`` and ``recall`` are
+    marked non-differentiable.  The backward is one ``pvnet_head_grad`` call that honours ``needs_input_grad``; it is
+    once-differentiable and gives no gradient for the mask, the targets or the weights.
+
+    ``packed(head_out, seg_dim, mask, vertex, vertex_weights)`` takes the network's output before it is sliced into the two
+    predictions (lib/networks/model_repository.py:76-78: ``x[:, :seg_dim]``, ``x[:, seg_dim:]``) and writes both gradients into one
+    tensor of its shape -- without the two zero-fill-and-copy passes the backward of torch's slices adds.  Same values."""
+
+    def __init__(self, sigma=1.0):
+        super().__init__()
+        self.sigma = float(sigma)
+
+    def forward(self, seg_pred, vertex_pred, mask, vertex, vertex_weights):
+        return _HeadLossFn.apply(seg_pred, vertex_pred, mask, vertex, vertex_weights, self.sigma)
+
+    def packed(self, head_out, seg_dim, mask, vertex, vertex_weights):
+        seg_dim = int(seg_dim)
+        if not (isinstance(head_out, torch.Tensor) and head_out.dim() == 4 and 2 <= seg_dim < head_out.shape[1]):
+            raise RuntimeError("head_out must be [b,seg_dim+2vn,h,w] with seg_dim >= 2")
+        return _PackedHeadLossFn.apply(head_out, seg_dim, mask, vertex, vertex_weights, self.sigma)
 
 
 class ValStep(object):
