@@ -1,6 +1,7 @@
 """The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h), of libpvnet_head.so
-(include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``) and of libpvnet_train.so (include/pvnet_train.h:
-``TRAIN_PROTOTYPES``, ``load_train_library``).
+(include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``), of libpvnet_train.so (include/pvnet_train.h:
+``TRAIN_PROTOTYPES``, ``load_train_library``) and of libpvnet_targets.so (include/pvnet_targets.h: ``TARGETS_PROTOTYPES``,
+``load_targets_library``).
 
 Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
 and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
@@ -120,10 +121,31 @@ TRAIN_PROTOTYPES = {
     "pvnet_head_grad": (_int, HEAD_PROTOTYPES["pvnet_head_metrics"][1][:18] + [_ptr, _ptr, _i64p, _ptr, _i64p, _ptr, _ptr, _size, _ptr]),
 }
 
+# ---- libpvnet_targets.so (include/pvnet_targets.h): the targets from the key-points and the head fused with them; it takes the
+# HEAD_F_* flags and HEAD_S_* bits above and adds one flag ----------------------------------------------------------------------------
+TARGETS_LIB_PATH = os.path.join(_HERE, "libpvnet_targets.so")
+TARGETS_ABI_VERSION = 1
+TARGETS_F_MOTION = 64   # the reference's use_motion=True: targets are not normalised
+_f32p, _f64p = _ptr, _ptr   # hcoords [b,vn,3] float64, weight_scale [b] float32 (device pointers)
+# seg_pred + strides + classes, vertex_pred + strides, hcoords, weight_scale, mask + dtype + strides, b, h, w, vn, sigma, flags
+_KP_HEAD = [_ptr, _i64p, _int, _ptr, _i64p, _f64p, _f32p, _ptr, _int, _i64p] + [_int] * 4 + [C.c_double, C.c_uint32]
+TARGETS_PROTOTYPES = {
+    "pvnet_targets_abi_version": (_int, []),
+    # mask + dtype + strides, hcoords, weight_scale, b, h, w, vn, flags, vertex + strides, vertex_weights + strides, stream
+    "pvnet_vertex_targets": (_int, [_ptr, _int, _i64p, _f64p, _f32p] + [_int] * 4 + [C.c_uint32, _ptr, _i64p, _ptr, _i64p, _ptr]),
+    "pvnet_head_metrics_kp_workspace_bytes": (_size, [_int] * 3),
+    # ..., losses, counts, status, workspace + bytes, stream
+    "pvnet_head_metrics_kp": (_int, _KP_HEAD + [_ptr, _ptr, _ptr, _ptr, _size, _ptr]),
+    "pvnet_head_grad_kp_workspace_bytes": (_size, [_int] * 3),
+    # ..., upstream, grad_seg + strides, grad_vertex + strides, status, workspace + bytes, stream
+    "pvnet_head_grad_kp": (_int, _KP_HEAD + [_ptr, _ptr, _i64p, _ptr, _i64p, _ptr, _ptr, _size, _ptr]),
+}
+
 _lib = None
 _libs = {}   # path -> loaded library
 _head_lib = None
 _train_lib = None
+_targets_lib = None
 
 
 def _wanted_library() -> str:
@@ -190,6 +212,24 @@ def load_train_library() -> C.CDLL:
             raise RuntimeError("pvnet_amd: libpvnet_train.so ABI version mismatch; rebuild it")
         _train_lib = lib
     return _train_lib
+
+
+def load_targets_library() -> C.CDLL:
+    """dlopen libpvnet_targets.so (targets from key-points, the head fused with them); loud failure if it has not been built.  There is
+    no CPU fallback."""
+    global _targets_lib
+    if _targets_lib is None:
+        if not os.path.exists(TARGETS_LIB_PATH):
+            raise RuntimeError(f"pvnet_amd: HIP library {TARGETS_LIB_PATH} is missing -- build it with "
+                               f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
+        lib = C.CDLL(TARGETS_LIB_PATH)
+        for name, (restype, argtypes) in TARGETS_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if lib.pvnet_targets_abi_version() != TARGETS_ABI_VERSION:
+            raise RuntimeError("pvnet_amd: libpvnet_targets.so ABI version mismatch; rebuild it")
+        _targets_lib = lib
+    return _targets_lib
 
 
 def reload_tuning():

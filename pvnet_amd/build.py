@@ -1,5 +1,6 @@
-"""Builds libpvnet_vote.so (the C-ABI HIP library), libpvnet_head.so (the head metrics, a library of its own) and libpvnet_train.so
-(the head losses' backward, likewise) in-tree for gfx950 with hipcc.
+"""Builds libpvnet_vote.so (the C-ABI HIP library), libpvnet_head.so (the head metrics, a library of its own), libpvnet_train.so
+(the head losses' backward, likewise) and libpvnet_targets.so (the targets from key-points and the head fused with them, likewise)
+in-tree for gfx950 with hipcc.
 
     python -m pvnet_amd.build            # build if sources are newer than the library
     python -m pvnet_amd.build --force
@@ -32,16 +33,24 @@ ARCH = "gfx950"
 # and its ABI stay as they are
 HEAD_TU = ["head_metrics.hip"]
 HEAD_SRC = [os.path.join(CSRC, f) for f in HEAD_TU]
-HEAD_DEPS = HEAD_SRC + [os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_head.h"),
+HEAD_DEPS = HEAD_SRC + [os.path.join(CSRC, "head_common.h"), os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_head.h"),
                         os.path.join(ROOT, "include", "pvnet_vote.h")]
 HEAD_LIB = os.path.join(HERE, "libpvnet_head.so")
 # the backward of the head losses of a training step (include/pvnet_train.h): one translation unit, a library of its own again --
 # libpvnet_head.so and its ABI stay as they are
 TRAIN_TU = ["head_grad.hip"]
 TRAIN_SRC = [os.path.join(CSRC, f) for f in TRAIN_TU]
-TRAIN_DEPS = TRAIN_SRC + [os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_train.h"),
+TRAIN_DEPS = TRAIN_SRC + [os.path.join(CSRC, "head_common.h"), os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_train.h"),
                           os.path.join(ROOT, "include", "pvnet_head.h"), os.path.join(ROOT, "include", "pvnet_vote.h")]
 TRAIN_LIB = os.path.join(HERE, "libpvnet_train.so")
+# the training targets from the key-points and the head's forward and backward fused with them (include/pvnet_targets.h): one
+# translation unit, a library of its own -- the three above and their ABIs stay as they are
+TARGETS_TU = ["head_targets.hip"]
+TARGETS_SRC = [os.path.join(CSRC, f) for f in TARGETS_TU]
+TARGETS_DEPS = TARGETS_SRC + [os.path.join(CSRC, "head_common.h"), os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"),
+                              os.path.join(ROOT, "include", "pvnet_targets.h"), os.path.join(ROOT, "include", "pvnet_head.h"),
+                              os.path.join(ROOT, "include", "pvnet_vote.h")]
+TARGETS_LIB = os.path.join(HERE, "libpvnet_targets.so")
 # host-side pose refinement (plain C++, g++): include/pvnet_pnp.h
 PNP_SRC = os.path.join(HERE, "csrc", "pvnet_pnp.cpp")
 PNP_DEPS = [PNP_SRC, os.path.join(ROOT, "include", "pvnet_pnp.h")]
@@ -147,6 +156,24 @@ def build_train(force: bool = False, verbose: bool = False) -> str:
         if os.path.exists(tmp):
             os.remove(tmp)
     return TRAIN_LIB
+
+
+def build_targets(force: bool = False, verbose: bool = False) -> str:
+    """hipcc -> libpvnet_targets.so; like build_head it replaces the previous library only after the register check passed"""
+    if not force and os.path.exists(TARGETS_LIB) and all(os.path.getmtime(TARGETS_LIB) >= os.path.getmtime(d) for d in TARGETS_DEPS):
+        return TARGETS_LIB
+    tmp = TARGETS_LIB + ".new"
+    try:
+        cmd = [hipcc_path()] + flags() + TARGETS_SRC + ["-o", tmp]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        check_resources(("check_kernel_resources.py",), ["--targets"])
+        os.replace(tmp, TARGETS_LIB)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return TARGETS_LIB
 
 
 # the reference's compiled extension module `ransac_voting` (src/ransac_voting.cpp) on this library: host-only C++ against
@@ -257,6 +284,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 os.remove(tmp)
     build_head(force, verbose)
     build_train(force, verbose)
+    build_targets(force, verbose)
     build_ext(force, verbose)
     build_canary(force, verbose)
     return LIB

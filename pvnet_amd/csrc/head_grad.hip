@@ -25,39 +25,35 @@
 // two calls agree bit for bit.  float64 after the load; each element is rounded ONCE to its tensor's type (float16 / bfloat16 through
 // a round-to-odd float32, which makes the second rounding exact).
 //
-// The load helpers restate those of head_metrics.hip: that translation unit is libpvnet_head.so's alone and is not touched.
+// The load and store helpers, the two formulas and the per-image bodies are head_common.h's, shared with head_metrics.hip.
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "head_common.h"   // the per-pixel helpers and the per-image bodies the head's translation units share
 #include "pvnet_train.h"
-#include "vote_common.h"   // ld_elem / ld_elem_rt (VT_*), PVNET_SPARE_VGPRS
 
 // no contraction: every product and sum rounds as the float64 restatement's separate operations do
 #pragma clang fp contract(off)
 
 namespace {
 
-using pvd::VT_BF16;
-using pvd::VT_F16;
-using pvd::VT_F32;
+using namespace pvh;
 
-constexpr int HG_T = 128;                // lanes of a workgroup of the per-pixel kernels
-constexpr int HG_PPL = 8;                // consecutive pixels per lane (fast path)
-constexpr int HG_SEG = HG_T * HG_PPL;    // pixels per workgroup
-constexpr int HG_FT = 256;               // lanes of the per-image workgroups
-constexpr int HG_MAX_B = 65535;
-constexpr int HG_MAX_PIXELS = 1 << 30;
+constexpr int HG_T = HC_T;                // lanes of a workgroup of the per-pixel kernels
+constexpr int HG_PPL = HC_PPL;            // consecutive pixels per lane (fast path)
+constexpr int HG_SEG = HC_SEG;            // pixels per workgroup
+constexpr int HG_FT = HC_FT;              // lanes of the per-image workgroups
+constexpr int HG_MAX_B = HC_MAX_B;
+constexpr int HG_MAX_PIXELS = HC_MAX_PIXELS;
 // the spare-VGPR granule of each kernel (PVNET_SPARE_VGPRS in vote_common.h; tools/check_kernel_resources.py holds them to it)
 #define HG_FAST_SPARE 135
 #define HG_GENERAL_SPARE 79
 #define HG_WSUM_SPARE 31
 #define HG_FINAL_SPARE 31
 #define HG_STATUS_SPARE 23
-
-enum { NT_NONE = 0, NT_TARGETS = 1, NT_ALL = 2 };
 
 struct GradArgs {
     const void* seg;
@@ -77,180 +73,6 @@ struct GradArgs {
     int32_t* bad;     // [b][nseg]: the segment holds a label outside 0 .. C-1
     int32_t* status;
 };
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
-
-template <bool NT, typename V>
-__device__ __forceinline__ V ldv(const void* p) {
-    return NT ? __builtin_nontemporal_load(reinterpret_cast<const V*>(p)) : *reinterpret_cast<const V*>(p);
-}
-template <bool NT, typename V>
-__device__ __forceinline__ void stv(void* p, V v) {
-    if (NT) __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
-    else *reinterpret_cast<V*>(p) = v;
-}
-
-// eight consecutive elements at element offset `off` (a multiple of 8 from a 16-byte aligned base), widened to float32
-template <int VT, bool NT>
-__device__ __forceinline__ void load8(const void* base, int64_t off, float* o) {
-    if (VT == VT_F32) {
-        const float* p = reinterpret_cast<const float*>(base) + off;
-        const f32x4 a = ldv<NT, f32x4>(p), b = ldv<NT, f32x4>(p + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            o[i] = a[i];
-            o[4 + i] = b[i];
-        }
-    } else if (VT == VT_F16) {
-        const f16x8 a = ldv<NT, f16x8>(reinterpret_cast<const _Float16*>(base) + off);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (float)a[i];
-    } else {
-        const u32x4 a = ldv<NT, u32x4>(reinterpret_cast<const uint16_t*>(base) + off);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            o[2 * i] = __uint_as_float(a[i] << 16);
-            o[2 * i + 1] = __uint_as_float(a[i] & 0xFFFF0000u);
-        }
-    }
-}
-template <bool NT>
-__device__ __forceinline__ void load8_rt(int vt, const void* base, int64_t off, float* o) {   // workgroup-uniform type
-    if (vt == VT_F16) load8<VT_F16, NT>(base, off, o);
-    else if (vt == VT_BF16) load8<VT_BF16, NT>(base, off, o);
-    else load8<VT_F32, NT>(base, off, o);
-}
-
-// a float64 rounded to float32 to odd: where the conversion is inexact the result's last bit is set.  Rounding that to a narrower
-// type (11 or 8 significant bits) gives what one rounding of the float64 would have given.
-__device__ __forceinline__ float to_f32_odd(double x) {
-    float f = (float)x;
-    const double r = (double)f;
-    if (r != x && x == x) {
-        uint32_t u = __float_as_uint(f);
-        if ((u & 1u) == 0) u += fabs(r) > fabs(x) ? 0xFFFFFFFFu : 1u;   // the other neighbour of x (sign and magnitude: +-1 steps it)
-        f = __uint_as_float(u);
-    }
-    return f;
-}
-__device__ __forceinline__ uint32_t to_bf16_bits(double x) {   // round to nearest even
-    const uint32_t u = __float_as_uint(to_f32_odd(x));
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;   // NaN stays NaN
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
-// eight consecutive gradient elements, each rounded once to the tensor's type
-template <int VT, bool NT>
-__device__ __forceinline__ void store8(void* base, int64_t off, const double* g) {
-    if (VT == VT_F32) {
-        float* p = reinterpret_cast<float*>(base) + off;
-        f32x4 a, b;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            a[i] = (float)g[i];
-            b[i] = (float)g[4 + i];
-        }
-        stv<NT, f32x4>(p, a);
-        stv<NT, f32x4>(p + 4, b);
-    } else if (VT == VT_F16) {
-        f16x8 a;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a[i] = (_Float16)to_f32_odd(g[i]);
-        stv<NT, f16x8>(reinterpret_cast<_Float16*>(base) + off, a);
-    } else {
-        u32x4 a;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = to_bf16_bits(g[2 * i]) | (to_bf16_bits(g[2 * i + 1]) << 16);
-        stv<NT, u32x4>(reinterpret_cast<uint16_t*>(base) + off, a);
-    }
-}
-template <bool NT>
-__device__ __forceinline__ void store8_rt(int vt, void* base, int64_t off, const double* g) {   // workgroup-uniform type
-    if (vt == VT_F16) store8<VT_F16, NT>(base, off, g);
-    else if (vt == VT_BF16) store8<VT_BF16, NT>(base, off, g);
-    else store8<VT_F32, NT>(base, off, g);
-}
-__device__ __forceinline__ void store_elem_rt(int vt, void* base, int64_t off, double g) {
-    if (vt == VT_F16) reinterpret_cast<_Float16*>(base)[off] = (_Float16)to_f32_odd(g);
-    else if (vt == VT_BF16) reinterpret_cast<uint16_t*>(base)[off] = (uint16_t)to_bf16_bits(g);
-    else reinterpret_cast<float*>(base)[off] = (float)g;
-}
-
-// a label as the kernels use it: 0 .. C-1, or -1 for a value outside
-__device__ __forceinline__ int label_of(long long v, int C) { return (v < 0 || v >= C) ? -1 : (int)v; }
-
-template <bool NT>
-__device__ __forceinline__ void load8_labels(int dt, const void* base, int64_t off, int C, int* lab) {
-    if (dt == PVNET_MASK_U8) {
-        const u32x2 a = ldv<NT, u32x2>(reinterpret_cast<const uint8_t*>(base) + off);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) lab[i] = label_of((a[i >> 2] >> (8 * (i & 3))) & 0xFFu, C);
-    } else if (dt == PVNET_MASK_I32) {
-        const int32_t* p = reinterpret_cast<const int32_t*>(base) + off;
-        const u32x4 a = ldv<NT, u32x4>(p), b = ldv<NT, u32x4>(p + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lab[i] = label_of((int32_t)a[i], C);
-            lab[4 + i] = label_of((int32_t)b[i], C);
-        }
-    } else {
-        const long long* p = reinterpret_cast<const long long*>(base) + off;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const i64x2 a = ldv<NT, i64x2>(p + 2 * i);
-            lab[2 * i] = label_of(a.x, C);
-            lab[2 * i + 1] = label_of(a.y, C);
-        }
-    }
-}
-
-__device__ __forceinline__ long long load_label_rt(int dt, const void* base, int64_t off) {
-    if (dt == PVNET_MASK_U8) return reinterpret_cast<const uint8_t*>(base)[off];
-    if (dt == PVNET_MASK_I32) return reinterpret_cast<const int32_t*>(base)[off];
-    return reinterpret_cast<const long long*>(base)[off];
-}
-
-// the running maximum of the logits as the forward keeps it: a NaN counts as the maximum and stays
-__device__ __forceinline__ bool takes_over(float best, float x) { return (best == best) & !(x <= best); }
-
-// the gradient of one field element over the image's coefficient kv = u_v / D_i: d = w (p - t); w d sigma^2 where |d| < 1 / sigma^2,
-// else w sign(d).  A NaN fails the comparison, takes the second branch and stays NaN; w = 0 gives d = 0 and an exact zero.
-__device__ __forceinline__ double field_grad(const GradArgs& A, double w, float p, float t, double kv) {
-    const double d = w * ((double)p - (double)t);
-    const double sgn = d > 0.0 ? 1.0 : d < 0.0 ? -1.0 : d;
-    return (fabs(d) < A.inv ? w * (d * A.s2) : w * sgn) * kv;
-}
-
-// the gradient of one logit over ks = u_s / (h w): e / S for another class than the label's; for the label's class minus the
-// others' share, rest / S -- not e / S - 1, which cancels once the label's logit leads by a margin
-__device__ __forceinline__ double logit_grad(int lab, int c, double e, double sum, double rest, double ks) {
-    if (lab < 0) return __builtin_nan("");
-    return lab == c ? -(ks * (rest / sum)) : ks * (e / sum);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {   // xor butterfly: every lane ends with the same, order-fixed sum
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
-// the workgroup's sum: waves reduced by butterfly, then added in wave order; valid in lane 0
-template <int T>
-__device__ __forceinline__ double block_sum(double v) {
-    constexpr int NW = T / 64;
-    __shared__ double s_d[NW];
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s_d[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = s_d[0];
-#pragma unroll
-    for (int i = 1; i < NW; ++i) v = v + s_d[i];
-    return v;
-}
 
 template <bool FAST>
 __global__ __launch_bounds__(HG_T) void head_grad_wsum_kernel(GradArgs A) {
@@ -279,16 +101,7 @@ __global__ __launch_bounds__(HG_T) void head_grad_wsum_kernel(GradArgs A) {
 
 __global__ __launch_bounds__(HG_FT) void head_grad_final_kernel(GradArgs A) {
     PVNET_SPARE_VGPRS(HG_FINAL_SPARE);
-    const int bi = blockIdx.x;
-    double wsum = 0.0;
-    if (A.gv) {
-        const double* rec = A.wpart + (size_t)bi * A.nseg;
-        for (int k = threadIdx.x; k < A.nseg; k += HG_FT) wsum = wsum + rec[k];   // lane t: records t, t + 256, ... in order
-        wsum = block_sum<HG_FT>(wsum);
-    }
-    if (threadIdx.x != 0) return;
-    A.coef[2 * bi] = A.upstream[2 * bi] / (double)A.npix;
-    A.coef[2 * bi + 1] = A.upstream[2 * bi + 1] / ((double)A.planes * wsum + 1e-3);   // net_utils.py:74
+    head_grad_final_image(A);
 }
 
 template <int VT, int NT>
@@ -414,24 +227,8 @@ __global__ __launch_bounds__(HG_T) void head_grad_general_kernel(GradArgs A) {
 
 __global__ __launch_bounds__(HG_FT) void head_grad_status_kernel(GradArgs A) {
     PVNET_SPARE_VGPRS(HG_STATUS_SPARE);
-    const int bi = blockIdx.x;
-    int bad = 0;
-    if (A.gs) {   // (without the logits' half the mask was not read: status 0)
-        const int32_t* rec = A.bad + (size_t)bi * A.nseg;
-        for (int k = threadIdx.x; k < A.nseg; k += HG_FT) bad |= rec[k];
-    }
-    const int any = __syncthreads_or(bad);
-    if (threadIdx.x == 0) A.status[bi] = any ? PVNET_HEAD_S_BAD_LABEL : 0;
+    head_grad_status_image(A);
 }
-
-// a tensor's planes can be accessed eight pixels at a time: pixels contiguous, base and every plane / image start on 16 bytes
-bool plane_linear(const void* base, int b, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int w) {
-    return sw == 1 && sh == w && (b == 1 || sb % 8 == 0) && sc % 8 == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
-}
-
-int type_of(uint32_t flags, uint32_t f16, uint32_t bf16) { return (flags & f16) ? VT_F16 : (flags & bf16) ? VT_BF16 : VT_F32; }
-
-size_t round256(size_t n) { return (n + 255) / 256 * 256; }
 
 template <int VT>
 void launch_fast(int nt, dim3 grid, hipStream_t s, const GradArgs& A) {

@@ -26,36 +26,26 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "head_common.h"   // the per-pixel helpers, the records and the per-image body the head's translation units share
 #include "pvnet_head.h"
-#include "vote_common.h"   // ld_elem / ld_elem_rt (VT_*), PVNET_SPARE_VGPRS
 
 // no contraction: the sums round as the float64 restatement's separate multiplies and adds do
 #pragma clang fp contract(off)
 
 namespace {
 
-using pvd::VT_BF16;
-using pvd::VT_F16;
-using pvd::VT_F32;
+using namespace pvh;
 
-constexpr int HM_T = 128;                // lanes of a pass-1 workgroup
-constexpr int HM_PPL = 8;                // consecutive pixels per lane (fast path)
-constexpr int HM_SEG = HM_T * HM_PPL;    // pixels per workgroup = per partial record
-constexpr int HM_FT = 256;               // lanes of the final workgroup
-constexpr int HM_MAX_B = 65535;
-constexpr int HM_MAX_PIXELS = 1 << 30;
+constexpr int HM_T = HC_T;                // lanes of a pass-1 workgroup
+constexpr int HM_PPL = HC_PPL;            // consecutive pixels per lane (fast path)
+constexpr int HM_SEG = HC_SEG;            // pixels per workgroup = per partial record
+constexpr int HM_FT = HC_FT;              // lanes of the final workgroup
+constexpr int HM_MAX_B = HC_MAX_B;
+constexpr int HM_MAX_PIXELS = HC_MAX_PIXELS;
 // the spare-VGPR granule of each kernel (PVNET_SPARE_VGPRS in vote_common.h; tools/check_kernel_resources.py holds them to it)
 #define HM_FAST_SPARE 119
 #define HM_GENERAL_SPARE 87
 #define HM_FINAL_SPARE 71
-
-enum { NT_NONE = 0, NT_TARGETS = 1, NT_ALL = 2 };
-
-struct HeadPartial {   // 32 bytes
-    double ce, sl1, wsum;
-    unsigned long long packed;   // tp | fp << 16 | fn << 32 | bad << 48: each at most HM_SEG
-};
-static_assert(sizeof(HeadPartial) == 32 && HM_SEG < (1 << 16), "a record's four counts share one 64-bit word");
 
 struct HeadArgs {
     const void* seg;
@@ -72,160 +62,6 @@ struct HeadArgs {
     int32_t* status;
     HeadPartial* partial;
 };
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef long long i64x2 __attribute__((ext_vector_type(2)));
-
-template <bool NT, typename V>
-__device__ __forceinline__ V ldv(const void* p) {
-    return NT ? __builtin_nontemporal_load(reinterpret_cast<const V*>(p)) : *reinterpret_cast<const V*>(p);
-}
-
-// eight consecutive elements at element offset `off` (a multiple of 8 from a 16-byte aligned base), widened to float32
-template <int VT, bool NT>
-__device__ __forceinline__ void load8(const void* base, int64_t off, float* o) {
-    if (VT == VT_F32) {
-        const float* p = reinterpret_cast<const float*>(base) + off;
-        const f32x4 a = ldv<NT, f32x4>(p), b = ldv<NT, f32x4>(p + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            o[i] = a[i];
-            o[4 + i] = b[i];
-        }
-    } else if (VT == VT_F16) {
-        const f16x8 a = ldv<NT, f16x8>(reinterpret_cast<const _Float16*>(base) + off);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (float)a[i];
-    } else {
-        const u32x4 a = ldv<NT, u32x4>(reinterpret_cast<const uint16_t*>(base) + off);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            o[2 * i] = __uint_as_float(a[i] << 16);
-            o[2 * i + 1] = __uint_as_float(a[i] & 0xFFFF0000u);
-        }
-    }
-}
-template <bool NT>
-__device__ __forceinline__ void load8_rt(int vt, const void* base, int64_t off, float* o) {   // workgroup-uniform type
-    if (vt == VT_F16) load8<VT_F16, NT>(base, off, o);
-    else if (vt == VT_BF16) load8<VT_BF16, NT>(base, off, o);
-    else load8<VT_F32, NT>(base, off, o);
-}
-
-// a label as the kernels use it: 0 .. C-1, or -1 for a value outside (which is still "not background")
-__device__ __forceinline__ int label_of(long long v, int C) { return (v < 0 || v >= C) ? -1 : (int)v; }
-
-template <bool NT>
-__device__ __forceinline__ void load8_labels(int dt, const void* base, int64_t off, int C, int* lab) {
-    if (dt == PVNET_MASK_U8) {
-        const u32x2 a = ldv<NT, u32x2>(reinterpret_cast<const uint8_t*>(base) + off);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) lab[i] = label_of((a[i >> 2] >> (8 * (i & 3))) & 0xFFu, C);
-    } else if (dt == PVNET_MASK_I32) {
-        const int32_t* p = reinterpret_cast<const int32_t*>(base) + off;
-        const u32x4 a = ldv<NT, u32x4>(p), b = ldv<NT, u32x4>(p + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lab[i] = label_of((int32_t)a[i], C);
-            lab[4 + i] = label_of((int32_t)b[i], C);
-        }
-    } else {
-        const long long* p = reinterpret_cast<const long long*>(base) + off;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const i64x2 a = ldv<NT, i64x2>(p + 2 * i);
-            lab[2 * i] = label_of(a.x, C);
-            lab[2 * i + 1] = label_of(a.y, C);
-        }
-    }
-}
-
-__device__ __forceinline__ long long load_label_rt(int dt, const void* base, int64_t off) {
-    if (dt == PVNET_MASK_U8) return reinterpret_cast<const uint8_t*>(base)[off];
-    if (dt == PVNET_MASK_I32) return reinterpret_cast<const int32_t*>(base)[off];
-    return reinterpret_cast<const long long*>(base)[off];
-}
-
-// torch.argmax's rule (k1_mask.hip:69-80): the first maximum wins and a NaN counts as the maximum -- a NaN replaces a number, a
-// later NaN never an earlier one
-__device__ __forceinline__ bool takes_over(float best, float x) { return (best == best) & !(x <= best); }
-
-// one smooth-L1 term (net_utils.py:66-71): d = w (p - t); d^2 sigma^2 / 2 where |d| < 1 / sigma^2, else |d| - 0.5 / sigma^2.  A NaN
-// fails the comparison, takes the second branch and stays NaN.
-__device__ __forceinline__ double smooth_l1(const HeadArgs& A, double w, float p, float t) {
-    const double d = w * ((double)p - (double)t);
-    const double a = fabs(d);
-    return a < A.inv ? d * d * A.hs : a - A.half;
-}
-
-// log(sum_c exp(s_c - m)) - (s_label - m): the cross-entropy of one pixel with the maximum m subtracted first, as log_softmax does
-__device__ __forceinline__ double cross_entropy(double sum, float s_label, float m) {
-    return log(sum) - ((double)s_label - (double)m);
-}
-
-struct Acc {
-    double ce = 0.0, sl1 = 0.0, wsum = 0.0;
-    unsigned long long packed = 0;
-};
-constexpr unsigned long long ONE_TP = 1ull, ONE_FP = 1ull << 16, ONE_FN = 1ull << 32, ONE_BAD = 1ull << 48;
-
-__device__ __forceinline__ unsigned long long confusion(bool pred_fg, int lab) {
-    const bool fg = lab != 0;
-    return (pred_fg && fg ? ONE_TP : 0) | (pred_fg && !fg ? ONE_FP : 0) | (!pred_fg && fg ? ONE_FN : 0) | (lab < 0 ? ONE_BAD : 0);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {   // xor butterfly: every lane ends with the same, order-fixed sum
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
-// the workgroup's record: waves reduced by butterfly, then added in wave order by lane 0
-template <int T>
-__device__ __forceinline__ bool block_reduce(Acc& a) {
-    constexpr int NW = T / 64;
-    __shared__ double s_d[NW][3];
-    __shared__ unsigned long long s_p[NW];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const double ce = wave_sum(a.ce), sl1 = wave_sum(a.sl1), wsum = wave_sum(a.wsum);
-    const unsigned long long packed = wave_sum(a.packed);
-    if (lane == 0) {
-        s_d[wave][0] = ce;
-        s_d[wave][1] = sl1;
-        s_d[wave][2] = wsum;
-        s_p[wave] = packed;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return false;
-    a.ce = s_d[0][0];
-    a.sl1 = s_d[0][1];
-    a.wsum = s_d[0][2];
-    a.packed = s_p[0];
-#pragma unroll
-    for (int i = 1; i < NW; ++i) {
-        a.ce = a.ce + s_d[i][0];
-        a.sl1 = a.sl1 + s_d[i][1];
-        a.wsum = a.wsum + s_d[i][2];
-        a.packed = a.packed + s_p[i];
-    }
-    return true;
-}
-
-__device__ __forceinline__ void store_partial(const HeadArgs& A, const Acc& a) {
-    HeadPartial* r = A.partial + (size_t)blockIdx.y * A.nseg + blockIdx.x;
-    r->ce = a.ce;
-    r->sl1 = a.sl1;
-    r->wsum = a.wsum;
-    r->packed = a.packed;
-}
 
 template <int VT, int NT>
 __global__ __launch_bounds__(HM_T) void head_partial_kernel(HeadArgs A) {
@@ -331,59 +167,8 @@ __global__ __launch_bounds__(HM_T) void head_partial_general_kernel(HeadArgs A) 
 
 __global__ __launch_bounds__(HM_FT) void head_final_kernel(HeadArgs A) {
     PVNET_SPARE_VGPRS(HM_FINAL_SPARE);
-    const int bi = blockIdx.x;
-    Acc acc;
-    long long tp = 0, fp = 0, fn = 0, bad = 0;   // a record's packed counts are unpacked before they are added: no field overflows
-    const HeadPartial* rec = A.partial + (size_t)bi * A.nseg;
-    for (int k = threadIdx.x; k < A.nseg; k += HM_FT) {   // lane t: records t, t + 256, ... in order
-        acc.ce = acc.ce + rec[k].ce;
-        acc.sl1 = acc.sl1 + rec[k].sl1;
-        acc.wsum = acc.wsum + rec[k].wsum;
-        const unsigned long long q = rec[k].packed;
-        tp += (long long)(q & 0xFFFFu);
-        fp += (long long)((q >> 16) & 0xFFFFu);
-        fn += (long long)((q >> 32) & 0xFFFFu);
-        bad += (long long)(q >> 48);
-    }
-    __shared__ long long s_cnt[HM_FT / 64][4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    tp = (long long)wave_sum((unsigned long long)tp);
-    fp = (long long)wave_sum((unsigned long long)fp);
-    fn = (long long)wave_sum((unsigned long long)fn);
-    bad = (long long)wave_sum((unsigned long long)bad);
-    if (lane == 0) {
-        s_cnt[wave][0] = tp;
-        s_cnt[wave][1] = fp;
-        s_cnt[wave][2] = fn;
-        s_cnt[wave][3] = bad;
-    }
-    if (!block_reduce<HM_FT>(acc)) return;   // (its barrier also orders s_cnt)
-    tp = fp = fn = bad = 0;
-#pragma unroll
-    for (int i = 0; i < HM_FT / 64; ++i) {
-        tp += s_cnt[i][0];
-        fp += s_cnt[i][1];
-        fn += s_cnt[i][2];
-        bad += s_cnt[i][3];
-    }
-    double* out = A.losses + (size_t)bi * 4;
-    out[0] = bad ? __builtin_nan("") : acc.ce / (double)A.npix;
-    out[1] = acc.sl1 / ((double)A.planes * acc.wsum + 1e-3);   // net_utils.py:74
-    out[2] = ((double)tp + 1.0) / ((double)tp + (double)fp + 1.0);
-    out[3] = ((double)tp + 1.0) / ((double)tp + (double)fn + 1.0);
-    int64_t* cnt = A.counts + (size_t)bi * 3;
-    cnt[0] = tp;
-    cnt[1] = fp;
-    cnt[2] = fn;
-    if (A.status) A.status[bi] = bad ? PVNET_HEAD_S_BAD_LABEL : 0;
+    head_final_image(A);
 }
-
-// a tensor's planes can be read eight pixels at a time: pixels contiguous, base and every plane / image start on 16 bytes
-bool plane_linear(const void* base, int b, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int w) {
-    return sw == 1 && sh == w && (b == 1 || sb % 8 == 0) && sc % 8 == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
-}
-
-int type_of(uint32_t flags, uint32_t f16, uint32_t bf16) { return (flags & f16) ? VT_F16 : (flags & bf16) ? VT_BF16 : VT_F32; }
 
 template <int VT>
 void launch_fast(int nt, dim3 grid, hipStream_t s, const HeadArgs& A) {

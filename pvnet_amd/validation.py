@@ -8,6 +8,10 @@
 * ``head_grad_device`` / ``HeadLoss`` -- the same four lines as the loss of the reference's TRAINING loop (train_linemod.py:146-153):
   ``HeadLoss`` is ``HeadMetrics`` with a backward, ONE fused pass that reads the forward's inputs again and writes both gradients
   (``pvnet_head_grad``, pvnet_amd/csrc/head_grad.hip, libpvnet_train.so; C ABI and the formulas: include/pvnet_train.h).
+* ``vertex_targets_device`` and the ``*_from_keypoints`` forms of all of the above -- the target field and its weights made on the
+  device from the mask and the loader's ``hcoords`` (the reference's ``compute_vertex_hcoords``, lib/datasets/linemod_dataset.py:68-81,
+  bit for bit), either written out or computed in registers inside the head's forward and backward, which then never read a target
+  (pvnet_amd/csrc/head_targets.hip, libpvnet_targets.so; C ABI and the definition: include/pvnet_targets.h).
 * ``ValStep`` -- the whole step on the current stream: head metrics, then ``voting.PoseEvalWrapper`` (fused arg-max voting and the
   pose solve), then the pose metrics ``Evaluator.evaluate_batch`` records (``evaluation.pose_metrics_device``); one host copy at the
   end.  ``enqueue`` is the part a graph captures.
@@ -21,7 +25,8 @@ import ctypes as C
 import torch
 
 from ._abi import (HEAD_F_LOGITS_BF16, HEAD_F_LOGITS_F16, HEAD_F_NT_ALL, HEAD_F_NT_NONE, HEAD_F_VERTEX_BF16,  # noqa: F401
-                   HEAD_F_VERTEX_F16, HEAD_S_BAD_LABEL, MASK_I32, MASK_I64, MASK_U8, _check, load_head_library, load_train_library)
+                   HEAD_F_VERTEX_F16, HEAD_S_BAD_LABEL, MASK_I32, MASK_I64, MASK_U8, TARGETS_F_MOTION, _check, load_head_library,
+                   load_targets_library, load_train_library)
 
 _VERTEX_FLAGS = {torch.float32: 0, torch.float16: HEAD_F_VERTEX_F16, torch.bfloat16: HEAD_F_VERTEX_BF16}
 _LOGITS_FLAGS = {torch.float32: 0, torch.float16: HEAD_F_LOGITS_F16, torch.bfloat16: HEAD_F_LOGITS_BF16}
@@ -130,6 +135,12 @@ class HeadMetrics(torch.nn.Module):
         losses, _, _ = head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=self.sigma)
         return tuple(losses.to(torch.float32).unbind(1))
 
+    def from_keypoints(self, seg_pred, vertex_pred, mask, hcoords, weight_scale=None, use_motion=False):
+        """the same four values from the loader's ``hcoords`` instead of the target field (``head_metrics_from_keypoints``)"""
+        losses, _, _ = head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_scale, sigma=self.sigma,
+                                                   use_motion=use_motion)
+        return tuple(losses.to(torch.float32).unbind(1))
+
 
 def head_grad_workspace_bytes(b, h, w):
     """the workspace ``head_grad_device`` needs for b images of h x w pixels (bytes)"""
@@ -196,6 +207,174 @@ def head_grad_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, upstre
     return grad_seg, grad_vertex, status
 
 
+# ---- the targets from the key-points (libpvnet_targets.so) ---------------------------------------------------------------------------
+def _keypoint_inputs(mask, hcoords, weight_scale):
+    """the checks the key-point entries share -> (device, b, h, w, vn, hcoords [b,vn,3] float64 contiguous, weight_scale or None)"""
+    for name, t in (("mask", mask), ("hcoords", hcoords)) + ((("weight_scale", weight_scale),) if weight_scale is not None else ()):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name} must be a CUDA tensor (there is no CPU fallback)")
+    dev = mask.device
+    if mask.dim() != 3 or mask.dtype not in _MASK_CODES:
+        raise RuntimeError(f"mask must be [b,h,w], uint8, bool, int32 or int64, got {tuple(mask.shape)} {mask.dtype}")
+    b, h, w = (int(x) for x in mask.shape)
+    if hcoords.device != dev or hcoords.dim() != 3 or hcoords.shape[0] != b or hcoords.shape[1] < 1 or hcoords.shape[2] not in (2, 3) or \
+            hcoords.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"hcoords must be [b,vn,3] (or [b,vn,2]: hz = 1) float32 or float64 on {dev} with b={b}, got "
+                           f"{tuple(hcoords.shape)} {hcoords.dtype}")
+    hc = hcoords.to(torch.float64)   # (float32 widens exactly: the reference's numpy computes in float64 whatever arrives)
+    if hc.shape[2] == 2:
+        hc = torch.cat([hc, torch.ones_like(hc[:, :, :1])], 2)
+    hc = hc.contiguous()
+    if weight_scale is not None:
+        if weight_scale.device != dev or tuple(weight_scale.shape) != (b,) or not weight_scale.dtype.is_floating_point:
+            raise RuntimeError(f"weight_scale must be a floating-point tensor of shape {(b,)} on {dev}")
+        weight_scale = weight_scale.to(torch.float32).contiguous()
+    return dev, b, h, w, int(hc.shape[1]), hc, weight_scale
+
+
+def _opt_ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def vertex_targets_device(mask, hcoords, weight_scale=None, use_motion=False, out=None):
+    """The reference's ``compute_vertex_hcoords`` (lib/datasets/linemod_dataset.py:68-81) and ``mask.float()`` weights (:227) for a
+    batch, enqueued on the current stream -- no synchronisation, no host copy.  Bit for bit what the reference's numpy computes.
+
+    :param mask:         [b,h,w] uint8 / bool / int32 / int64 CUDA tensor, any strides.  Target pixels are ``mask == 1``
+    :param hcoords:      [b,vn,3] homogeneous 2-D key-points as the loader returns them (float64, or float32 which widens exactly);
+                         [b,vn,2] is taken as hz = 1 (tools/demo.py:58-71)
+    :param weight_scale: None (1), or [b]: a factor on an image's weights (the reference's ``ver_weight *= 0.0`` of its "fuse" images)
+    :param use_motion:   the reference's ``use_motion=True``: the targets are not normalised
+    :param out:          None, or caller-owned float32 ``(vertex [b,2vn,h,w], vertex_weights [b,1,h,w])``, ANY strides; either may be
+                         ``None`` to skip that output
+    :return: ``(vertex, vertex_weights)``: plane 2k of ``vertex`` is x and plane 2k+1 is y of key-point k, zero off ``mask == 1``;
+             the weight of a pixel is its mask VALUE times the image's scale."""
+    lib = load_targets_library()
+    dev, b, h, w, vn, hc, weight_scale = _keypoint_inputs(mask, hcoords, weight_scale)
+    with torch.cuda.device(dev):
+        if out is None:
+            vertex = torch.empty((b, 2 * vn, h, w), dtype=torch.float32, device=dev)
+            weights = torch.empty((b, 1, h, w), dtype=torch.float32, device=dev)
+        else:
+            vertex, weights = out
+            for t, shape, name in ((vertex, (b, 2 * vn, h, w), "out[0]"), (weights, (b, 1, h, w), "out[1]")):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and
+                                          tuple(t.shape) == shape):
+                    raise RuntimeError(f"{name} must be a float32 CUDA tensor of shape {shape} on {dev}")
+            if vertex is None and weights is None:
+                raise RuntimeError("out: at least one of the two outputs must be asked for")
+        if b == 0:
+            return vertex, weights
+        _check(lib.pvnet_vertex_targets(
+            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)), C.c_void_p(hc.data_ptr()),
+            _opt_ptr(weight_scale), b, h, w, vn, TARGETS_F_MOTION if use_motion else 0,
+            _opt_ptr(vertex), None if vertex is None else _strides(vertex, (0, 1, 2, 3)),
+            _opt_ptr(weights), None if weights is None else _strides(weights, (0, 2, 3)),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_vertex_targets")
+    return vertex, weights
+
+
+def _kp_head_inputs(seg_pred, vertex_pred, mask, hcoords, weight_scale, flags, use_motion):
+    """the checks ``head_metrics_from_keypoints`` and ``head_grad_from_keypoints`` share"""
+    for name, t in (("seg_pred", seg_pred), ("vertex_pred", vertex_pred)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name} must be a CUDA tensor (there is no CPU fallback)")
+    dev, b, h, w, vn, hc, weight_scale = _keypoint_inputs(mask, hcoords, weight_scale)
+    if seg_pred.device != dev or vertex_pred.device != dev:
+        raise RuntimeError("seg_pred, vertex_pred, mask and hcoords must live on the same device")
+    if seg_pred.dim() != 4 or seg_pred.shape[1] < 2 or (seg_pred.shape[0], seg_pred.shape[2], seg_pred.shape[3]) != (b, h, w):
+        raise RuntimeError(f"seg_pred must be [b,C,h,w] with C >= 2 and (b,h,w)={(b, h, w)}, got {tuple(seg_pred.shape)}")
+    if tuple(vertex_pred.shape) != (b, 2 * vn, h, w):
+        raise RuntimeError(f"vertex_pred must be [b,2vn,h,w]={(b, 2 * vn, h, w)}, got {tuple(vertex_pred.shape)}")
+    if seg_pred.dtype not in _LOGITS_FLAGS or vertex_pred.dtype not in _VERTEX_FLAGS:
+        raise RuntimeError("seg_pred and vertex_pred must be float32, float16 or bfloat16")
+    flags = int(flags) | _LOGITS_FLAGS[seg_pred.dtype] | _VERTEX_FLAGS[vertex_pred.dtype] | (TARGETS_F_MOTION if use_motion else 0)
+    return dev, b, int(seg_pred.shape[1]), h, w, vn, hc, weight_scale, flags
+
+
+def head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_scale=None, sigma=1.0, use_motion=False, out=None,
+                                workspace=None, flags=0):
+    """``head_metrics_device`` on the targets of ``vertex_targets_device(mask, hcoords, weight_scale, use_motion)`` without making
+    them: the target and the weight of a pixel are computed in registers.  Same ``(losses, counts, status)``, bit for bit; the other
+    parameters are those of ``head_metrics_device``."""
+    lib = load_targets_library()
+    dev, b, nc, h, w, vn, hc, weight_scale, flags = _kp_head_inputs(seg_pred, vertex_pred, mask, hcoords, weight_scale, flags, use_motion)
+    with torch.cuda.device(dev):
+        if out is None:
+            losses = torch.empty((b, 4), dtype=torch.float64, device=dev)
+            counts = torch.empty((b, 3), dtype=torch.int64, device=dev)
+            status = torch.empty((b,), dtype=torch.int32, device=dev)
+        else:
+            losses, counts, status = out
+            for t, dt, shape, name in ((losses, torch.float64, (b, 4), "out[0]"), (counts, torch.int64, (b, 3), "out[1]"),
+                                       (status, torch.int32, (b,), "out[2]")):
+                if not (t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise RuntimeError(f"{name} must be a contiguous {dt} CUDA tensor of shape {shape} on {dev}")
+        if b == 0:
+            return losses, counts, status
+        nbytes = lib.pvnet_head_metrics_kp_workspace_bytes(b, h, w)
+        if workspace is None:
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
+            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
+        _check(lib.pvnet_head_metrics_kp(
+            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
+            C.c_void_p(hc.data_ptr()), _opt_ptr(weight_scale),
+            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
+            b, h, w, vn, float(sigma), flags,
+            C.c_void_p(losses.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(status.data_ptr()),
+            C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_metrics_kp")
+    return losses, counts, status
+
+
+def head_grad_from_keypoints(seg_pred, vertex_pred, mask, hcoords, upstream, weight_scale=None, sigma=1.0, use_motion=False,
+                             need=(True, True), out=None, workspace=None, flags=0):
+    """``head_grad_device`` on the targets of ``vertex_targets_device(mask, hcoords, weight_scale, use_motion)`` without making them.
+    Same ``(grad_seg, grad_vertex, status)``, bit for bit; ``upstream``, ``need``, ``out``, ``workspace`` and ``flags`` as there."""
+    lib = load_targets_library()
+    dev, b, nc, h, w, vn, hc, weight_scale, flags = _kp_head_inputs(seg_pred, vertex_pred, mask, hcoords, weight_scale, flags, use_motion)
+    need = (bool(need[0]), bool(need[1]))
+    if not any(need):
+        raise RuntimeError("need: at least one of the two gradients must be wanted")
+    if not (isinstance(upstream, torch.Tensor) and upstream.is_cuda):
+        raise RuntimeError("upstream must be a CUDA tensor (there is no CPU fallback)")
+    if not (upstream.device == dev and upstream.dtype == torch.float64 and tuple(upstream.shape) == (b, 2) and upstream.is_contiguous()):
+        raise RuntimeError(f"upstream must be a contiguous float64 CUDA tensor of shape {(b, 2)} on {dev}")
+    with torch.cuda.device(dev):
+        grads = []
+        for k, (pred, name) in enumerate(((seg_pred, "out[0]"), (vertex_pred, "out[1]"))):
+            g = None if out is None else out[k]
+            if not need[k]:
+                g = None
+            elif g is None:
+                g = torch.empty_like(pred)
+            elif not (isinstance(g, torch.Tensor) and g.is_cuda and g.device == dev and g.dtype == pred.dtype and g.shape == pred.shape):
+                raise RuntimeError(f"{name} must be a {pred.dtype} CUDA tensor of shape {tuple(pred.shape)} on {dev}")
+            grads.append(g)
+        grad_seg, grad_vertex = grads
+        status = torch.empty((b,), dtype=torch.int32, device=dev)
+        if b == 0:
+            return grad_seg, grad_vertex, status
+        nbytes = lib.pvnet_head_grad_kp_workspace_bytes(b, h, w)
+        if workspace is None:
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
+            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
+        _check(lib.pvnet_head_grad_kp(
+            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
+            C.c_void_p(hc.data_ptr()), _opt_ptr(weight_scale),
+            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
+            b, h, w, vn, float(sigma), flags, C.c_void_p(upstream.data_ptr()),
+            _opt_ptr(grad_seg), None if grad_seg is None else _strides(grad_seg, (0, 1, 2, 3)),
+            _opt_ptr(grad_vertex), None if grad_vertex is None else _strides(grad_vertex, (0, 1, 2, 3)),
+            C.c_void_p(status.data_ptr()), C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_grad_kp")
+    return grad_seg, grad_vertex, status
+
+
 def _upstream(grad_seg_loss, grad_vertex_loss, b, dev):
     """[b,2] float64 from the two incoming gradients of a backward; a missing one is zeros"""
     cols = [torch.zeros((b,), dtype=torch.float64, device=dev) if g is None else g.to(torch.float64) for g in (grad_seg_loss, grad_vertex_loss)]
@@ -256,6 +435,62 @@ class _PackedHeadLossFn(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
+class _KpHeadLossFn(torch.autograd.Function):
+    """``_HeadLossFn`` from key-points: saves the predictions, the mask and the key-points only"""
+
+    @staticmethod
+    def forward(ctx, seg_pred, vertex_pred, mask, hcoords, weight_scale, sigma, use_motion):
+        losses, _, _ = head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_scale, sigma=sigma, use_motion=use_motion)
+        saved = (seg_pred, vertex_pred, mask, hcoords) + (() if weight_scale is None else (weight_scale,))
+        ctx.save_for_backward(*saved)
+        ctx.sigma, ctx.use_motion = sigma, use_motion
+        loss_seg, loss_vertex, precision, recall = _float32_columns(losses)
+        ctx.mark_non_differentiable(precision, recall)
+        return loss_seg, loss_vertex, precision, recall
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_seg, g_vertex, _g_precision, _g_recall):
+        seg_pred, vertex_pred, mask, hcoords = ctx.saved_tensors[:4]
+        weight_scale = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        need = ctx.needs_input_grad[:2]
+        if not any(need):
+            return (None,) * 7
+        upstream = _upstream(g_seg, g_vertex, seg_pred.shape[0], seg_pred.device)
+        grad_seg, grad_vertex, _ = head_grad_from_keypoints(seg_pred, vertex_pred, mask, hcoords, upstream, weight_scale, sigma=ctx.sigma,
+                                                            use_motion=ctx.use_motion, need=need)
+        return grad_seg, grad_vertex, None, None, None, None, None
+
+
+class _KpPackedHeadLossFn(torch.autograd.Function):
+    """``_PackedHeadLossFn`` from key-points"""
+
+    @staticmethod
+    def forward(ctx, head_out, seg_dim, mask, hcoords, weight_scale, sigma, use_motion):
+        losses, _, _ = head_metrics_from_keypoints(head_out[:, :seg_dim], head_out[:, seg_dim:], mask, hcoords, weight_scale, sigma=sigma,
+                                                   use_motion=use_motion)
+        saved = (head_out, mask, hcoords) + (() if weight_scale is None else (weight_scale,))
+        ctx.save_for_backward(*saved)
+        ctx.sigma, ctx.seg_dim, ctx.use_motion = sigma, seg_dim, use_motion
+        loss_seg, loss_vertex, precision, recall = _float32_columns(losses)
+        ctx.mark_non_differentiable(precision, recall)
+        return loss_seg, loss_vertex, precision, recall
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_seg, g_vertex, _g_precision, _g_recall):
+        head_out, mask, hcoords = ctx.saved_tensors[:3]
+        weight_scale = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        k = ctx.seg_dim
+        upstream = _upstream(g_seg, g_vertex, head_out.shape[0], head_out.device)
+        grad = torch.empty_like(head_out)
+        head_grad_from_keypoints(head_out[:, :k], head_out[:, k:], mask, hcoords, upstream, weight_scale, sigma=ctx.sigma,
+                                 use_motion=ctx.use_motion, out=(grad[:, :k], grad[:, k:]))
+        return grad, None, None, None, None, None, None
+
+
 class HeadLoss(torch.nn.Module):
     """The four loss lines of the reference's ``NetWrapper.forward`` (tools/train_linemod.py:87-91) as a differentiable module:
     ``forward(seg_pred, vertex_pred, mask, vertex, vertex_weights) -> (loss_seg, loss_vertex, precision, recall)``, float32 [b] each,
@@ -265,7 +500,15 @@ class HeadLoss(torch.nn.Module):
 
     ``packed(head_out, seg_dim, mask, vertex, vertex_weights)`` takes the network's output before it is sliced into the two
     predictions (lib/networks/model_repository.py:76-78: ``x[:, :seg_dim]``, ``x[:, seg_dim:]``) and writes both gradients into one
-    tensor of its shape -- without the two zero-fill-and-copy passes the backward of torch's slices adds.  Same values."""
+    tensor of its shape -- without the two zero-fill-and-copy passes the backward of torch's slices adds.  Same values.
+
+    ``from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_scale=None, use_motion=False)`` and ``packed_from_keypoints(head_out,
+    seg_dim, mask, hcoords, weight_scale=None, use_motion=False)`` take the loader's ``hcoords [b,vn,3]`` instead of the target field and
+    its weights (``vertex_targets_device`` states what they and ``use_motion`` stand for; the switch is per call here as in every
+    other key-point entry).  Forward and backward compute a pixel's target in registers; the autograd functions save the predictions,
+    the mask and the key-points only.
+    Same values and gradients as the two forms above on ``vertex_targets_device(mask, hcoords, weight_scale)``, bit for bit; no
+    gradient for the mask, the key-points or the scale."""
 
     def __init__(self, sigma=1.0):
         super().__init__()
@@ -279,6 +522,15 @@ class HeadLoss(torch.nn.Module):
         if not (isinstance(head_out, torch.Tensor) and head_out.dim() == 4 and 2 <= seg_dim < head_out.shape[1]):
             raise RuntimeError("head_out must be [b,seg_dim+2vn,h,w] with seg_dim >= 2")
         return _PackedHeadLossFn.apply(head_out, seg_dim, mask, vertex, vertex_weights, self.sigma)
+
+    def from_keypoints(self, seg_pred, vertex_pred, mask, hcoords, weight_scale=None, use_motion=False):
+        return _KpHeadLossFn.apply(seg_pred, vertex_pred, mask, hcoords, weight_scale, self.sigma, bool(use_motion))
+
+    def packed_from_keypoints(self, head_out, seg_dim, mask, hcoords, weight_scale=None, use_motion=False):
+        seg_dim = int(seg_dim)
+        if not (isinstance(head_out, torch.Tensor) and head_out.dim() == 4 and 2 <= seg_dim < head_out.shape[1]):
+            raise RuntimeError("head_out must be [b,seg_dim+2vn,h,w] with seg_dim >= 2")
+        return _KpPackedHeadLossFn.apply(head_out, seg_dim, mask, hcoords, weight_scale, self.sigma, bool(use_motion))
 
 
 class ValStep(object):
@@ -301,14 +553,25 @@ class ValStep(object):
         self.eval_net = PoseEvalWrapper(evaluator.points_3d[class_type], self.K, round_hyp_num=round_hyp_num,
                                         inlier_thresh=inlier_thresh, max_num=max_num)
 
-    def enqueue(self, seg_pred, vertex_pred, mask, vertex, vertex_weights, pose_targets):
+    def _after_head(self, head, seg_pred, vertex_pred, pose_targets):
+        """the chain behind the head's ``(losses, counts, status)``: vote, pose solve, pose metrics"""
         from .evaluation import pose_metrics_device
-        losses, counts, hstatus = head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=self.sigma)
+        losses, counts, hstatus = head
         poses, pstatus, _, _ = self.eval_net(seg_pred, vertex_pred, return_all=True)
         _, Kd = self.eval_net._constants(poses.device)
         errors, passed, mstatus = pose_metrics_device(poses, pose_targets, Kd, self.evaluator.device_models(poses.device),
                                                       class_ids=self.class_type, sym_projection=self.sym_projection)
         return losses, counts, hstatus, poses, pstatus, errors, passed, mstatus
+
+    def enqueue(self, seg_pred, vertex_pred, mask, vertex, vertex_weights, pose_targets):
+        head = head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=self.sigma)
+        return self._after_head(head, seg_pred, vertex_pred, pose_targets)
+
+    def enqueue_from_keypoints(self, seg_pred, vertex_pred, mask, hcoords, pose_targets, weight_scale=None, use_motion=False):
+        """``enqueue`` with the head metrics taken from the loader's ``hcoords`` (``head_metrics_from_keypoints``): the same chain, the
+        same eight tensors, no target field"""
+        head = head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_scale, sigma=self.sigma, use_motion=use_motion)
+        return self._after_head(head, seg_pred, vertex_pred, pose_targets)
 
     def __call__(self, seg_pred, vertex_pred, mask, vertex, vertex_weights, pose_targets):
         losses, _, _, poses, _, errors, passed, _ = self.enqueue(seg_pred, vertex_pred, mask, vertex, vertex_weights, pose_targets)
