@@ -180,56 +180,39 @@ def _load(lib_path: str) -> C.CDLL:
     return lib
 
 
+def _load_side(name: str) -> C.CDLL:
+    """dlopen one of the head's libraries, bind its table, check its ABI version -- once.  Its path, table, version and cache are this
+    module's ``<NAME>_LIB_PATH``, ``<NAME>_PROTOTYPES``, ``<NAME>_ABI_VERSION`` and ``_<name>_lib``, read when called."""
+    g = globals()
+    if g[f"_{name}_lib"] is None:
+        path = g[f"{name.upper()}_LIB_PATH"]
+        if not os.path.exists(path):
+            raise RuntimeError(f"pvnet_amd: HIP library {path} is missing -- build it with "
+                               f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
+        lib = C.CDLL(path)
+        for fn_name, (restype, argtypes) in g[f"{name.upper()}_PROTOTYPES"].items():
+            fn = getattr(lib, fn_name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if getattr(lib, f"pvnet_{name}_abi_version")() != g[f"{name.upper()}_ABI_VERSION"]:
+            raise RuntimeError(f"pvnet_amd: libpvnet_{name}.so ABI version mismatch; rebuild it")
+        g[f"_{name}_lib"] = lib
+    return g[f"_{name}_lib"]
+
+
 def load_head_library() -> C.CDLL:
     """dlopen libpvnet_head.so (the head metrics); loud failure if it has not been built.  There is no CPU fallback."""
-    global _head_lib
-    if _head_lib is None:
-        if not os.path.exists(HEAD_LIB_PATH):
-            raise RuntimeError(f"pvnet_amd: HIP library {HEAD_LIB_PATH} is missing -- build it with "
-                               f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
-        lib = C.CDLL(HEAD_LIB_PATH)
-        for name, (restype, argtypes) in HEAD_PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if lib.pvnet_head_abi_version() != HEAD_ABI_VERSION:
-            raise RuntimeError("pvnet_amd: libpvnet_head.so ABI version mismatch; rebuild it")
-        _head_lib = lib
-    return _head_lib
+    return _load_side("head")
 
 
 def load_train_library() -> C.CDLL:
     """dlopen libpvnet_train.so (the head losses' backward); loud failure if it has not been built.  There is no CPU fallback."""
-    global _train_lib
-    if _train_lib is None:
-        if not os.path.exists(TRAIN_LIB_PATH):
-            raise RuntimeError(f"pvnet_amd: HIP library {TRAIN_LIB_PATH} is missing -- build it with "
-                               f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
-        lib = C.CDLL(TRAIN_LIB_PATH)
-        for name, (restype, argtypes) in TRAIN_PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if lib.pvnet_train_abi_version() != TRAIN_ABI_VERSION:
-            raise RuntimeError("pvnet_amd: libpvnet_train.so ABI version mismatch; rebuild it")
-        _train_lib = lib
-    return _train_lib
+    return _load_side("train")
 
 
 def load_targets_library() -> C.CDLL:
     """dlopen libpvnet_targets.so (targets from key-points, the head fused with them); loud failure if it has not been built.  There is
     no CPU fallback."""
-    global _targets_lib
-    if _targets_lib is None:
-        if not os.path.exists(TARGETS_LIB_PATH):
-            raise RuntimeError(f"pvnet_amd: HIP library {TARGETS_LIB_PATH} is missing -- build it with "
-                               f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
-        lib = C.CDLL(TARGETS_LIB_PATH)
-        for name, (restype, argtypes) in TARGETS_PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if lib.pvnet_targets_abi_version() != TARGETS_ABI_VERSION:
-            raise RuntimeError("pvnet_amd: libpvnet_targets.so ABI version mismatch; rebuild it")
-        _targets_lib = lib
-    return _targets_lib
+    return _load_side("targets")
 
 
 def reload_tuning():

@@ -29,28 +29,28 @@ LIB = os.path.join(HERE, "libpvnet_vote.so")          # release: the knobs are c
 DEV_LIB = os.path.join(HERE, "libpvnet_vote_dev.so")  # -DPVNET_DEV: environment knobs + every kernel variant (knob tests, fuzz, tuning tools)
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
-# the network-head metrics of a validation step (include/pvnet_head.h): one translation unit, a library of its own -- libpvnet_vote.so
-# and its ABI stay as they are
-HEAD_TU = ["head_metrics.hip"]
-HEAD_SRC = [os.path.join(CSRC, f) for f in HEAD_TU]
-HEAD_DEPS = HEAD_SRC + [os.path.join(CSRC, "head_common.h"), os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_head.h"),
-                        os.path.join(ROOT, "include", "pvnet_vote.h")]
-HEAD_LIB = os.path.join(HERE, "libpvnet_head.so")
-# the backward of the head losses of a training step (include/pvnet_train.h): one translation unit, a library of its own again --
-# libpvnet_head.so and its ABI stay as they are
-TRAIN_TU = ["head_grad.hip"]
-TRAIN_SRC = [os.path.join(CSRC, f) for f in TRAIN_TU]
-TRAIN_DEPS = TRAIN_SRC + [os.path.join(CSRC, "head_common.h"), os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"), os.path.join(ROOT, "include", "pvnet_train.h"),
-                          os.path.join(ROOT, "include", "pvnet_head.h"), os.path.join(ROOT, "include", "pvnet_vote.h")]
-TRAIN_LIB = os.path.join(HERE, "libpvnet_train.so")
-# the training targets from the key-points and the head's forward and backward fused with them (include/pvnet_targets.h): one
-# translation unit, a library of its own -- the three above and their ABIs stay as they are
-TARGETS_TU = ["head_targets.hip"]
-TARGETS_SRC = [os.path.join(CSRC, f) for f in TARGETS_TU]
-TARGETS_DEPS = TARGETS_SRC + [os.path.join(CSRC, "head_common.h"), os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "pvnet_rng.h"),
-                              os.path.join(ROOT, "include", "pvnet_targets.h"), os.path.join(ROOT, "include", "pvnet_head.h"),
-                              os.path.join(ROOT, "include", "pvnet_vote.h")]
-TARGETS_LIB = os.path.join(HERE, "libpvnet_targets.so")
+# the head behind the backbone: three libraries of one translation unit each, beside libpvnet_vote.so, whose ABI stays as it is.
+# name -> (translation units, its header under include/ beyond pvnet_head.h, the register checker's option)
+SIDE_LIBRARIES = {
+    "head": (["head_metrics.hip"], "pvnet_head.h", "--head"),          # the head metrics of a validation step
+    "train": (["head_grad.hip"], "pvnet_train.h", "--train"),          # the backward of the head losses of a training step
+    "targets": (["head_targets.hip"], "pvnet_targets.h", "--targets"),  # the targets from key-points, the head fused with them
+}
+
+
+def _side(name):
+    """(sources, what they depend on, the library) of one of SIDE_LIBRARIES"""
+    tu, header, _ = SIDE_LIBRARIES[name]
+    src = [os.path.join(CSRC, f) for f in tu]
+    deps = src + [os.path.join(CSRC, f) for f in ("head_common.h", "vote_common.h", "pvnet_rng.h")] + \
+        [os.path.join(ROOT, "include", f) for f in sorted({header, "pvnet_head.h", "pvnet_vote.h"})]
+    return src, deps, os.path.join(HERE, f"libpvnet_{name}.so")
+
+
+HEAD_TU, TRAIN_TU, TARGETS_TU = (SIDE_LIBRARIES[n][0] for n in ("head", "train", "targets"))
+HEAD_SRC, HEAD_DEPS, HEAD_LIB = _side("head")
+TRAIN_SRC, TRAIN_DEPS, TRAIN_LIB = _side("train")
+TARGETS_SRC, TARGETS_DEPS, TARGETS_LIB = _side("targets")
 # host-side pose refinement (plain C++, g++): include/pvnet_pnp.h
 PNP_SRC = os.path.join(HERE, "csrc", "pvnet_pnp.cpp")
 PNP_DEPS = [PNP_SRC, os.path.join(ROOT, "include", "pvnet_pnp.h")]
@@ -122,58 +122,35 @@ def build_pnp(force: bool = False, verbose: bool = False) -> str:
     return PNP_LIB
 
 
-def build_head(force: bool = False, verbose: bool = False) -> str:
-    """hipcc -> libpvnet_head.so; like the vote library it replaces the previous one only after the register check passed"""
-    if not force and os.path.exists(HEAD_LIB) and all(os.path.getmtime(HEAD_LIB) >= os.path.getmtime(d) for d in HEAD_DEPS):
-        return HEAD_LIB
-    tmp = HEAD_LIB + ".new"
+def build_side(name: str, force: bool = False, verbose: bool = False) -> str:
+    """hipcc -> one of SIDE_LIBRARIES; like the vote library it replaces the previous one only after the register check passed"""
+    src, deps, lib = _side(name)
+    if not force and os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(d) for d in deps):
+        return lib
+    tmp = lib + ".new"
     try:
-        cmd = [hipcc_path()] + flags() + HEAD_SRC + ["-o", tmp]
+        cmd = [hipcc_path()] + flags() + src + ["-o", tmp]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
-        check_resources(("check_kernel_resources.py",), ["--head"])
-        os.replace(tmp, HEAD_LIB)
+        check_resources(("check_kernel_resources.py",), [SIDE_LIBRARIES[name][2]])
+        os.replace(tmp, lib)
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
-    return HEAD_LIB
+    return lib
+
+
+def build_head(force: bool = False, verbose: bool = False) -> str:
+    return build_side("head", force, verbose)
 
 
 def build_train(force: bool = False, verbose: bool = False) -> str:
-    """hipcc -> libpvnet_train.so; like build_head it replaces the previous library only after the register check passed"""
-    if not force and os.path.exists(TRAIN_LIB) and all(os.path.getmtime(TRAIN_LIB) >= os.path.getmtime(d) for d in TRAIN_DEPS):
-        return TRAIN_LIB
-    tmp = TRAIN_LIB + ".new"
-    try:
-        cmd = [hipcc_path()] + flags() + TRAIN_SRC + ["-o", tmp]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        check_resources(("check_kernel_resources.py",), ["--train"])
-        os.replace(tmp, TRAIN_LIB)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-    return TRAIN_LIB
+    return build_side("train", force, verbose)
 
 
 def build_targets(force: bool = False, verbose: bool = False) -> str:
-    """hipcc -> libpvnet_targets.so; like build_head it replaces the previous library only after the register check passed"""
-    if not force and os.path.exists(TARGETS_LIB) and all(os.path.getmtime(TARGETS_LIB) >= os.path.getmtime(d) for d in TARGETS_DEPS):
-        return TARGETS_LIB
-    tmp = TARGETS_LIB + ".new"
-    try:
-        cmd = [hipcc_path()] + flags() + TARGETS_SRC + ["-o", tmp]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        check_resources(("check_kernel_resources.py",), ["--targets"])
-        os.replace(tmp, TARGETS_LIB)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-    return TARGETS_LIB
+    return build_side("targets", force, verbose)
 
 
 # the reference's compiled extension module `ransac_voting` (src/ransac_voting.cpp) on this library: host-only C++ against

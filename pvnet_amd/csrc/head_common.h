@@ -1,13 +1,28 @@
-// head_common.h -- what the translation units of the network head share: head_metrics.hip (libpvnet_head.so), head_grad.hip
-// (libpvnet_train.so) and head_targets.hip (libpvnet_targets.so).  Per-pixel helpers only -- the 16-byte loads and stores, the label
-// rule, torch's arg-max rule, the smooth-L1 term and its gradient, the cross-entropy and the logits' class rule, the order-fixed
-// reductions -- and the bodies of the per-image kernels, which are the same whether the targets come from memory or from key-points.
-// Every function is inlined into the kernel that calls it: the three libraries share source, not symbols.  namespace pvh.
+// head_common.h -- the network head behind the backbone, written once for its three translation units: head_metrics.hip
+// (libpvnet_head.so), head_grad.hip (libpvnet_train.so) and head_targets.hip (libpvnet_targets.so).
+//
+//   per-pixel helpers   the 16-byte loads and stores, the label rule, torch's arg-max rule, the smooth-L1 term and its gradient, the
+//                       cross-entropy and the logits' class rule, the order-fixed reductions
+//   per-image bodies    head_final_image, head_grad_final_image, head_grad_status_image
+//   per-pixel bodies    head_partial8 / head_partial1 (forward, fast and general path), head_grad8 / head_grad1 (backward),
+//                       head_grad_wsum: ALL of the head's arithmetic, templates over a target source -- the policy that says where a
+//                       pixel's label, weight and targets come from.  MemSource (here) loads them; KpSource (head_targets.hip) computes
+//                       them from the mask and the image's key-points.  The fused forms equal the head on materialised targets bit
+//                       for bit because both instantiate the same body; the sources differ in where (t, w) come from and in the
+//                       order they walk the field's planes, nothing else.
+//   arguments           HeadArgs<SRC> for the forward, GradArgs<SRC> for the backward: one layout each, the source a member
+//   host side           the argument checks and their order, the size limits, the workspaces, the arguments' filling, the VT x NT
+//                       dispatch: what the five entry points do before they launch
+//
+// The __global__ kernels stay in their translation units, as thin wrappers with their spare-VGPR constants.  Every function here is
+// inlined into the kernel that calls it: the three libraries share source, not symbols.  namespace pvh.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "pvnet_head.h"
 #include "vote_common.h"   // ld_elem / ld_elem_rt (VT_*), PVNET_SPARE_VGPRS
@@ -389,14 +404,483 @@ __device__ __forceinline__ void head_grad_status_image(const ARGS& A) {
     if (threadIdx.x == 0) A.status[bi] = any ? PVNET_HEAD_S_BAD_LABEL : 0;
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------------
+// ---- the memory source: a pixel's target and weight are loaded ------------------------------------------------------------------
+// A target source is the policy of the four per-pixel bodies below: it says where the label, the weight and the 2 vn targets of a
+// pixel come from, and in which order the field's planes are walked.  This one loads them (head_metrics.hip, head_grad.hip); the
+// other, KpSource of head_targets.hip, computes them from the mask and the image's key-points.  What a source provides:
+//   Lane8 / Pixel, Image     what it keeps of a lane's eight pixels / of one pixel between the two halves, and of an image
+//   pixels8                  opens a lane's eight pixels and gives their labels (the mask is read for them alone here: not at all
+//                            where `labels` is false)
+//   pixel1, label1           the same for one pixel, the label on demand
+//   weights8 / weight1       the weights as float64
+//   planes8 / planes1        the field loop: load(k, p) fetches plane k of the prediction, use(k, p, t) takes it with its targets
+struct MemSource {
+    const float* vt;
+    const float* vw;
+    const void* mask;
+    int64_t ts[4], ws[3], ms[3];
+    int mask_dtype;
+
+    struct Lane8 {};
+    struct Image {};
+    struct Pixel {};
+
+    template <bool NT>
+    __device__ __forceinline__ void pixels8(int bi, int p0, int C, bool labels, int* lab, Lane8&) const {
+        if (labels) load8_labels<NT>(mask_dtype, mask, (int64_t)bi * ms[0] + p0, C, lab);
+    }
+    template <bool NT>
+    __device__ __forceinline__ void weights8(int bi, int p0, const Lane8&, double* wd) const {
+        float wf[HC_PPL];
+        load8<VT_F32, NT>(vw, (int64_t)bi * ws[0] + p0, wf);
+#pragma unroll
+        for (int i = 0; i < HC_PPL; ++i) wd[i] = (double)wf[i];
+    }
+    // prediction, then target, plane by plane (BOTH is the key-point source's: see there)
+    template <bool NT, bool BOTH, typename LOAD, typename USE>
+    __device__ __forceinline__ void planes8(const double*, int bi, int p0, int planes, const Lane8&, LOAD load, USE use) const {
+        const int64_t toff = (int64_t)bi * ts[0] + p0;
+#pragma unroll 2
+        for (int k = 0; k < planes; ++k) {
+            float p[HC_PPL], t[HC_PPL];
+            load(k, p);
+            load8<VT_F32, NT>(vt, toff + (int64_t)k * ts[1], t);
+            use(k, p, t);
+        }
+    }
+
+    __device__ __forceinline__ Image image(int) const { return Image(); }
+    __device__ __forceinline__ Pixel pixel1(int, int, int) const { return Pixel(); }
+    __device__ __forceinline__ int label1(int bi, int x, int y, int C, const Pixel&) const {
+        return label_of(load_label_rt(mask_dtype, mask, (int64_t)bi * ms[0] + (int64_t)y * ms[1] + (int64_t)x * ms[2]), C);
+    }
+    __device__ __forceinline__ double weight1(const Image&, int bi, int x, int y, const Pixel&) const {
+        return (double)vw[(int64_t)bi * ws[0] + (int64_t)y * ws[1] + (int64_t)x * ws[2]];
+    }
+    template <typename USE>
+    __device__ __forceinline__ void planes1(const double*, int bi, int x, int y, int planes, const Pixel&, USE use) const {
+        const int64_t toff = (int64_t)bi * ts[0] + (int64_t)y * ts[2] + (int64_t)x * ts[3];
+        for (int k = 0; k < planes; ++k) use(k, vt[toff + (int64_t)k * ts[1]]);
+    }
+
+    // host: the fast path's shape of what the field's half loads
+    bool targets_linear(int b, int w) const;
+};
+
+// ---- the kernels' arguments: one layout for the forward, one for the backward, the source a member -------------------------------
+template <typename SRC>
+struct HeadInputs {   // what both read.  Pointers, then the source, then the strides: the kernels hold most of this in SGPRs, and with
+                      // the source's pointers away from the others head_grad_general_kernel no longer keeps its scalars in registers
+    const void* seg;
+    const void* vp;
+    SRC T;            // where a pixel's label, weight and targets come from
+    int64_t ss[4], vs[4];
+    int seg_type, vp_type, num_classes, planes;
+    int w, npix, nseg;
+    double s2, hs, inv, half;   // sigma^2, sigma^2 / 2, 1 / sigma^2, 0.5 / sigma^2
+};
+template <typename SRC>
+struct HeadArgs : HeadInputs<SRC> {
+    double* losses;
+    int64_t* counts;
+    int32_t* status;
+    HeadPartial* partial;
+};
+template <typename SRC>
+struct GradArgs : HeadInputs<SRC> {
+    void* gs;   // NULL: the logits' half is skipped
+    void* gv;   // NULL: the field's half is skipped
+    int64_t gss[4], gvs[4];
+    const double* upstream;
+    double* coef;     // [b][2]: u_s / (h w), u_v / D_i
+    double* wpart;    // [b][nseg]: a segment's sum of the weights
+    int32_t* bad;     // [b][nseg]: the segment holds a label outside 0 .. C-1
+    int32_t* status;
+};
+
+// ---- the four per-pixel bodies, each written once for both sources.  grid (segments of HC_SEG pixels, images), HC_T lanes; hcb: the
+//      image's key-points (the key-point source's; NULL otherwise) -- a kernel argument of its own, see head_targets.hip ------------
+// forward, fast path: eight consecutive pixels per lane (npix a multiple of 8: a lane's eight pixels are all inside or all outside)
+template <int VT, int NT, typename SRC>
+__device__ __forceinline__ void head_partial8(const HeadArgs<SRC>& A, const double* __restrict__ hcb) {
+    constexpr bool NT_P = NT == NT_ALL, NT_T = NT != NT_NONE;   // predictions, what the source loads
+    const int bi = blockIdx.y;
+    const int p0 = blockIdx.x * HC_SEG + (int)threadIdx.x * HC_PPL;
+    Acc acc;
+    if (p0 < A.npix) {
+        int lab[HC_PPL];
+        typename SRC::Lane8 L;
+        A.T.template pixels8<NT_T>(bi, p0, A.num_classes, true, lab, L);
+        // ---- class logits: maximum and arg-max in one pass, then sum exp(s - max) in a second (the planes are in cache) -------------
+        const int64_t soff = (int64_t)bi * A.ss[0] + p0;
+        float best[HC_PPL], sl[HC_PPL], s[HC_PPL];
+        bool pfg[HC_PPL];
+        load8_rt<NT_P>(A.seg_type, A.seg, soff, best);
+#pragma unroll
+        for (int i = 0; i < HC_PPL; ++i) {
+            pfg[i] = false;
+            sl[i] = best[i];   // label 0, or a bad label (not used then)
+        }
+        for (int c = 1; c < A.num_classes; ++c) {
+            load8_rt<NT_P>(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1], s);
+#pragma unroll
+            for (int i = 0; i < HC_PPL; ++i) {
+                const bool take = takes_over(best[i], s[i]);
+                best[i] = take ? s[i] : best[i];
+                pfg[i] = take ? true : pfg[i];
+                sl[i] = lab[i] == c ? s[i] : sl[i];
+            }
+        }
+        double sum[HC_PPL];
+#pragma unroll
+        for (int i = 0; i < HC_PPL; ++i) sum[i] = 0.0;
+        for (int c = 0; c < A.num_classes; ++c) {
+            load8_rt<NT_P>(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1], s);
+#pragma unroll
+            for (int i = 0; i < HC_PPL; ++i) sum[i] = sum[i] + exp((double)s[i] - (double)best[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < HC_PPL; ++i) {
+            if (lab[i] >= 0) acc.ce = acc.ce + cross_entropy(sum[i], sl[i], best[i]);
+            acc.packed += confusion(pfg[i], lab[i]);
+        }
+        // ---- the field: 2 vn planes of prediction against their targets under one plane of weights; a plane's prediction is loaded
+        //      when its targets are there -------------------------------------------------------------------------------------------
+        double wd[HC_PPL];
+        A.T.template weights8<NT_T>(bi, p0, L, wd);
+#pragma unroll
+        for (int i = 0; i < HC_PPL; ++i) acc.wsum = acc.wsum + wd[i];
+        const int64_t poff = (int64_t)bi * A.vs[0] + p0;
+        A.T.template planes8<NT_T, false>(
+            hcb, bi, p0, A.planes, L, [&](int k, float* p) { load8<VT, NT_P>(A.vp, poff + (int64_t)k * A.vs[1], p); },
+            [&](int, const float* p, const float* t) {
+#pragma unroll
+                for (int i = 0; i < HC_PPL; ++i) acc.sl1 = acc.sl1 + smooth_l1(A, wd[i], p[i], t[i]);
+            });
+    }
+    if (block_reduce<HC_T>(acc)) store_partial(A, acc);
+}
+
+// forward, general path: the same record from any element strides, any alignment, any h * w -- a pixel per lane and load
+template <typename SRC>
+__device__ __forceinline__ void head_partial1(const HeadArgs<SRC>& A, const double* __restrict__ hcb) {
+    const int bi = blockIdx.y;
+    const typename SRC::Image I = A.T.image(bi);
+    Acc acc;
+    for (int j = 0; j < HC_PPL; ++j) {
+        const int p = blockIdx.x * HC_SEG + j * HC_T + (int)threadIdx.x;
+        if (p >= A.npix) break;
+        const int y = p / A.w, x = p - y * A.w;
+        const typename SRC::Pixel P = A.T.pixel1(bi, x, y);
+        const int lab = A.T.label1(bi, x, y, A.num_classes, P);
+        const int64_t soff = (int64_t)bi * A.ss[0] + (int64_t)y * A.ss[2] + (int64_t)x * A.ss[3];
+        float best = pvd::ld_elem_rt(A.seg_type, A.seg, soff);
+        float sl = best;
+        bool pfg = false;
+        for (int c = 1; c < A.num_classes; ++c) {
+            const float s = pvd::ld_elem_rt(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1]);
+            const bool take = takes_over(best, s);
+            best = take ? s : best;
+            pfg = take ? true : pfg;
+            sl = lab == c ? s : sl;
+        }
+        double sum = 0.0;
+        for (int c = 0; c < A.num_classes; ++c)
+            sum = sum + exp((double)pvd::ld_elem_rt(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1]) - (double)best);
+        if (lab >= 0) acc.ce = acc.ce + cross_entropy(sum, sl, best);
+        acc.packed += confusion(pfg, lab);
+        const double wd = A.T.weight1(I, bi, x, y, P);
+        acc.wsum = acc.wsum + wd;
+        const int64_t poff = (int64_t)bi * A.vs[0] + (int64_t)y * A.vs[2] + (int64_t)x * A.vs[3];
+        A.T.planes1(hcb, bi, x, y, A.planes, P, [&](int k, float t) {
+            acc.sl1 = acc.sl1 + smooth_l1(A, wd, pvd::ld_elem_rt(A.vp_type, A.vp, poff + (int64_t)k * A.vs[1]), t);
+        });
+    }
+    if (block_reduce<HC_T>(acc)) store_partial(A, acc);
+}
+
+// the segment's bad-label flag, for head_grad_status_image (A.gs is uniform over the grid: every lane reaches the barrier)
+template <typename SRC>
+__device__ __forceinline__ void store_bad(const GradArgs<SRC>& A, int bad) {
+    if (!A.gs) return;
+    const int any = __syncthreads_or(bad);
+    if (threadIdx.x == 0) A.bad[(size_t)blockIdx.y * A.nseg + blockIdx.x] = any ? 1 : 0;
+}
+
+// backward, fast path: reads every input byte once, writes every gradient byte once; a half that is not asked for is skipped, its
+// loads included
+template <int VT, int NT, typename SRC>
+__device__ __forceinline__ void head_grad8(const GradArgs<SRC>& A, const double* __restrict__ hcb) {
+    constexpr bool NT_P = NT == NT_ALL, NT_T = NT != NT_NONE, NT_S = NT == NT_ALL;   // predictions, what the source loads, stores
+    const int bi = blockIdx.y;
+    const int p0 = blockIdx.x * HC_SEG + (int)threadIdx.x * HC_PPL;
+    const bool inside = p0 < A.npix;
+    int bad = 0;
+    int lab[HC_PPL];
+    typename SRC::Lane8 L;
+    if (inside) A.T.template pixels8<NT_T>(bi, p0, A.num_classes, A.gs != nullptr, lab, L);
+    if (inside && A.gs) {
+        const double ks = A.coef[2 * bi];
+        // ---- the maximum, then sum exp(s - max) and the share of the classes other than the label's, then the gradients: the planes
+        //      are in cache after the first pass -----------------------------------------------------------------------------------
+        const int64_t soff = (int64_t)bi * A.ss[0] + p0, goff = (int64_t)bi * A.gss[0] + p0;
+        float best[HC_PPL], s[HC_PPL];
+        load8_rt<NT_P>(A.seg_type, A.seg, soff, best);
+        for (int c = 1; c < A.num_classes; ++c) {
+            load8_rt<NT_P>(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1], s);
+#pragma unroll
+            for (int i = 0; i < HC_PPL; ++i) best[i] = takes_over(best[i], s[i]) ? s[i] : best[i];
+        }
+        double sum[HC_PPL], rest[HC_PPL];
+#pragma unroll
+        for (int i = 0; i < HC_PPL; ++i) {
+            sum[i] = 0.0;
+            rest[i] = 0.0;
+            bad |= lab[i] < 0;
+        }
+        for (int c = 0; c < A.num_classes; ++c) {
+            load8_rt<NT_P>(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1], s);
+#pragma unroll
+            for (int i = 0; i < HC_PPL; ++i) {
+                const double e = exp((double)s[i] - (double)best[i]);
+                sum[i] = sum[i] + e;
+                rest[i] = rest[i] + (lab[i] == c ? 0.0 : e);
+            }
+        }
+        for (int c = 0; c < A.num_classes; ++c) {
+            load8_rt<NT_P>(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1], s);
+            double g[HC_PPL];
+#pragma unroll
+            for (int i = 0; i < HC_PPL; ++i)
+                g[i] = logit_grad(lab[i], c, exp((double)s[i] - (double)best[i]), sum[i], rest[i], ks);
+            store8_rt<NT_S>(A.seg_type, A.gs, goff + (int64_t)c * A.gss[1], g);
+        }
+    }
+    if (inside && A.gv) {
+        // ---- the field: 2 vn planes of prediction against their targets under one plane of weights; the predictions are in flight
+        //      while the targets are made --------------------------------------------------------------------------------------------
+        const double kv = A.coef[2 * bi + 1];
+        double wd[HC_PPL];
+        A.T.template weights8<NT_T>(bi, p0, L, wd);
+        const int64_t poff = (int64_t)bi * A.vs[0] + p0, goff = (int64_t)bi * A.gvs[0] + p0;
+        A.T.template planes8<NT_T, true>(
+            hcb, bi, p0, A.planes, L, [&](int k, float* p) { load8<VT, NT_P>(A.vp, poff + (int64_t)k * A.vs[1], p); },
+            [&](int k, const float* p, const float* t) {
+                double g[HC_PPL];
+#pragma unroll
+                for (int i = 0; i < HC_PPL; ++i) g[i] = field_grad(A, wd[i], p[i], t[i], kv);
+                store8<VT, NT_S>(A.gv, goff + (int64_t)k * A.gvs[1], g);
+            });
+    }
+    store_bad(A, bad);
+}
+
+// backward, general path: a pixel per lane and access
+template <typename SRC>
+__device__ __forceinline__ void head_grad1(const GradArgs<SRC>& A, const double* __restrict__ hcb) {
+    const int bi = blockIdx.y;
+    const typename SRC::Image I = A.T.image(bi);
+    int bad = 0;
+    for (int j = 0; j < HC_PPL; ++j) {
+        const int p = blockIdx.x * HC_SEG + j * HC_T + (int)threadIdx.x;
+        if (p >= A.npix) break;
+        const int y = p / A.w, x = p - y * A.w;
+        const typename SRC::Pixel P = A.T.pixel1(bi, x, y);
+        if (A.gs) {
+            const double ks = A.coef[2 * bi];
+            const int lab = A.T.label1(bi, x, y, A.num_classes, P);
+            bad |= lab < 0;
+            const int64_t soff = (int64_t)bi * A.ss[0] + (int64_t)y * A.ss[2] + (int64_t)x * A.ss[3];
+            const int64_t goff = (int64_t)bi * A.gss[0] + (int64_t)y * A.gss[2] + (int64_t)x * A.gss[3];
+            float best = pvd::ld_elem_rt(A.seg_type, A.seg, soff);
+            for (int c = 1; c < A.num_classes; ++c) {
+                const float s = pvd::ld_elem_rt(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1]);
+                best = takes_over(best, s) ? s : best;
+            }
+            double sum = 0.0, rest = 0.0;
+            for (int c = 0; c < A.num_classes; ++c) {
+                const double e = exp((double)pvd::ld_elem_rt(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1]) - (double)best);
+                sum = sum + e;
+                rest = rest + (lab == c ? 0.0 : e);
+            }
+            for (int c = 0; c < A.num_classes; ++c) {
+                const double e = exp((double)pvd::ld_elem_rt(A.seg_type, A.seg, soff + (int64_t)c * A.ss[1]) - (double)best);
+                store_elem_rt(A.seg_type, A.gs, goff + (int64_t)c * A.gss[1], logit_grad(lab, c, e, sum, rest, ks));
+            }
+        }
+        if (A.gv) {
+            const double kv = A.coef[2 * bi + 1];
+            const double wd = A.T.weight1(I, bi, x, y, P);
+            const int64_t poff = (int64_t)bi * A.vs[0] + (int64_t)y * A.vs[2] + (int64_t)x * A.vs[3];
+            const int64_t goff = (int64_t)bi * A.gvs[0] + (int64_t)y * A.gvs[2] + (int64_t)x * A.gvs[3];
+            A.T.planes1(hcb, bi, x, y, A.planes, P, [&](int k, float t) {
+                store_elem_rt(A.vp_type, A.gv, goff + (int64_t)k * A.gvs[1],
+                              field_grad(A, wd, pvd::ld_elem_rt(A.vp_type, A.vp, poff + (int64_t)k * A.vs[1]), t, kv));
+            });
+        }
+    }
+    store_bad(A, bad);
+}
+
+// the segment's sum of the weights, in the forward's order (so D_i = 2vn sum w + 1e-3 is the forward's denominator bit for bit).  What
+// it reads is loaded plainly: the gradient kernel reads it again.
+template <bool FAST, typename SRC>
+__device__ __forceinline__ void head_grad_wsum(const GradArgs<SRC>& A) {
+    const int bi = blockIdx.y;
+    double acc = 0.0;
+    if (FAST) {
+        const int p0 = blockIdx.x * HC_SEG + (int)threadIdx.x * HC_PPL;
+        if (p0 < A.npix) {   // (npix is a multiple of 8 here: the lane's eight pixels are all inside)
+            int lab[HC_PPL];
+            typename SRC::Lane8 L;
+            double wd[HC_PPL];
+            A.T.template pixels8<false>(bi, p0, A.num_classes, false, lab, L);
+            A.T.template weights8<false>(bi, p0, L, wd);
+#pragma unroll
+            for (int i = 0; i < HC_PPL; ++i) acc = acc + wd[i];
+        }
+    } else {
+        const typename SRC::Image I = A.T.image(bi);
+        for (int j = 0; j < HC_PPL; ++j) {
+            const int p = blockIdx.x * HC_SEG + j * HC_T + (int)threadIdx.x;
+            if (p >= A.npix) break;
+            const int y = p / A.w, x = p - y * A.w;
+            acc = acc + A.T.weight1(I, bi, x, y, A.T.pixel1(bi, x, y));
+        }
+    }
+    acc = block_sum<HC_T>(acc);
+    if (threadIdx.x == 0) A.wpart[(size_t)bi * A.nseg + blockIdx.x] = acc;
+}
+
+// ---- host side: what the five entry points of the three libraries do before they launch ------------------------------------------
 // a tensor's planes can be accessed eight pixels at a time: pixels contiguous, base and every plane / image start on 16 bytes
 inline bool plane_linear(const void* base, int b, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int w) {
     return sw == 1 && sh == w && (b == 1 || sb % 8 == 0) && sc % 8 == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
 }
+inline bool linear4(const void* base, int b, const int64_t* s, int w) { return plane_linear(base, b, s[0], s[1], s[2], s[3], w); }
+inline bool linear3(const void* base, int b, const int64_t* s, int w) { return plane_linear(base, b, s[0], 0, s[1], s[2], w); }
+inline bool MemSource::targets_linear(int b, int w) const { return linear4(vt, b, ts, w) && linear3(vw, b, ws, w); }
 
 inline int type_of(uint32_t flags, uint32_t f16, uint32_t bf16) { return (flags & f16) ? VT_F16 : (flags & bf16) ? VT_BF16 : VT_F32; }
 
 inline size_t round256(size_t n) { return (n + 255) / 256 * 256; }
+
+constexpr uint32_t HEAD_FLAGS = PVNET_HEAD_F_VERTEX_F16 | PVNET_HEAD_F_VERTEX_BF16 | PVNET_HEAD_F_LOGITS_F16 | PVNET_HEAD_F_LOGITS_BF16 |
+                                PVNET_HEAD_F_NT_NONE | PVNET_HEAD_F_NT_ALL;
+
+// the argument checks, in the order every entry point makes them: 0 or the code to return.  pointers: none of the call's required
+// pointers is NULL; known: the flags the call takes.  (The targets alone have no classes and no sigma: they pass 2 and 1.)
+inline int check_args(bool pointers, int mask_dtype, int b, int h, int w, int vn, int num_classes, double sigma, uint32_t flags,
+                      uint32_t known) {
+    if (!pointers) return PVNET_E_BADARG;
+    if (b < 0 || h <= 0 || w <= 0 || vn <= 0 || num_classes < 2 || !(sigma > 0.0) || !isfinite(sigma) || (flags & ~known) != 0)
+        return PVNET_E_BADARG;
+    if (((flags & PVNET_HEAD_F_VERTEX_F16) && (flags & PVNET_HEAD_F_VERTEX_BF16)) ||
+        ((flags & PVNET_HEAD_F_LOGITS_F16) && (flags & PVNET_HEAD_F_LOGITS_BF16)) ||
+        ((flags & PVNET_HEAD_F_NT_NONE) && (flags & PVNET_HEAD_F_NT_ALL)))
+        return PVNET_E_BADARG;
+    if (mask_dtype == PVNET_MASK_I16 || mask_dtype == PVNET_MASK_F32 || mask_dtype == PVNET_MASK_LOGITS_F32) return PVNET_E_UNSUPPORTED;
+    if (mask_dtype != PVNET_MASK_U8 && mask_dtype != PVNET_MASK_I32 && mask_dtype != PVNET_MASK_I64) return PVNET_E_BADARG;
+    if (b > HC_MAX_B || (long long)h * w > HC_MAX_PIXELS || vn > (1 << 20)) return PVNET_E_UNSUPPORTED;
+    return 0;
+}
+
+// the workspaces: the forward's records; the backward's coefficients, weight sums and bad-label flags.  0 for sizes out of range.
+inline size_t segments(size_t npix) { return (npix + HC_SEG - 1) / HC_SEG; }
+inline bool sizes_ok(int b, int h, int w) { return b > 0 && h > 0 && w > 0 && b <= HC_MAX_B && (long long)h * w <= HC_MAX_PIXELS; }
+inline size_t head_workspace_bytes(int b, int h, int w) {
+    return sizes_ok(b, h, w) ? round256((size_t)b * segments((size_t)h * w) * sizeof(HeadPartial)) : 0;
+}
+inline size_t grad_workspace_bytes(int b, int h, int w) {
+    if (!sizes_ok(b, h, w)) return 0;
+    const size_t nseg = segments((size_t)h * w);
+    return round256((size_t)b * 2 * sizeof(double)) + round256((size_t)b * nseg * sizeof(double)) + round256((size_t)b * nseg * sizeof(int32_t));
+}
+inline int check_workspace(const void* workspace, size_t have, size_t need) {
+    if (!workspace || have < need) return PVNET_E_WORKSPACE;
+    return (reinterpret_cast<uintptr_t>(workspace) & 7u) != 0 ? PVNET_E_BADARG : 0;
+}
+
+// what the forward's and the backward's arguments share, from a checked call (A.T is the caller's)
+template <typename SRC>
+void fill_inputs(HeadInputs<SRC>& A, const void* seg_pred, const int64_t* seg_strides, int num_classes, const void* vertex_pred,
+                 const int64_t* vp_strides, int h, int w, int vn, double sigma, uint32_t flags) {
+    A.seg = seg_pred;
+    A.vp = vertex_pred;
+    for (int i = 0; i < 4; ++i) {
+        A.ss[i] = seg_strides[i];
+        A.vs[i] = vp_strides[i];
+    }
+    A.seg_type = type_of(flags, PVNET_HEAD_F_LOGITS_F16, PVNET_HEAD_F_LOGITS_BF16);
+    A.vp_type = type_of(flags, PVNET_HEAD_F_VERTEX_F16, PVNET_HEAD_F_VERTEX_BF16);
+    A.num_classes = num_classes;
+    A.planes = 2 * vn;
+    A.w = w;
+    A.npix = h * w;
+    A.nseg = (int)segments((size_t)A.npix);
+    A.s2 = sigma * sigma;
+    A.hs = A.s2 / 2.0;
+    A.inv = 1.0 / A.s2;
+    A.half = 0.5 / A.s2;
+}
+inline MemSource make_mem_source(const float* vertex_target, const int64_t* vt_strides, const float* vertex_weights, const int64_t* w_strides,
+                                 const void* mask, int mask_dtype, const int64_t* mask_strides) {
+    MemSource T;
+    T.vt = vertex_target;
+    T.vw = vertex_weights;
+    T.mask = mask;
+    for (int i = 0; i < 4; ++i) T.ts[i] = vt_strides[i];
+    for (int i = 0; i < 3; ++i) {
+        T.ws[i] = w_strides[i];
+        T.ms[i] = mask_strides[i];
+    }
+    T.mask_dtype = mask_dtype;
+    return T;
+}
+template <typename SRC>
+void fill_head(HeadArgs<SRC>& A, double* losses, int64_t* counts, int32_t* status, void* workspace) {
+    A.losses = losses;
+    A.counts = counts;
+    A.status = status;
+    A.partial = static_cast<HeadPartial*>(workspace);
+}
+template <typename SRC>
+void fill_grad(GradArgs<SRC>& A, int b, const double* upstream, void* grad_seg, const int64_t* gs_strides, void* grad_vertex,
+               const int64_t* gv_strides, int32_t* status, void* workspace) {
+    A.gs = grad_seg;
+    A.gv = grad_vertex;
+    for (int i = 0; i < 4; ++i) {
+        A.gss[i] = grad_seg ? gs_strides[i] : 0;
+        A.gvs[i] = grad_vertex ? gv_strides[i] : 0;
+    }
+    A.upstream = upstream;
+    char* ws = static_cast<char*>(workspace);
+    A.coef = reinterpret_cast<double*>(ws);
+    ws += round256((size_t)b * 2 * sizeof(double));
+    A.wpart = reinterpret_cast<double*>(ws);
+    ws += round256((size_t)b * A.nseg * sizeof(double));
+    A.bad = reinterpret_cast<int32_t*>(ws);
+    A.status = status;
+}
+
+// the fast kernels' dispatch over the field's element type and the non-temporal policy: launch(VT, NT) gets two integral constants
+template <int V>
+using ic = std::integral_constant<int, V>;
+template <typename F>
+void launch_fast(int vt, uint32_t flags, F launch) {
+    const auto with = [&](auto v) {
+        if (flags & PVNET_HEAD_F_NT_NONE) launch(v, ic<NT_NONE>());
+        else if (flags & PVNET_HEAD_F_NT_ALL) launch(v, ic<NT_ALL>());
+        else launch(v, ic<NT_TARGETS>());
+    };
+    if (vt == VT_F16) with(ic<VT_F16>());
+    else if (vt == VT_BF16) with(ic<VT_BF16>());
+    else with(ic<VT_F32>());
+}
+
+inline int launched() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
 
 }  // namespace pvh

@@ -70,6 +70,59 @@ def _head_inputs(seg_pred, vertex_pred, mask, vertex, vertex_weights, flags):
     return dev, b, nc, h, w, planes, flags
 
 
+def _metric_outputs(out, b, dev):
+    """``(losses [b,4] float64, counts [b,3] int64, status [b] int32)``: new, or the caller's ``out`` checked"""
+    if out is None:
+        return (torch.empty((b, 4), dtype=torch.float64, device=dev), torch.empty((b, 3), dtype=torch.int64, device=dev),
+                torch.empty((b,), dtype=torch.int32, device=dev))
+    losses, counts, status = out
+    for t, dt, shape, name in ((losses, torch.float64, (b, 4), "out[0]"), (counts, torch.int64, (b, 3), "out[1]"),
+                               (status, torch.int32, (b,), "out[2]")):
+        if not (t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError(f"{name} must be a contiguous {dt} CUDA tensor of shape {shape} on {dev}")
+    return losses, counts, status
+
+
+def _workspace(workspace, nbytes, dev):
+    """-> (pointer, bytes) of the caller's workspace, or of a new one of ``nbytes``"""
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
+        raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
+    return C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size()
+
+
+def _grad_outputs(seg_pred, vertex_pred, upstream, need, out, b, dev):
+    """the checks of ``upstream``, ``need`` and ``out`` -> (grad_seg, grad_vertex, status): new tensors or the caller's, None for a
+    half that is not wanted"""
+    need = (bool(need[0]), bool(need[1]))
+    if not any(need):
+        raise RuntimeError("need: at least one of the two gradients must be wanted")
+    if not (isinstance(upstream, torch.Tensor) and upstream.is_cuda):
+        raise RuntimeError("upstream must be a CUDA tensor (there is no CPU fallback)")
+    if not (upstream.device == dev and upstream.dtype == torch.float64 and tuple(upstream.shape) == (b, 2) and upstream.is_contiguous()):
+        raise RuntimeError(f"upstream must be a contiguous float64 CUDA tensor of shape {(b, 2)} on {dev}")
+    grads = []
+    for k, (pred, name) in enumerate(((seg_pred, "out[0]"), (vertex_pred, "out[1]"))):
+        g = None if out is None else out[k]
+        if not need[k]:
+            g = None
+        elif g is None:
+            g = torch.empty_like(pred)
+        elif not (isinstance(g, torch.Tensor) and g.is_cuda and g.device == dev and g.dtype == pred.dtype and g.shape == pred.shape):
+            raise RuntimeError(f"{name} must be a {pred.dtype} CUDA tensor of shape {tuple(pred.shape)} on {dev}")
+        grads.append(g)
+    return grads[0], grads[1], torch.empty((b,), dtype=torch.int32, device=dev)
+
+
+def _opt_ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _opt_strides(t, dims):
+    return None if t is None else _strides(t, dims)
+
+
 def head_metrics_workspace_bytes(b, h, w):
     """the workspace ``head_metrics_device`` needs for b images of h x w pixels (bytes)"""
     return int(load_head_library().pvnet_head_metrics_workspace_bytes(int(b), int(h), int(w)))
@@ -92,23 +145,9 @@ def head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sig
     lib = load_head_library()
     dev, b, nc, h, w, planes, flags = _head_inputs(seg_pred, vertex_pred, mask, vertex, vertex_weights, flags)
     with torch.cuda.device(dev):
-        if out is None:
-            losses = torch.empty((b, 4), dtype=torch.float64, device=dev)
-            counts = torch.empty((b, 3), dtype=torch.int64, device=dev)
-            status = torch.empty((b,), dtype=torch.int32, device=dev)
-        else:
-            losses, counts, status = out
-            for t, dt, shape, name in ((losses, torch.float64, (b, 4), "out[0]"), (counts, torch.int64, (b, 3), "out[1]"),
-                                       (status, torch.int32, (b,), "out[2]")):
-                if not (t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
-                    raise RuntimeError(f"{name} must be a contiguous {dt} CUDA tensor of shape {shape} on {dev}")
+        losses, counts, status = _metric_outputs(out, b, dev)
         if b == 0:
             return losses, counts, status
-        nbytes = lib.pvnet_head_metrics_workspace_bytes(b, h, w)
-        if workspace is None:
-            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
-            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
         _check(lib.pvnet_head_metrics(
             C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
             C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
@@ -117,7 +156,7 @@ def head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sig
             C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
             b, h, w, planes // 2, float(sigma), flags,
             C.c_void_p(losses.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(status.data_ptr()),
-            C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            *_workspace(workspace, lib.pvnet_head_metrics_workspace_bytes(b, h, w), dev),
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_metrics")
     return losses, counts, status
 
@@ -165,33 +204,10 @@ def head_grad_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, upstre
              pixel's C gradients are NaN; 0 when grad_seg is not wanted -- the mask is not read then)."""
     lib = load_train_library()
     dev, b, nc, h, w, planes, flags = _head_inputs(seg_pred, vertex_pred, mask, vertex, vertex_weights, flags)
-    need = (bool(need[0]), bool(need[1]))
-    if not any(need):
-        raise RuntimeError("need: at least one of the two gradients must be wanted")
-    if not (isinstance(upstream, torch.Tensor) and upstream.is_cuda):
-        raise RuntimeError("upstream must be a CUDA tensor (there is no CPU fallback)")
-    if not (upstream.device == dev and upstream.dtype == torch.float64 and tuple(upstream.shape) == (b, 2) and upstream.is_contiguous()):
-        raise RuntimeError(f"upstream must be a contiguous float64 CUDA tensor of shape {(b, 2)} on {dev}")
     with torch.cuda.device(dev):
-        grads = []
-        for k, (pred, name) in enumerate(((seg_pred, "out[0]"), (vertex_pred, "out[1]"))):
-            g = None if out is None else out[k]
-            if not need[k]:
-                g = None
-            elif g is None:
-                g = torch.empty_like(pred)
-            elif not (isinstance(g, torch.Tensor) and g.is_cuda and g.device == dev and g.dtype == pred.dtype and g.shape == pred.shape):
-                raise RuntimeError(f"{name} must be a {pred.dtype} CUDA tensor of shape {tuple(pred.shape)} on {dev}")
-            grads.append(g)
-        grad_seg, grad_vertex = grads
-        status = torch.empty((b,), dtype=torch.int32, device=dev)
+        grad_seg, grad_vertex, status = _grad_outputs(seg_pred, vertex_pred, upstream, need, out, b, dev)
         if b == 0:
             return grad_seg, grad_vertex, status
-        nbytes = lib.pvnet_head_grad_workspace_bytes(b, h, w)
-        if workspace is None:
-            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
-            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
         _check(lib.pvnet_head_grad(
             C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
             C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
@@ -199,10 +215,8 @@ def head_grad_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, upstre
             C.c_void_p(vertex_weights.data_ptr()), _strides(vertex_weights, (0, 2, 3)),
             C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
             b, h, w, planes // 2, float(sigma), flags, C.c_void_p(upstream.data_ptr()),
-            None if grad_seg is None else C.c_void_p(grad_seg.data_ptr()), None if grad_seg is None else _strides(grad_seg, (0, 1, 2, 3)),
-            None if grad_vertex is None else C.c_void_p(grad_vertex.data_ptr()),
-            None if grad_vertex is None else _strides(grad_vertex, (0, 1, 2, 3)),
-            C.c_void_p(status.data_ptr()), C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            _opt_ptr(grad_seg), _opt_strides(grad_seg, (0, 1, 2, 3)), _opt_ptr(grad_vertex), _opt_strides(grad_vertex, (0, 1, 2, 3)),
+            C.c_void_p(status.data_ptr()), *_workspace(workspace, lib.pvnet_head_grad_workspace_bytes(b, h, w), dev),
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_grad")
     return grad_seg, grad_vertex, status
 
@@ -230,10 +244,6 @@ def _keypoint_inputs(mask, hcoords, weight_scale):
             raise RuntimeError(f"weight_scale must be a floating-point tensor of shape {(b,)} on {dev}")
         weight_scale = weight_scale.to(torch.float32).contiguous()
     return dev, b, h, w, int(hc.shape[1]), hc, weight_scale
-
-
-def _opt_ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def vertex_targets_device(mask, hcoords, weight_scale=None, use_motion=False, out=None):
@@ -268,8 +278,7 @@ def vertex_targets_device(mask, hcoords, weight_scale=None, use_motion=False, ou
         _check(lib.pvnet_vertex_targets(
             C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)), C.c_void_p(hc.data_ptr()),
             _opt_ptr(weight_scale), b, h, w, vn, TARGETS_F_MOTION if use_motion else 0,
-            _opt_ptr(vertex), None if vertex is None else _strides(vertex, (0, 1, 2, 3)),
-            _opt_ptr(weights), None if weights is None else _strides(weights, (0, 2, 3)),
+            _opt_ptr(vertex), _opt_strides(vertex, (0, 1, 2, 3)), _opt_ptr(weights), _opt_strides(weights, (0, 2, 3)),
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_vertex_targets")
     return vertex, weights
 
@@ -300,23 +309,9 @@ def head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_sca
     lib = load_targets_library()
     dev, b, nc, h, w, vn, hc, weight_scale, flags = _kp_head_inputs(seg_pred, vertex_pred, mask, hcoords, weight_scale, flags, use_motion)
     with torch.cuda.device(dev):
-        if out is None:
-            losses = torch.empty((b, 4), dtype=torch.float64, device=dev)
-            counts = torch.empty((b, 3), dtype=torch.int64, device=dev)
-            status = torch.empty((b,), dtype=torch.int32, device=dev)
-        else:
-            losses, counts, status = out
-            for t, dt, shape, name in ((losses, torch.float64, (b, 4), "out[0]"), (counts, torch.int64, (b, 3), "out[1]"),
-                                       (status, torch.int32, (b,), "out[2]")):
-                if not (t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
-                    raise RuntimeError(f"{name} must be a contiguous {dt} CUDA tensor of shape {shape} on {dev}")
+        losses, counts, status = _metric_outputs(out, b, dev)
         if b == 0:
             return losses, counts, status
-        nbytes = lib.pvnet_head_metrics_kp_workspace_bytes(b, h, w)
-        if workspace is None:
-            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
-            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
         _check(lib.pvnet_head_metrics_kp(
             C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
             C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
@@ -324,7 +319,7 @@ def head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_sca
             C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
             b, h, w, vn, float(sigma), flags,
             C.c_void_p(losses.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(status.data_ptr()),
-            C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            *_workspace(workspace, lib.pvnet_head_metrics_kp_workspace_bytes(b, h, w), dev),
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_metrics_kp")
     return losses, counts, status
 
@@ -335,42 +330,18 @@ def head_grad_from_keypoints(seg_pred, vertex_pred, mask, hcoords, upstream, wei
     Same ``(grad_seg, grad_vertex, status)``, bit for bit; ``upstream``, ``need``, ``out``, ``workspace`` and ``flags`` as there."""
     lib = load_targets_library()
     dev, b, nc, h, w, vn, hc, weight_scale, flags = _kp_head_inputs(seg_pred, vertex_pred, mask, hcoords, weight_scale, flags, use_motion)
-    need = (bool(need[0]), bool(need[1]))
-    if not any(need):
-        raise RuntimeError("need: at least one of the two gradients must be wanted")
-    if not (isinstance(upstream, torch.Tensor) and upstream.is_cuda):
-        raise RuntimeError("upstream must be a CUDA tensor (there is no CPU fallback)")
-    if not (upstream.device == dev and upstream.dtype == torch.float64 and tuple(upstream.shape) == (b, 2) and upstream.is_contiguous()):
-        raise RuntimeError(f"upstream must be a contiguous float64 CUDA tensor of shape {(b, 2)} on {dev}")
     with torch.cuda.device(dev):
-        grads = []
-        for k, (pred, name) in enumerate(((seg_pred, "out[0]"), (vertex_pred, "out[1]"))):
-            g = None if out is None else out[k]
-            if not need[k]:
-                g = None
-            elif g is None:
-                g = torch.empty_like(pred)
-            elif not (isinstance(g, torch.Tensor) and g.is_cuda and g.device == dev and g.dtype == pred.dtype and g.shape == pred.shape):
-                raise RuntimeError(f"{name} must be a {pred.dtype} CUDA tensor of shape {tuple(pred.shape)} on {dev}")
-            grads.append(g)
-        grad_seg, grad_vertex = grads
-        status = torch.empty((b,), dtype=torch.int32, device=dev)
+        grad_seg, grad_vertex, status = _grad_outputs(seg_pred, vertex_pred, upstream, need, out, b, dev)
         if b == 0:
             return grad_seg, grad_vertex, status
-        nbytes = lib.pvnet_head_grad_kp_workspace_bytes(b, h, w)
-        if workspace is None:
-            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
-            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
         _check(lib.pvnet_head_grad_kp(
             C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
             C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
             C.c_void_p(hc.data_ptr()), _opt_ptr(weight_scale),
             C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
             b, h, w, vn, float(sigma), flags, C.c_void_p(upstream.data_ptr()),
-            _opt_ptr(grad_seg), None if grad_seg is None else _strides(grad_seg, (0, 1, 2, 3)),
-            _opt_ptr(grad_vertex), None if grad_vertex is None else _strides(grad_vertex, (0, 1, 2, 3)),
-            C.c_void_p(status.data_ptr()), C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
+            _opt_ptr(grad_seg), _opt_strides(grad_seg, (0, 1, 2, 3)), _opt_ptr(grad_vertex), _opt_strides(grad_vertex, (0, 1, 2, 3)),
+            C.c_void_p(status.data_ptr()), *_workspace(workspace, lib.pvnet_head_grad_kp_workspace_bytes(b, h, w), dev),
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_grad_kp")
     return grad_seg, grad_vertex, status
 
@@ -381,114 +352,54 @@ def _upstream(grad_seg_loss, grad_vertex_loss, b, dev):
     return torch.stack(cols, 1)
 
 
-def _float32_columns(losses):
-    return tuple(losses.to(torch.float32).unbind(1))
-
-
 class _HeadLossFn(torch.autograd.Function):
-    """forward: ``head_metrics_device``; backward: ONE ``head_grad_device`` on the saved inputs"""
+    """The four forms of ``HeadLoss``.  ``apply(pred, pred2, seg_dim, mask, source, source2, sigma, use_motion, keypoints)``:
+
+    * the predictions are ``(pred, pred2) = (seg_pred, vertex_pred)`` with ``seg_dim`` None, or the two channel slices of the ONE tensor
+      ``pred`` at ``seg_dim`` (``pred2`` None): the backward then writes both halves into one gradient tensor of its shape;
+    * the targets are ``(source, source2) = (vertex, vertex_weights)``, or with ``keypoints`` ``(hcoords, weight_scale or None)``.
+
+    forward: ``head_metrics_device`` / ``head_metrics_from_keypoints``; backward: ONE ``head_grad_device`` /
+    ``head_grad_from_keypoints`` on the saved inputs -- with key-points those are the predictions, the mask and the key-points only."""
 
     @staticmethod
-    def forward(ctx, seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma):
-        losses, _, _ = head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sigma=sigma)
-        ctx.save_for_backward(seg_pred, vertex_pred, mask, vertex, vertex_weights)
-        ctx.sigma = sigma
-        loss_seg, loss_vertex, precision, recall = _float32_columns(losses)
+    def _predictions(pred, pred2, seg_dim):
+        return (pred, pred2) if seg_dim is None else (pred[:, :seg_dim], pred[:, seg_dim:])
+
+    @staticmethod
+    def forward(ctx, pred, pred2, seg_dim, mask, source, source2, sigma, use_motion, keypoints):
+        seg_pred, vertex_pred = _HeadLossFn._predictions(pred, pred2, seg_dim)
+        if keypoints:
+            losses, _, _ = head_metrics_from_keypoints(seg_pred, vertex_pred, mask, source, source2, sigma=sigma, use_motion=use_motion)
+        else:
+            losses, _, _ = head_metrics_device(seg_pred, vertex_pred, mask, source, source2, sigma=sigma)
+        ctx.present = tuple(t is not None for t in (pred, pred2, mask, source, source2))   # pred2 / weight_scale may be None
+        ctx.save_for_backward(*(t for t in (pred, pred2, mask, source, source2) if t is not None))
+        ctx.seg_dim, ctx.sigma, ctx.use_motion, ctx.keypoints = seg_dim, sigma, use_motion, keypoints
+        loss_seg, loss_vertex, precision, recall = losses.to(torch.float32).unbind(1)
         ctx.mark_non_differentiable(precision, recall)
         return loss_seg, loss_vertex, precision, recall
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_seg, g_vertex, _g_precision, _g_recall):
-        seg_pred, vertex_pred, mask, vertex, vertex_weights = ctx.saved_tensors
-        need = ctx.needs_input_grad[:2]
-        if not any(need):
-            return (None,) * 6
-        upstream = _upstream(g_seg, g_vertex, seg_pred.shape[0], seg_pred.device)
-        grad_seg, grad_vertex, _ = head_grad_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, upstream, sigma=ctx.sigma, need=need)
-        return grad_seg, grad_vertex, None, None, None, None
-
-
-class _PackedHeadLossFn(torch.autograd.Function):
-    """the same on the two channel slices of ONE tensor; backward writes both halves into one gradient tensor of its shape"""
-
-    @staticmethod
-    def forward(ctx, head_out, seg_dim, mask, vertex, vertex_weights, sigma):
-        losses, _, _ = head_metrics_device(head_out[:, :seg_dim], head_out[:, seg_dim:], mask, vertex, vertex_weights, sigma=sigma)
-        ctx.save_for_backward(head_out, mask, vertex, vertex_weights)
-        ctx.sigma, ctx.seg_dim = sigma, seg_dim
-        loss_seg, loss_vertex, precision, recall = _float32_columns(losses)
-        ctx.mark_non_differentiable(precision, recall)
-        return loss_seg, loss_vertex, precision, recall
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_seg, g_vertex, _g_precision, _g_recall):
-        head_out, mask, vertex, vertex_weights = ctx.saved_tensors
-        if not ctx.needs_input_grad[0]:
-            return (None,) * 6
-        k = ctx.seg_dim
-        upstream = _upstream(g_seg, g_vertex, head_out.shape[0], head_out.device)
-        grad = torch.empty_like(head_out)
-        head_grad_device(head_out[:, :k], head_out[:, k:], mask, vertex, vertex_weights, upstream, sigma=ctx.sigma,
-                         out=(grad[:, :k], grad[:, k:]))
-        return grad, None, None, None, None, None
-
-
-class _KpHeadLossFn(torch.autograd.Function):
-    """``_HeadLossFn`` from key-points: saves the predictions, the mask and the key-points only"""
-
-    @staticmethod
-    def forward(ctx, seg_pred, vertex_pred, mask, hcoords, weight_scale, sigma, use_motion):
-        losses, _, _ = head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_scale, sigma=sigma, use_motion=use_motion)
-        saved = (seg_pred, vertex_pred, mask, hcoords) + (() if weight_scale is None else (weight_scale,))
-        ctx.save_for_backward(*saved)
-        ctx.sigma, ctx.use_motion = sigma, use_motion
-        loss_seg, loss_vertex, precision, recall = _float32_columns(losses)
-        ctx.mark_non_differentiable(precision, recall)
-        return loss_seg, loss_vertex, precision, recall
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_seg, g_vertex, _g_precision, _g_recall):
-        seg_pred, vertex_pred, mask, hcoords = ctx.saved_tensors[:4]
-        weight_scale = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
-        need = ctx.needs_input_grad[:2]
-        if not any(need):
-            return (None,) * 7
-        upstream = _upstream(g_seg, g_vertex, seg_pred.shape[0], seg_pred.device)
-        grad_seg, grad_vertex, _ = head_grad_from_keypoints(seg_pred, vertex_pred, mask, hcoords, upstream, weight_scale, sigma=ctx.sigma,
-                                                            use_motion=ctx.use_motion, need=need)
-        return grad_seg, grad_vertex, None, None, None, None, None
-
-
-class _KpPackedHeadLossFn(torch.autograd.Function):
-    """``_PackedHeadLossFn`` from key-points"""
-
-    @staticmethod
-    def forward(ctx, head_out, seg_dim, mask, hcoords, weight_scale, sigma, use_motion):
-        losses, _, _ = head_metrics_from_keypoints(head_out[:, :seg_dim], head_out[:, seg_dim:], mask, hcoords, weight_scale, sigma=sigma,
-                                                   use_motion=use_motion)
-        saved = (head_out, mask, hcoords) + (() if weight_scale is None else (weight_scale,))
-        ctx.save_for_backward(*saved)
-        ctx.sigma, ctx.seg_dim, ctx.use_motion = sigma, seg_dim, use_motion
-        loss_seg, loss_vertex, precision, recall = _float32_columns(losses)
-        ctx.mark_non_differentiable(precision, recall)
-        return loss_seg, loss_vertex, precision, recall
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_seg, g_vertex, _g_precision, _g_recall):
-        head_out, mask, hcoords = ctx.saved_tensors[:3]
-        weight_scale = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
-        if not ctx.needs_input_grad[0]:
-            return (None,) * 7
-        k = ctx.seg_dim
-        upstream = _upstream(g_seg, g_vertex, head_out.shape[0], head_out.device)
-        grad = torch.empty_like(head_out)
-        head_grad_from_keypoints(head_out[:, :k], head_out[:, k:], mask, hcoords, upstream, weight_scale, sigma=ctx.sigma,
-                                 use_motion=ctx.use_motion, out=(grad[:, :k], grad[:, k:]))
-        return grad, None, None, None, None, None, None
+        saved = iter(ctx.saved_tensors)
+        pred, pred2, mask, source, source2 = (next(saved) if there else None for there in ctx.present)
+        packed = ctx.seg_dim is not None
+        need = (True, True) if packed else ctx.needs_input_grad[:2]
+        if not (ctx.needs_input_grad[0] if packed else any(need)):
+            return (None,) * 9
+        seg_pred, vertex_pred = _HeadLossFn._predictions(pred, pred2, ctx.seg_dim)
+        upstream = _upstream(g_seg, g_vertex, pred.shape[0], pred.device)
+        grad = torch.empty_like(pred) if packed else None
+        out = _HeadLossFn._predictions(grad, None, ctx.seg_dim) if packed else None
+        if ctx.keypoints:
+            grad_seg, grad_vertex, _ = head_grad_from_keypoints(seg_pred, vertex_pred, mask, source, upstream, source2, sigma=ctx.sigma,
+                                                                use_motion=ctx.use_motion, need=need, out=out)
+        else:
+            grad_seg, grad_vertex, _ = head_grad_device(seg_pred, vertex_pred, mask, source, source2, upstream, sigma=ctx.sigma, need=need,
+                                                        out=out)
+        return ((grad, None) if packed else (grad_seg, grad_vertex)) + (None,) * 7
 
 
 class HeadLoss(torch.nn.Module):
@@ -515,22 +426,24 @@ class HeadLoss(torch.nn.Module):
         self.sigma = float(sigma)
 
     def forward(self, seg_pred, vertex_pred, mask, vertex, vertex_weights):
-        return _HeadLossFn.apply(seg_pred, vertex_pred, mask, vertex, vertex_weights, self.sigma)
+        return _HeadLossFn.apply(seg_pred, vertex_pred, None, mask, vertex, vertex_weights, self.sigma, False, False)
+
+    @staticmethod
+    def _seg_dim(head_out, seg_dim):
+        seg_dim = int(seg_dim)
+        if not (isinstance(head_out, torch.Tensor) and head_out.dim() == 4 and 2 <= seg_dim < head_out.shape[1]):
+            raise RuntimeError("head_out must be [b,seg_dim+2vn,h,w] with seg_dim >= 2")
+        return seg_dim
 
     def packed(self, head_out, seg_dim, mask, vertex, vertex_weights):
-        seg_dim = int(seg_dim)
-        if not (isinstance(head_out, torch.Tensor) and head_out.dim() == 4 and 2 <= seg_dim < head_out.shape[1]):
-            raise RuntimeError("head_out must be [b,seg_dim+2vn,h,w] with seg_dim >= 2")
-        return _PackedHeadLossFn.apply(head_out, seg_dim, mask, vertex, vertex_weights, self.sigma)
+        return _HeadLossFn.apply(head_out, None, self._seg_dim(head_out, seg_dim), mask, vertex, vertex_weights, self.sigma, False, False)
 
     def from_keypoints(self, seg_pred, vertex_pred, mask, hcoords, weight_scale=None, use_motion=False):
-        return _KpHeadLossFn.apply(seg_pred, vertex_pred, mask, hcoords, weight_scale, self.sigma, bool(use_motion))
+        return _HeadLossFn.apply(seg_pred, vertex_pred, None, mask, hcoords, weight_scale, self.sigma, bool(use_motion), True)
 
     def packed_from_keypoints(self, head_out, seg_dim, mask, hcoords, weight_scale=None, use_motion=False):
-        seg_dim = int(seg_dim)
-        if not (isinstance(head_out, torch.Tensor) and head_out.dim() == 4 and 2 <= seg_dim < head_out.shape[1]):
-            raise RuntimeError("head_out must be [b,seg_dim+2vn,h,w] with seg_dim >= 2")
-        return _KpPackedHeadLossFn.apply(head_out, seg_dim, mask, hcoords, weight_scale, self.sigma, bool(use_motion))
+        return _HeadLossFn.apply(head_out, None, self._seg_dim(head_out, seg_dim), mask, hcoords, weight_scale, self.sigma,
+                                 bool(use_motion), True)
 
 
 class ValStep(object):

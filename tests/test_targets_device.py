@@ -215,6 +215,38 @@ def test_fused_equals_materialised(pred_dtype, h, w):
     check_fused(seg3, vp3, mask3, hc3, what="three classes")
 
 
+@pytest.mark.parametrize("h,w", [(48, 64), (37, 53)])
+def test_fused_one_half_equals_that_half_of_both(h, w):
+    """one body serves both halves: a half asked for alone is bit for bit the same half of the two-half call, fast and general path;
+    without the logits' half no label is judged -- status 0 even with a label outside 0..C-1"""
+    d = dev()
+    seg, vp, mask, hc = head_case(2, h, w, 3, d, seed=h + 21)
+    mask[1, h // 2, w // 3] = 2   # outside 0..1
+    up = upstream_for(2, d)
+    both = V.head_grad_from_keypoints(seg, vp, mask, hc, up)
+    only_s = V.head_grad_from_keypoints(seg, vp, mask, hc, up, need=(True, False))
+    only_v = V.head_grad_from_keypoints(seg, vp, mask, hc, up, need=(False, True))
+    torch.cuda.synchronize()
+    assert only_s[1] is None and only_v[0] is None
+    assert same(only_s[0], both[0]) and int(torch.isnan(both[0]).sum()) == 2   # the bad pixel's C gradients are NaN in either call
+    assert torch.equal(only_v[1], both[1]) and float(both[1].abs().max()) > 0.0
+    assert both[2].tolist() == [0, V.HEAD_S_BAD_LABEL] and only_s[2].tolist() == [0, V.HEAD_S_BAD_LABEL]
+    assert only_v[2].tolist() == [0, 0]
+
+
+@pytest.mark.parametrize("h,w", [(1, 1), (3, 1024), (8, 1)])
+def test_fused_degenerate_sizes(h, w):
+    """one pixel (general path); three rows of one segment each, where a lane's eight pixels never wrap to the next row; a column,
+    where they wrap at every pixel (fast path)"""
+    d = dev()
+    seg, vp, mask, hc = head_case(2, h, w, 3, d, seed=h + w)
+    mask[:, 0, 0] = 1   # a target pixel in every image, the 1 x 1 one included
+    hc = torch.from_numpy(keypoints_for(mask, 3, seed=h * w)).to(d)
+    got, ggot = check_fused(seg, vp, mask, hc, what=f"{h}x{w}")
+    assert torch.isfinite(got[0]).all() and float(ggot[1].abs().max()) > 0.0
+    check_fused(seg.bfloat16(), vp.bfloat16(), mask, hc, use_motion=True, what=f"{h}x{w} bfloat16, motion")
+
+
 @pytest.mark.parametrize("mask_dtype", [torch.uint8, torch.bool, torch.int32])
 def test_fused_every_mask_dtype_and_bad_labels(mask_dtype):
     d = dev()

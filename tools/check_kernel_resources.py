@@ -91,40 +91,29 @@ def assembly():
     return _ASM
 
 
-def head_assembly():
-    """[(translation unit, assembly text)] of libpvnet_head.so (pvnet_amd/csrc/head_metrics.hip; one build, no development variant)"""
+def side_assembly(name):
+    """[(translation unit, assembly text)] of one of build.SIDE_LIBRARIES (libpvnet_head.so, libpvnet_train.so, libpvnet_targets.so:
+    one build each, no development variant)"""
     sys.path.insert(0, ROOT)
     from pvnet_amd import build as B
     out = []
     with tempfile.TemporaryDirectory() as d:
-        for k, src in enumerate(B.HEAD_SRC):
-            compile_to_asm(src, os.path.join(d, f"h{k}.s"))
-            out.append((src, open(os.path.join(d, f"h{k}.s")).read()))
+        for k, src in enumerate(B._side(name)[0]):
+            compile_to_asm(src, os.path.join(d, f"{name}{k}.s"))
+            out.append((src, open(os.path.join(d, f"{name}{k}.s")).read()))
     return out
+
+
+def head_assembly():
+    return side_assembly("head")
 
 
 def train_assembly():
-    """[(translation unit, assembly text)] of libpvnet_train.so (pvnet_amd/csrc/head_grad.hip; one build, no development variant)"""
-    sys.path.insert(0, ROOT)
-    from pvnet_amd import build as B
-    out = []
-    with tempfile.TemporaryDirectory() as d:
-        for k, src in enumerate(B.TRAIN_SRC):
-            compile_to_asm(src, os.path.join(d, f"t{k}.s"))
-            out.append((src, open(os.path.join(d, f"t{k}.s")).read()))
-    return out
+    return side_assembly("train")
 
 
 def targets_assembly():
-    """[(translation unit, assembly text)] of libpvnet_targets.so (pvnet_amd/csrc/head_targets.hip; one build, no development variant)"""
-    sys.path.insert(0, ROOT)
-    from pvnet_amd import build as B
-    out = []
-    with tempfile.TemporaryDirectory() as d:
-        for k, src in enumerate(B.TARGETS_SRC):
-            compile_to_asm(src, os.path.join(d, f"g{k}.s"))
-            out.append((src, open(os.path.join(d, f"g{k}.s")).read()))
-    return out
+    return side_assembly("targets")
 
 
 def kernel_code(text):
