@@ -1,7 +1,7 @@
 """The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h), of libpvnet_head.so
 (include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``), of libpvnet_train.so (include/pvnet_train.h:
-``TRAIN_PROTOTYPES``, ``load_train_library``) and of libpvnet_targets.so (include/pvnet_targets.h: ``TARGETS_PROTOTYPES``,
-``load_targets_library``).
+``TRAIN_PROTOTYPES``, ``load_train_library``), of libpvnet_targets.so (include/pvnet_targets.h: ``TARGETS_PROTOTYPES``,
+``load_targets_library``) and of libpvnet_augment.so (include/pvnet_augment.h: ``AUGMENT_PROTOTYPES``, ``load_augment_library``).
 
 Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
 and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
@@ -141,11 +141,40 @@ TARGETS_PROTOTYPES = {
     "pvnet_head_grad_kp": (_int, _KP_HEAD + [_ptr, _ptr, _i64p, _ptr, _i64p, _ptr, _ptr, _size, _ptr]),
 }
 
+# ---- libpvnet_augment.so (include/pvnet_augment.h): the augmentation of a training batch; it takes the MASK_* codes and E_* above ---
+AUGMENT_LIB_PATH = os.path.join(_HERE, "libpvnet_augment.so")
+AUGMENT_ABI_VERSION = 1
+AUGMENT_F_MASK, AUGMENT_F_ROTATION, AUGMENT_F_CROP, AUGMENT_F_FLIP, AUGMENT_F_USE_MASK_OUT = 1, 2, 4, 8, 16
+AUGMENT_OUT_F32, AUGMENT_OUT_BF16, AUGMENT_OUT_F16 = 0, 1, 2
+AUGMENT_S_RANGE, AUGMENT_S_EMPTIED, AUGMENT_S_DEGENERATE, AUGMENT_S_NO_FOREGROUND = 1, 2, 4, 8
+AUGMENT_UNIFORMS = 14
+
+
+class AugmentConfigStruct(C.Structure):
+    """ctypes image of ``PvnetAugmentConfig`` (include/pvnet_augment.h)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(n, C.c_double) for n in ("min_mask", "max_mask", "overlap_ratio", "resize_hmin", "resize_hmax", "resize_wmin",
+                                          "resize_wmax")] + [("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
+_cfgp = C.POINTER(AugmentConfigStruct)
+AUGMENT_PROTOTYPES = {
+    "pvnet_augment_abi_version": (_int, []),
+    "pvnet_augment_workspace_bytes": (_size, [_int]),
+    # rgb + strides, mask + dtype + strides, hcoords, uniforms, b, h, w, vn, height, width, cfg, seed, image + dtype, mask_out + dtype,
+    # hcoords_out, status, workspace + bytes, stream
+    "pvnet_augment": (_int, [_ptr, _i64p, _ptr, _int, _i64p, _ptr, _ptr] + [_int] * 6 + [_cfgp, C.c_uint64, _ptr, _int, _ptr, _int, _ptr,
+                             _ptr, _ptr, _size, _ptr]),
+    # rgb + strides, b, h, w, cfg, image + dtype, stream
+    "pvnet_normalize": (_int, [_ptr, _i64p, _int, _int, _int, _cfgp, _ptr, _int, _ptr]),
+}
+
 _lib = None
 _libs = {}   # path -> loaded library
 _head_lib = None
 _train_lib = None
 _targets_lib = None
+_augment_lib = None
 
 
 def _wanted_library() -> str:
@@ -213,6 +242,12 @@ def load_targets_library() -> C.CDLL:
     """dlopen libpvnet_targets.so (targets from key-points, the head fused with them); loud failure if it has not been built.  There is
     no CPU fallback."""
     return _load_side("targets")
+
+
+def load_augment_library() -> C.CDLL:
+    """dlopen libpvnet_augment.so (the augmentation of a training batch); loud failure if it has not been built.  There is no CPU
+    fallback."""
+    return _load_side("augment")
 
 
 def reload_tuning():

@@ -1,6 +1,6 @@
 """Builds libpvnet_vote.so (the C-ABI HIP library), libpvnet_head.so (the head metrics, a library of its own), libpvnet_train.so
-(the head losses' backward, likewise) and libpvnet_targets.so (the targets from key-points and the head fused with them, likewise)
-in-tree for gfx950 with hipcc.
+(the head losses' backward, likewise), libpvnet_targets.so (the targets from key-points and the head fused with them, likewise) and
+libpvnet_augment.so (the augmentation of a training batch, likewise) in-tree for gfx950 with hipcc.
 
     python -m pvnet_amd.build            # build if sources are newer than the library
     python -m pvnet_amd.build --force
@@ -35,6 +35,7 @@ SIDE_LIBRARIES = {
     "head": (["head_metrics.hip"], "pvnet_head.h", "--head"),          # the head metrics of a validation step
     "train": (["head_grad.hip"], "pvnet_train.h", "--train"),          # the backward of the head losses of a training step
     "targets": (["head_targets.hip"], "pvnet_targets.h", "--targets"),  # the targets from key-points, the head fused with them
+    "augment": (["augment.hip"], "pvnet_augment.h", "--augment"),       # the inputs of a training step: warp, normalise, key-points
 }
 
 
@@ -51,6 +52,8 @@ HEAD_TU, TRAIN_TU, TARGETS_TU = (SIDE_LIBRARIES[n][0] for n in ("head", "train",
 HEAD_SRC, HEAD_DEPS, HEAD_LIB = _side("head")
 TRAIN_SRC, TRAIN_DEPS, TRAIN_LIB = _side("train")
 TARGETS_SRC, TARGETS_DEPS, TARGETS_LIB = _side("targets")
+AUGMENT_TU = SIDE_LIBRARIES["augment"][0]
+AUGMENT_SRC, AUGMENT_DEPS, AUGMENT_LIB = _side("augment")
 # host-side pose refinement (plain C++, g++): include/pvnet_pnp.h
 PNP_SRC = os.path.join(HERE, "csrc", "pvnet_pnp.cpp")
 PNP_DEPS = [PNP_SRC, os.path.join(ROOT, "include", "pvnet_pnp.h")]
@@ -151,6 +154,10 @@ def build_train(force: bool = False, verbose: bool = False) -> str:
 
 def build_targets(force: bool = False, verbose: bool = False) -> str:
     return build_side("targets", force, verbose)
+
+
+def build_augment(force: bool = False, verbose: bool = False) -> str:
+    return build_side("augment", force, verbose)
 
 
 # the reference's compiled extension module `ransac_voting` (src/ransac_voting.cpp) on this library: host-only C++ against
@@ -262,6 +269,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_head(force, verbose)
     build_train(force, verbose)
     build_targets(force, verbose)
+    build_augment(force, verbose)
     build_ext(force, verbose)
     build_canary(force, verbose)
     return LIB

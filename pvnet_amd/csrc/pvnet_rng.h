@@ -16,6 +16,7 @@
 
 #define PVNET_TAG_HYP 0x48595031u /* pixel-pair draws   : stream = image, counter = (h*vn + k)*2 + j */
 #define PVNET_TAG_SUB 0x53554231u /* subsample decisions: stream = image, counter = y*w + x          */
+#define PVNET_TAG_AUG 0x41554731u /* mask-out fill (augment.hip): stream = image, counter = (y*w + x)*3 + c; value pvnet_rng_below(r, 255) */
 
 PVNET_HD uint32_t pvnet_mix32(uint32_t x) {
     x ^= x >> 16; x *= 0x21F0AAADu;
