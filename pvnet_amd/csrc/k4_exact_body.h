@@ -121,10 +121,161 @@ __device__ __forceinline__ void vote_slow_close(unsigned& cnt, unsigned& flg, un
         : "vcc");
 }
 
+// The open cell of the FOLD = 1 step: the x of the eight tests whose slow operations are still due (see vote_subs), the open
+// cell's votes / minimum.  A chain of steps is first() or, from an idle() cell, next(); then next() per step; then close().
+#define PV_XS x0, x1, x2, x3, x4, x5, x6, x7
+#define PV_LO(v, w) v[0], w[0], v[1], w[1], v[2], w[2], v[3], w[3], v[4], w[4], v[5], w[5], v[6], w[6], v[7], w[7]
+#define PV_HI(v, w) v[8], w[8], v[9], w[9], v[10], w[10], v[11], w[11], v[12], w[12], v[13], w[13], v[14], w[14], v[15], w[15]
+struct OpenCell {
+    float x0, x1, x2, x3, x4, x5, x6, x7, dmo;
+    unsigned acc;
+    __device__ __forceinline__ void idle() {   // nothing due: x = -4 counts no vote and flags nothing, closing it shifts in a zero
+        x0 = x1 = x2 = x3 = x4 = x5 = x6 = x7 = -4.f, dmo = 3.0e38f, acc = 0u;
+    }
+    __device__ __forceinline__ void subs_lo(const f32x16& va, const f32x16& vb) { vote_subs(PV_XS, PV_LO(va, vb)); }
+    __device__ __forceinline__ void subs_hi(const f32x16& va, const f32x16& vb) { vote_subs(PV_XS, PV_HI(va, vb)); }
+    __device__ __forceinline__ void open() { vote_slow_open(acc, dmo, PV_XS); }
+    __device__ __forceinline__ void close(unsigned& cnt, unsigned& flg) { vote_slow_close(cnt, flg, acc, dmo, PV_XS); }
+    __device__ __forceinline__ void open_on(const f32x16& va, const f32x16& vb) {
+        subs_lo(va, vb);
+        open();
+        subs_hi(va, vb);
+    }
+    // both right behind the step's two MFMAs (the votes are inline asm: the wait states are ours, tools/check_mfma_hazard.py);
+    // next(): the previous step's last 15 operations fill most of the wait
+    __device__ __forceinline__ void first(const f32x16& va, const f32x16& vb) {
+        asm volatile("s_nop 11");
+        open_on(va, vb);
+    }
+    __device__ __forceinline__ void next(unsigned& cnt, unsigned& flg, const f32x16& va, const f32x16& vb) {
+        close(cnt, flg);
+        asm volatile("s_nop 3");
+        open_on(va, vb);
+    }
+};
+
+// TIMED only: shader-clock cycles of this workgroup's wave 0 per phase (the bodies say which four), stored behind the workgroups'
+// wall-clock stamps in the launch's stamp array (P.pix; tools/phase_probe.py)
+template <bool TIMED>
+struct PhaseClock {
+    unsigned long long ph[4] = {0ull, 0ull, 0ull, 0ull}, tprev = 0ull;
+    static __device__ __forceinline__ void stamp(const VoteParams& P, int end) {   // the workgroup's opening (0) / closing (1) stamp
+        if (TIMED && threadIdx.x == 0) reinterpret_cast<unsigned long long*>(P.pix)[2 * blockIdx.x + end] = (unsigned long long)wall_clock64();
+    }
+    __device__ __forceinline__ void start() {
+        if (TIMED) tprev = (unsigned long long)clock64();
+    }
+    __device__ __forceinline__ void mark(int i) {
+        if (TIMED) {
+            const unsigned long long now_ = (unsigned long long)clock64();
+            ph[i] += now_ - tprev;
+            tprev = now_;
+        }
+    }
+    __device__ __forceinline__ void finish(const VoteParams& P) {
+        if (TIMED) {
+            lds_barrier();
+            mark(3);
+            stamp(P, 1);
+            if (threadIdx.x == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) reinterpret_cast<unsigned long long*>(P.pix)[2 * gridDim.x + 4 * blockIdx.x + i] = ph[i];
+            }
+        }
+    }
+};
+
+// the clean cells' votes of a finished item / run into their row of the counts (pc: the wave's first hypothesis), hypothesis tiles in
+// pairs; the counters start again at zero
+template <int MH>
+__device__ __forceinline__ void flush_counts(int32_t* const pc, unsigned (&cnt)[MH]) {
+    int lanex = threadIdx.x;
+    asm volatile("" : "+v"(lanex));   // (opaque: keeps the eight addresses from being hoisted above the scoring loop)
+    lanex &= 63;
+    if (MH >= 2) {  // lanes 0..31 finish tile t, lanes 32..63 tile t + 1
+#pragma unroll
+        for (int t = 0; t + 1 < MH; t += 2) {
+            const int c = votes_of_norm(half_wave_sum2(cnt[t], cnt[t + 1]));
+            if (c > 0) atomicAdd(pc + t * 32 + lanex, c);
+        }
+    } else {
+        const int c = votes_of_norm(half_wave_sum2(cnt[0], cnt[0]));
+        if (lanex < 32 && c > 0) atomicAdd(pc + lanex, c);
+    }
+#pragma unroll
+    for (int t = 0; t < MH; ++t) cnt[t] = 0u;
+}
+
+// The wave's flagged cells (flg[t] != 0: hypothesis tile t of this lane) into the item's list: ONE slot reservation per wave and item
+// -- the MH ballots and their popcounts are scalar work, the wave's cells go behind one LDS atomic (round 6; one reservation per
+// hypothesis tile, most of them taken, cost ~70 vector operations more).  A cell's word: hypothesis in the slice | half-wave << 10 |
+// flg << 11.  h0 = the wave's first hypothesis; columns from P.hn on are padding.
+template <int MH>
+__device__ __forceinline__ void list_flagged_cells(const VoteParams& P, unsigned (&flg)[MH], int h0, int lane, int wave, int colx, int halfx,
+                                                   unsigned* s_cells, int* s_ncell) {
+    const bool padded = h0 + MH * 32 > P.hn;  // wave-uniform: only the last slice can hold padding columns
+    unsigned long long bal[MH];
+    int ncw = 0;
+#pragma unroll
+    for (int t = 0; t < MH; ++t) {
+        if (padded && h0 + t * 32 + colx >= P.hn) flg[t] = 0u;  // padding columns of the last slice: nobody reads their counts
+        bal[t] = __ballot(flg[t] != 0u);
+        ncw += (int)__popcll(bal[t]);
+    }
+    if (ncw) {  // wave-uniform
+        int base = 0;
+        if (lane == 0) base = atomicAdd(s_ncell, ncw);
+        base = __builtin_amdgcn_readfirstlane(base);
+        const unsigned cell0 = (unsigned)(wave * MH * 32 + colx) | ((unsigned)halfx << 10);
+#pragma unroll
+        for (int t = 0; t < MH; ++t) {
+            if (bal[t]) {  // wave-uniform
+                const int slot = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal[t] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal[t], 0u));
+                if (flg[t] != 0u) s_cells[slot] = (cell0 + (unsigned)(t * 32)) | (flg[t] << 11);
+                base += (int)__popcll(bal[t]);
+            }
+        }
+    }
+}
+
+// re-evaluation of a flagged cell, 16 lanes (q = 0..15) with one pixel each: their votes summed, lane 0 adds them to the cell's count
+__device__ __forceinline__ void add_cell_votes(int32_t* const count, int votes, int q) {
+    votes += (int)lane_xor((uint32_t)votes, 8);   // (DPP / ds_swizzle: no lane index, no address operand -- __shfl_xor's was
+    votes += (int)lane_xor((uint32_t)votes, 4);   //  kept in a register across the whole item loop)
+    votes += (int)lane_xor((uint32_t)votes, 2);
+    votes += (int)lane_xor((uint32_t)votes, 1);
+    if (q == 0 && votes > 0) atomicAdd(count, votes);
+}
+// PVNET_F_BAND_STATS, development aid: how much was re-evaluated (tools/exact_probe.py)
+__device__ __forceinline__ void add_band_stats(const VoteParams& P, int tid, int q, int ncell, int ntests) {
+    if (P.flags & PVNET_F_BAND_STATS) {
+        if (tid == 0) atomicAdd(P.ctrl + P.b * CTRL_STRIDE + 4, ncell);
+        if (q == 0 && ntests > 0) atomicAdd(P.ctrl + P.b * CTRL_STRIDE + 5, ntests);
+    }
+}
+
+// a work item's descriptor (P.items: image, key-point | culled flag, pixel group, hypothesis slice) decoded
+template <int MH>
+struct ItemHeader {
+    int cg, hq, tpad;      // pixel group, hypothesis slice, the key-point's record count padded
+    size_t bk;             // (image, key-point)
+    float rho, ox, oy;     // band_rho(tn), from the plan block of K3; the band's origin for this key-point (hypothesis_kernel)
+    int hslice, h0;        // first hypothesis of this work item / of this wave
+    __device__ __forceinline__ ItemHeader(const VoteParams& P, const int32_t* __restrict__ ctrl, const int4& desc, int wave) {
+        const int bi = desc.x, tn = ctrl[bi * CTRL_STRIDE + C_TN];
+        cg = desc.z, hq = desc.w, tpad = (tn + PAD - 1) / PAD * PAD;
+        rho = __uint_as_float((unsigned)ctrl[bi * CTRL_STRIDE + C_RHO]);
+        bk = (size_t)bi * P.vn + item_kp(desc.y);
+        const int32_t* const org = band_origin_ptr(P, bk);
+        ox = (float)org[0], oy = (float)org[1];
+        hslice = hq * 4 * MH * 32, h0 = hslice + wave * MH * 32;
+    }
+};
+
 // FOLD = 0: one cell per (lane, hypothesis tile) and work item -- the minimum runs over all the item's pixel tiles
-//           (cheapest epilogue; right when flagged cells are very rare: loose thresholds, band_fold());
+//           (cheapest epilogue; right when flagged cells are very rare: loose thresholds, band_fold1());
 // FOLD = 1: one cell per (lane, hypothesis tile, PIXEL tile) -- the test is made after every step (four more VALU operations,
-//           vote8x_open / vote8x_close), and a flagged cell costs 16 literal tests instead of 16 * tiles.
+//           vote_slow_open / vote_slow_close), and a flagged cell costs 16 literal tests instead of 16 * tiles.
 // NACC = 2: two accumulator pairs -- the MFMAs of step i + 1 are issued around the votes of step i (the flat pipeline of the
 //           approximate kernel);
 // NACC = 1: one pair -- a wave issues the step's two MFMAs and consumes their results right away, the SIMD's other waves
@@ -137,19 +288,19 @@ __device__ __forceinline__ void vote_slow_close(unsigned& cnt, unsigned& flg, un
 //           votes in their counters: loaded / flushed once per run instead of once per 256-pixel item.  Same-box A/B
 //           (profiles/r04_ab_runs.txt): +2 % with six batches in flight (less work), -4.5 % for a batch alone (the contiguous
 //           mapping itself: a launch of strided items ends more evenly) -- so it is what calls flagged PVNET_F_CONCURRENT run.
-// HEAD (round 6): the body is the FIRST of the two a merged launch runs (score_exact_both_kernel: the dense items here, the
+// HEAD (round 6): the body is the FIRST of the two a merged launch runs (score_exact_kernel_both_*: the dense items here, the
 //           disc-culled ones in score_cull_body behind it) -- the kernel's register allocation and its closing clock stamps are
 //           the second body's.
 template <int MH, int FOLD, bool TIMED, int NACC, bool RUNS_, bool HEAD = false>
 __device__ __forceinline__ void score_exact_body(VoteParams P) {
-    if (HEAD) { }
-    else if (MH == 8 && NACC == 2) PVNET_SPARE_VGPRS(167);
-    else if (MH == 8 && RUNS_) PVNET_SPARE_VGPRS(135);
-    else if (MH == 8) PVNET_SPARE_VGPRS(127);  // (one pair, strided items: what a batch ALONE runs, four waves per SIMD)
-    else if (MH == 4) PVNET_SPARE_VGPRS(143);
-    else PVNET_SPARE_VGPRS(111);
-    unsigned long long* __restrict__ stamps = reinterpret_cast<unsigned long long*>(P.pix);
-    if (TIMED && threadIdx.x == 0) stamps[2 * blockIdx.x] = (unsigned long long)wall_clock64();
+    if (!HEAD) {
+        if (MH == 8 && NACC == 2) PVNET_SPARE_VGPRS(167);
+        else if (MH == 8 && RUNS_) PVNET_SPARE_VGPRS(135);
+        else if (MH == 8) PVNET_SPARE_VGPRS(127);  // (one pair, strided items: what a batch ALONE runs, four waves per SIMD)
+        else if (MH == 4) PVNET_SPARE_VGPRS(143);
+        else PVNET_SPARE_VGPRS(111);
+    }
+    PhaseClock<TIMED>::stamp(P, 0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -164,18 +315,10 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const uint4* lbase = s_t + half * 32 + col;
 
-    // TIMED only: shader-clock cycles of this workgroup's wave 0 per phase (0 staging incl. the wait for its loads and the
-    // barrier, 1 scoring loop, 2 count flush + cell list + barrier, 3 re-evaluation + the next item's first barrier)
-    unsigned long long ph[4] = {0ull, 0ull, 0ull, 0ull}, tprev = 0ull;
-#define PV_PHASE(i)                                                     \
-    do {                                                                \
-        if (TIMED) {                                                    \
-            const unsigned long long now_ = (unsigned long long)clock64(); \
-            ph[i] += now_ - tprev;                                      \
-            tprev = now_;                                               \
-        }                                                               \
-    } while (0)
-    if (TIMED) tprev = (unsigned long long)clock64();
+    // phases: 0 staging incl. the wait for its loads and the barrier, 1 scoring loop, 2 count flush + cell list + barrier,
+    // 3 re-evaluation + the next item's first barrier
+    PhaseClock<TIMED> clk;
+    clk.start();
     constexpr bool RUNS = RUNS_ && FOLD == 1;
     bf16x8 B[MH];
     unsigned cnt[MH];   // wrapped vote counters of the clean cells (vote8x / votes_of_norm)
@@ -184,74 +327,48 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
     long long run_key = -1;      // (image, key-point) * slices + slice of the run the counters belong to
     int run_h0 = 0, run_items = 0;
     size_t run_bk = 0;
-    auto flush_counts = [&](size_t fbk, int fh0) {   // the clean cells' votes of a finished item / run, hypothesis tiles in pairs
-        int32_t* const pc = P.counts + fbk * P.hn_pad + fh0;
-        int lanex = threadIdx.x;
-        asm volatile("" : "+v"(lanex));   // (opaque: keeps the eight addresses from being hoisted above the scoring loop)
-        lanex &= 63;
-        if (MH >= 2) {  // lanes 0..31 finish tile t, lanes 32..63 tile t + 1
-#pragma unroll
-            for (int t = 0; t + 1 < MH; t += 2) {
-                const int c = votes_of_norm(half_wave_sum2(cnt[t], cnt[t + 1]));
-                if (c > 0) atomicAdd(pc + t * 32 + lanex, c);
-            }
-        } else {
-            const int c = votes_of_norm(half_wave_sum2(cnt[0], cnt[0]));
-            if (lanex < 32 && c > 0) atomicAdd(pc + lanex, c);
-        }
-#pragma unroll
-        for (int t = 0; t < MH; ++t) cnt[t] = 0u;
-    };
     const ItemRange ir = my_items<RUNS>(P, total);
     for (int item = ir.first; item < ir.end; item += ir.step) {
         const int4 desc = P.items[item];
         if (item_culled(desc.y)) continue;   // (workgroup-uniform) a key-point the disc-culling body scores
-        const int bi = desc.x, k = item_kp(desc.y), cg = desc.z, hq = desc.w;
-        const int tn = ctrl[bi * CTRL_STRIDE + C_TN];
-        const float rho = __uint_as_float((unsigned)ctrl[bi * CTRL_STRIDE + C_RHO]);   // band_rho(tn), from the plan block of K3
-        const size_t bk = (size_t)bi * P.vn + k;
-        const int32_t* const org = band_origin_ptr(P, bk);   // the band's origin for this key-point (hypothesis_kernel)
-        const float ox = (float)org[0], oy = (float)org[1];
-        const int tpad = (tn + PAD - 1) / PAD * PAD;
-        const int hslice = hq * 4 * MH * 32;            // first hypothesis of this work item
-        const int h0 = hslice + wave * MH * 32;         // this wave's first hypothesis
-        const long long key = (long long)bk * (P.hgroups / P.wg_g) + hq;
+        const ItemHeader<MH> it(P, ctrl, desc, wave);
+        const long long key = (long long)it.bk * (P.hgroups / P.wg_g) + it.hq;
         // workgroup-uniform: a new run.  The packed-norm counters hold < 65536 votes per half: a lane adds 8 votes per half and
         // pixel tile, half_wave_sum2 joins two lanes -- 16 * ntiles per item, so a run is cut after 65535 / (16 * ntiles) items
         // (a fixed 256 overflowed from 16 tiles per item on, PVNET_SCORE_CHUNK >= 256)
         const bool fresh = !RUNS || key != run_key || run_items >= 65535 / (16 * ntiles);
 
         lds_barrier();  // the previous item's tiles, raw records and cell list have been consumed
-        PV_PHASE(3);
+        clk.mark(3);
         if (threadIdx.x == 0) s_ncell = 0;
         int tid = threadIdx.x;  // opaque copies of the thread index: what staging and re-evaluation derive from it is
         asm volatile("" : "+v"(tid));  // recomputed per item instead of staying in VGPRs across the scoring loop
         float2 hreg[(4 * MH * 32 + 255) / 256];  // the run's hypotheses: loaded now, parked in LDS after the staging arithmetic
         if (fresh) {
-            if (RUNS && run_key >= 0) flush_counts(run_bk, run_h0);
+            if (RUNS && run_key >= 0) flush_counts<MH>(P.counts + run_bk * P.hn_pad + run_h0, cnt);
             run_key = key;
-            run_bk = bk;
-            run_h0 = h0;
+            run_bk = it.bk;
+            run_h0 = it.h0;
             run_items = 0;
 #pragma unroll
             for (int j = 0; j < (4 * MH * 32 + 255) / 256; ++j)
-                hreg[j] = (tid + 256 * j < 4 * MH * 32) ? P.hyp[bk * P.hn_pad + hslice + tid + 256 * j] : make_float2(0.f, 0.f);
+                hreg[j] = (tid + 256 * j < 4 * MH * 32) ? P.hyp[it.bk * P.hn_pad + it.hslice + tid + 256 * j] : make_float2(0.f, 0.f);
 #pragma unroll
             for (int t = 0; t < MH; ++t) {
-                const uint4 raw = P.hypb[(bk * P.hn_pad + h0 + t * 32 + (tid & 31)) * 2 + ((tid >> 5) & 1)];  // (column, half-wave)
+                const uint4 raw = P.hypb[(it.bk * P.hn_pad + it.h0 + t * 32 + (tid & 31)) * 2 + ((tid >> 5) & 1)];  // (column, half-wave)
                 B[t] = __builtin_bit_cast(bf16x8, raw);
             }
         }
         ++run_items;
         for (int i = tid; i < npx; i += 256) {
-            const int p = cg * npx + i;
+            const int p = it.cg * npx + i;
             float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (p < tpad) q = P.rec[bk * P.cap + p];
+            if (p < it.tpad) q = P.rec[it.bk * P.cap + p];
             s_raw[i] = q;
             uint4* t = s_t + (i >> 5) * TILE_U4 + (i & 31);
             uint4 r0, r1, r2, r3;  // (in registers first: by reference into LDS every assignment inside would be a store)
             float mu_unused;
-            a_rows_exact(q, P.tau, ox, oy, rho, r0, r1, r2, r3, mu_unused);
+            a_rows_exact(q, P.tau, it.ox, it.oy, it.rho, r0, r1, r2, r3, mu_unused);
             t[0] = r0;
             t[32] = r1;
             t[64] = r2;
@@ -263,7 +380,7 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                 if (tid + 256 * j < 4 * MH * 32) s_hyp[tid + 256 * j] = hreg[j];
         }
         lds_barrier();
-        PV_PHASE(0);
+        clk.mark(0);
 
         float dmn[MH];      // min |x| of the open cell so far
         unsigned flg[MH];   // FOLD: bit (nti - 1 - tile) set = pixel tile `tile` holds a test inside the band
@@ -272,17 +389,13 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
             flg[t] = 0u;
             dmn[t] = 3.0e38f;
         }
-        const int left = (tpad - cg * npx + 31) >> 5;
+        const int left = (it.tpad - it.cg * npx + 31) >> 5;
         const int nti = left < ntiles ? left : ntiles;
         bf16x8 Aa = __builtin_bit_cast(bf16x8, lbase[0]), Ab = __builtin_bit_cast(bf16x8, lbase[64]);
-        // FOLD: the x of the eight tests whose slow operations are still due (see vote_subs), the open cell's votes / minimum.
-        // Before the first step nothing is due: x = -4 counts no vote and flags nothing, the cell it "closes" shifts a zero
-        // into a zero flag word of the last hypothesis tile.
-        float x0 = -4.f, x1 = -4.f, x2 = -4.f, x3 = -4.f, x4 = -4.f, x5 = -4.f, x6 = -4.f, x7 = -4.f, dmo = 3.0e38f;
-        unsigned acc = 0u;
-#define PV_XS x0, x1, x2, x3, x4, x5, x6, x7
-#define PV_LO(v, w) v[0], w[0], v[1], w[1], v[2], w[2], v[3], w[3], v[4], w[4], v[5], w[5], v[6], w[6], v[7], w[7]
-#define PV_HI(v, w) v[8], w[8], v[9], w[9], v[10], w[10], v[11], w[11], v[12], w[12], v[13], w[13], v[14], w[14], v[15], w[15]
+        // FOLD: before the first step nothing is due -- every step is a next(), the first one "closes" an idle cell into the
+        // zero flag word of the last hypothesis tile
+        OpenCell oc;
+        oc.idle();
         if (NACC == 1) {
             // one pixel tile against the wave's MH hypothesis tiles
             auto tile_steps = [&](const bf16x8& Ta, const bf16x8& Tb) __attribute__((always_inline)) {
@@ -291,14 +404,10 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                     const f32x16 va = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ta, B[t], zero, 0, 0, 0);
                     const f32x16 vb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Tb, B[t], zero, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (FOLD) {   // the previous step's last 15 operations fill the wait for this step's MFMAs
-                        vote_slow_close(cnt[(t + MH - 1) % MH], flg[(t + MH - 1) % MH], acc, dmo, PV_XS);
-                        asm volatile("s_nop 3");   // (the votes are inline asm: the wait states are ours, tools/check_mfma_hazard.py)
-                        vote_subs(PV_XS, PV_LO(va, vb));
-                        vote_slow_open(acc, dmo, PV_XS);
-                        vote_subs(PV_XS, PV_HI(va, vb));
+                    if (FOLD) {
+                        oc.next(cnt[(t + MH - 1) % MH], flg[(t + MH - 1) % MH], va, vb);
                     } else {
-                        asm volatile("s_nop 11");
+                        asm volatile("s_nop 11");   // (the votes are inline asm: the wait states are ours, tools/check_mfma_hazard.py)
                         __builtin_amdgcn_sched_barrier(0);
                         vote8x(cnt[t], dmn[t], PV_LO(va, vb));
                         vote8x(cnt[t], dmn[t], PV_HI(va, vb));
@@ -332,8 +441,8 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                 const f32x16 va2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t + 1 < MH ? Aa : Na, B[(t + 1) % MH], zero, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (FOLD) {
-                    vote_slow_close(cnt[(t + MH - 1) % MH], flg[(t + MH - 1) % MH], acc, dmo, PV_XS);
-                    vote_subs(PV_XS, PV_LO(va, vb));
+                    oc.close(cnt[(t + MH - 1) % MH], flg[(t + MH - 1) % MH]);
+                    oc.subs_lo(va, vb);
                 } else {
                     vote8x(cnt[t], dmn[t], PV_LO(va, vb));
                 }
@@ -341,8 +450,8 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                 const f32x16 vb2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t + 1 < MH ? Ab : Nb, B[(t + 1) % MH], zero, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (FOLD) {
-                    vote_slow_open(acc, dmo, PV_XS);
-                    vote_subs(PV_XS, PV_HI(va, vb));
+                    oc.open();
+                    oc.subs_hi(va, vb);
                 } else {
                     vote8x(cnt[t], dmn[t], PV_HI(va, vb));
                 }
@@ -354,50 +463,23 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
             Ab = Nb;
         }
         }
-        if (FOLD) vote_slow_close(cnt[MH - 1], flg[MH - 1], acc, dmo, PV_XS);   // the last step's second half
-#undef PV_XS
-#undef PV_LO
-#undef PV_HI
-        PV_PHASE(1);
+        if (FOLD) oc.close(cnt[MH - 1], flg[MH - 1]);   // the last step's second half
+        clk.mark(1);
         // ---- clean cells: their counts; flagged cells: into the item's list
-        const unsigned all_groups = 1u;  // FOLD = 0: the one cell of the item
         int lx = lane;   // opaque copy: keeps the eight per-tile addresses below from being hoisted above the scoring loop,
         asm volatile("" : "+v"(lx));   // where they would cost 20 VGPRs at the point of highest pressure (and the half-wave's bit of
         const int colx = lx & 31, halfx = lx >> 5;   // the cell word: hoisted, the merged kernel spilled it)
-        const bool padded = h0 + MH * 32 > P.hn;  // wave-uniform: only the last slice can hold padding columns
-        if (!FOLD) {
-#pragma unroll
-            for (int t = 0; t < MH; ++t) cnt[t] = dmn[t] >= BAND_CLEAN ? cnt[t] : 0u;  // a flagged cell's votes are discarded
-        }
-        if (!RUNS) flush_counts(bk, h0);  // (RUNS: when the run ends)
-        // (round 6: ONE slot reservation per wave and item -- the eight ballots and their popcounts are scalar work, the wave's
-        //  cells go behind one LDS atomic; one reservation per hypothesis tile, most of them taken, cost ~70 vector operations more)
-        unsigned long long bal[MH];
-        int ncw = 0;
-#pragma unroll
-        for (int t = 0; t < MH; ++t) {
-            unsigned mask = FOLD ? flg[t] : (dmn[t] >= BAND_CLEAN ? 0u : all_groups);
-            if (padded && h0 + t * 32 + colx >= P.hn) mask = 0u;  // padding columns of the last slice: nobody reads their counts
-            flg[t] = mask;
-            bal[t] = __ballot(mask != 0u);
-            ncw += (int)__popcll(bal[t]);
-        }
-        if (ncw) {  // wave-uniform
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_ncell, ncw);
-            base = __builtin_amdgcn_readfirstlane(base);
-            const unsigned cell0 = (unsigned)(wave * MH * 32 + colx) | ((unsigned)halfx << 10);
+        if (!FOLD) {   // the one cell of the item: flagged, its votes are discarded
 #pragma unroll
             for (int t = 0; t < MH; ++t) {
-                if (bal[t]) {  // wave-uniform
-                    const int slot = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal[t] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal[t], 0u));
-                    if (flg[t] != 0u) s_cells[slot] = (cell0 + (unsigned)(t * 32)) | (flg[t] << 11);
-                    base += (int)__popcll(bal[t]);
-                }
+                flg[t] = dmn[t] >= BAND_CLEAN ? 0u : 1u;
+                cnt[t] = flg[t] ? 0u : cnt[t];
             }
         }
+        if (!RUNS) flush_counts<MH>(P.counts + it.bk * P.hn_pad + it.h0, cnt);  // (RUNS: when the run ends)
+        list_flagged_cells<MH>(P, flg, it.h0, lane, wave, colx, halfx, s_cells, &s_ncell);
         lds_barrier();
-        PV_PHASE(2);
+        clk.mark(2);
         // ---- flagged cells, decided by the reference's arithmetic: 16 lanes per cell, one pixel row each
         const int ncell = s_ncell;
         if (ncell > 0) {
@@ -413,7 +495,7 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                 const int row = (q >> 2) * 8 + hf * 4 + (q & 3);  // the 16 rows a lane of that half-wave holds
                 int votes = 0;
                 while (m) {
-                    const int g = __ffs((int)m) - 1;  // FOLD: bit g = pixel tile nti - 1 - g (vote8x_close shifts them in)
+                    const int g = __ffs((int)m) - 1;  // FOLD: bit g = pixel tile nti - 1 - g (vote_slow_close shifts them in)
                     m &= m - 1u;
                     const int t0 = FOLD ? nti - 1 - g : 0, t1 = FOLD ? t0 + 1 : nti;
                     for (int tile = t0; tile < t1; ++tile) {
@@ -422,30 +504,17 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                         ++ntests;
                     }
                 }
-                votes += (int)lane_xor((uint32_t)votes, 8);   // (DPP / ds_swizzle: no lane index, no address operand)
-                votes += (int)lane_xor((uint32_t)votes, 4);
-                votes += (int)lane_xor((uint32_t)votes, 2);
-                votes += (int)lane_xor((uint32_t)votes, 1);
-                if (q == 0 && votes > 0) atomicAdd(P.counts + bk * P.hn_pad + hslice + hl, votes);
+                add_cell_votes(P.counts + it.bk * P.hn_pad + it.hslice + hl, votes, q);
             }
-            if (P.flags & PVNET_F_BAND_STATS) {  // development aid: how much was re-evaluated (tools/exact_probe.py)
-                if (tid2 == 0) atomicAdd(P.ctrl + P.b * CTRL_STRIDE + 4, ncell);
-                if (q == 0 && ntests > 0) atomicAdd(P.ctrl + P.b * CTRL_STRIDE + 5, ntests);
-            }
+            add_band_stats(P, tid2, q, ncell, ntests);
         }
     }
-    if (RUNS && run_key >= 0) flush_counts(run_bk, run_h0);
-    if (TIMED && !HEAD) {
-        lds_barrier();
-        PV_PHASE(3);
-        if (threadIdx.x == 0) {
-            stamps[2 * blockIdx.x + 1] = (unsigned long long)wall_clock64();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) stamps[2 * gridDim.x + 4 * blockIdx.x + i] = ph[i];  // (tools/phase_probe.py)
-        }
-    }
-#undef PV_PHASE
+    if (RUNS && run_key >= 0) flush_counts<MH>(P.counts + run_bk * P.hn_pad + run_h0, cnt);
+    if (!HEAD) clk.finish(P);
 }
+#undef PV_XS
+#undef PV_LO
+#undef PV_HI
 
 }  // namespace
 }  // namespace pvd

@@ -36,8 +36,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
     // is left of the SIMD's 512 holds other streams' small stages -- at 144 the six-stream rate fell 2.8 %, r06g), 128 for a batch
     // alone (four waves per SIMD, four workgroups of 40 KB per CU).  What this body keeps across its item loop is made per use where the allocator would otherwise spill it.
     if (WIDE) PVNET_SPARE_VGPRS(135); else PVNET_SPARE_VGPRS(127);
-    unsigned long long* __restrict__ stamps = reinterpret_cast<unsigned long long*>(P.pix);
-    if (TIMED && !TAIL && threadIdx.x == 0) stamps[2 * blockIdx.x] = (unsigned long long)wall_clock64();
+    if (!TAIL) PhaseClock<TIMED>::stamp(P, 0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // (TAIL: an opaque copy of the thread index -- what this body derives from it is worked out here, behind the dense body, instead of
     //  being kept for it in registers the dense body's loop needs: the merged kernel spilled them)
@@ -61,16 +60,9 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
     const uint4* lbase = s_t + half * 32 + col;
     const int ntl = P.hn_pad >> 5;
 
-    unsigned long long ph[4] = {0ull, 0ull, 0ull, 0ull}, tprev = 0ull;
-#define PV_PHASE(i)                                                     \
-    do {                                                                \
-        if (TIMED) {                                                    \
-            const unsigned long long now_ = (unsigned long long)clock64(); \
-            ph[i] += now_ - tprev;                                      \
-            tprev = now_;                                               \
-        }                                                               \
-    } while (0)
-    if (TIMED) tprev = (unsigned long long)clock64();
+    // phases: 0 staging, 1 coarse pass + barrier, 2 fine pass, 3 flush + cell list + re-evaluation + barriers
+    PhaseClock<TIMED> clk;
+    clk.start();
     bf16x8 B[MH];
     bf16x8 Bc = __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u));   // centre column of hypothesis tile `col` of the slice
     float gcol = 0.f;                                                     // its g (0: every live pixel is uncertain)
@@ -79,19 +71,6 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
 #pragma unroll
     for (int t = 0; t < MH; ++t) cnt[t] = 0u;
     unsigned st_steps = 0u, st_full = 0u;   // PVNET_F_BAND_STATS: fine steps executed / steps the exact kernel would execute (this wave)
-    auto flush_counts = [&](size_t fbk, int fh0) {
-        int32_t* const pc = P.cnts + fbk * P.hn_pad + fh0;
-        int lanex = threadIdx.x;
-        asm volatile("" : "+v"(lanex));
-        lanex &= 63;
-#pragma unroll
-        for (int t = 0; t + 1 < MH; t += 2) {  // lanes 0..31 finish tile t, lanes 32..63 tile t + 1
-            const int c = votes_of_norm(half_wave_sum2(cnt[t], cnt[t + 1]));
-            if (c > 0) atomicAdd(pc + t * 32 + lanex, c);
-        }
-#pragma unroll
-        for (int t = 0; t < MH; ++t) cnt[t] = 0u;
-    };
     // Round 6: the record of this thread's pixel of the NEXT item is requested while the current item is scored.  On the fields where
     // culling pays, an item is a chain of waits (descriptor -> pixel count -> record -> barrier -> centres -> lists -> ...), three
     // workgroups per CU deep, not a stream of instructions (profiles/r06d_phase_probe_cull.txt: 13 300 cycles per item on the clean
@@ -103,20 +82,12 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
     for (int item = ir.first; item < ir.end; item += ir.step) {
         const int4 desc = P.items[item];
         if (!item_culled(desc.y)) continue;   // (workgroup-uniform) a key-point the full exact kernel scores
-        const int bi = desc.x, k = item_kp(desc.y), cg = desc.z, hq = desc.w;
-        const int tn = ctrl[bi * CTRL_STRIDE + C_TN];
-        const float rho = __uint_as_float((unsigned)ctrl[bi * CTRL_STRIDE + C_RHO]);   // band_rho(tn), from the plan block of K3
-        const size_t bk = (size_t)bi * P.vn + k;
-        const int32_t* const org = band_origin_ptr(P, bk);
-        const float ox = (float)org[0], oy = (float)org[1];
-        const int tpad = (tn + PAD - 1) / PAD * PAD;
-        const int hslice = hq * 4 * MH * 32;
-        const int h0 = hslice + wave * MH * 32;
+        const ItemHeader<MH> it(P, ctrl, desc, wave);
         // (the counters hold < 65536 votes per half: per item and lane pair at most 16 fine votes per group (8 groups) and the certain
         //  votes of the item's 256 pixels -- 384)
 
         lds_barrier();  // the previous item's tiles, lists and cells have been consumed
-        PV_PHASE(3);
+        clk.mark(3);
         if (threadIdx.x == 0) s_ncell = 0;
         if (threadIdx.x < 64) s_nu[threadIdx.x] = 0;   // s_nu and s_cv
         int tid = threadIdx.x;
@@ -125,23 +96,23 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             const int c2 = tid & 31, h2 = (tid >> 5) & 1;
 #pragma unroll
             for (int t = 0; t < MH; ++t) {
-                const uint4 raw = P.hypb[(bk * P.hn_pad + h0 + t * 32 + c2) * 2 + h2];
+                const uint4 raw = P.hypb[(it.bk * P.hn_pad + it.h0 + t * 32 + c2) * 2 + h2];
                 B[t] = __builtin_bit_cast(bf16x8, raw);
             }
-            Bc = __builtin_bit_cast(bf16x8, P.hypc[(bk * ntl + hq * 32 + c2) * 2 + h2]);
-            gcol = P.hypg[bk * ntl + hq * 32 + c2];
-            tile_live = hslice + c2 * 32 < P.hn;
+            Bc = __builtin_bit_cast(bf16x8, P.hypc[(it.bk * ntl + it.hq * 32 + c2) * 2 + h2]);
+            gcol = P.hypg[it.bk * ntl + it.hq * 32 + c2];
+            tile_live = it.hslice + c2 * 32 < P.hn;
         }
         {   // thread = pixel: its A rows, its raw record, its 1 - mu
             const int i = tid;
-            const int p = cg * CULL_NPX + i;
+            const int p = it.cg * CULL_NPX + i;
             float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
             if (next_item == item) q = q_next;   // (workgroup-uniform) requested during the previous item
-            else if (p < tpad) q = P.rec[bk * P.cap + p];
+            else if (p < it.tpad) q = P.rec[it.bk * P.cap + p];
             uint4* t = s_t + (i >> 5) * TILE_U4 + (i & 31);
             uint4 r0, r1, r2, r3;
             float mu;
-            a_rows_exact(q, P.tau, ox, oy, rho, r0, r1, r2, r3, mu);
+            a_rows_exact(q, P.tau, it.ox, it.oy, it.rho, r0, r1, r2, r3, mu);
             t[0] = r0;
             t[32] = r1;
             t[64] = r2;
@@ -157,7 +128,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             }
         }
         lds_barrier();
-        PV_PHASE(0);
+        clk.mark(0);
         // (WIDE only: in 128 VGPRs the four registers did not survive the fine pass -- the record was waited for at once and spilled to
         //  scratch, a prefetch in name only)
         if (WIDE && item + ir.step < ir.end) {   // the next item's record for this thread, if the next item is one of this kernel's
@@ -171,7 +142,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             }
         }
 
-        const int left = (tpad - cg * CULL_NPX + 31) >> 5;
+        const int left = (it.tpad - it.cg * CULL_NPX + 31) >> 5;
         const int nti = left < 8 ? left : 8;
         // ---- coarse pass: this wave's two pixel tiles against the 32 tile centres (both MFMA pairs issued before either is consumed)
         f32x16 cvd[2], cvc[2];
@@ -226,7 +197,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             }
         }
         lds_barrier();
-        PV_PHASE(1);   // (TIMED, this kernel: 0 staging, 1 coarse pass + barrier, 2 fine pass, 3 flush + cell list + re-evaluation + barriers)
+        clk.mark(1);
         // ---- fine pass: the uncertain pixels of each of this wave's eight hypothesis tiles, gathered into groups of 32
         // the wave's eight list lengths and certain-vote counts in four 16-byte reads (one wait) -- read one by one, each behind the
         // store before it, they were a chain of sixteen LDS round trips per item: 3 600 cycles with nothing to score (r06d)
@@ -244,11 +215,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             }
         }
         unsigned flg[MH];   // bit (groups - 1 - g) set = gathered group g of tile t holds a test inside the band
-        float x0, x1, x2, x3, x4, x5, x6, x7, dmo;
-        unsigned acc;
-#define PV_XS x0, x1, x2, x3, x4, x5, x6, x7
-#define PV_LO(v, w) v[0], w[0], v[1], w[1], v[2], w[2], v[3], w[3], v[4], w[4], v[5], w[5], v[6], w[6], v[7], w[7]
-#define PV_HI(v, w) v[8], w[8], v[9], w[9], v[10], w[10], v[11], w[11], v[12], w[12], v[13], w[13], v[14], w[14], v[15], w[15]
+        OpenCell oc;   // (every chain opens with first(): nothing to initialise)
 #pragma unroll
         for (int t = 0; t < MH; ++t) {
             flg[t] = 0u;
@@ -257,7 +224,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
             const int ng = (nu + 31) >> 5;
             if (TIMED || (P.flags & PVNET_F_BAND_STATS)) {
                 st_steps += (unsigned)ng;
-                st_full += (h0 + t * 32 < P.hn) ? (unsigned)nti : 0u;
+                st_full += (it.h0 + t * 32 < P.hn) ? (unsigned)nti : 0u;
             }
             if (ng > 0) {   // wave-uniform
                 // Software pipeline over the tile's gathered groups: a group's A rows are requested one trip ahead (list entry -> row
@@ -281,10 +248,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
                     Rb = s_t[an + half * 32 + 64];
                     an = row_of(ng > 2 ? 2 : ng - 1);
                     __builtin_amdgcn_sched_barrier(0);
-                    asm volatile("s_nop 11");   // (the votes are inline asm: the wait states are ours, tools/check_mfma_hazard.py)
-                    vote_subs(PV_XS, PV_LO(va, vb));
-                    vote_slow_open(acc, dmo, PV_XS);
-                    vote_subs(PV_XS, PV_HI(va, vb));
+                    oc.first(va, vb);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 for (int g = 1; g < ng; ++g) {
@@ -294,47 +258,18 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
                     Rb = s_t[an + half * 32 + 64];
                     an = row_of(g + 2 < ng ? g + 2 : ng - 1);
                     __builtin_amdgcn_sched_barrier(0);
-                    vote_slow_close(cnt[t], flg[t], acc, dmo, PV_XS);   // the previous group's last 15 operations fill the wait
-                    asm volatile("s_nop 3");
-                    vote_subs(PV_XS, PV_LO(va, vb));
-                    vote_slow_open(acc, dmo, PV_XS);
-                    vote_subs(PV_XS, PV_HI(va, vb));
+                    oc.next(cnt[t], flg[t], va, vb);   // the previous group's last 15 operations fill the wait
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                vote_slow_close(cnt[t], flg[t], acc, dmo, PV_XS);
+                oc.close(cnt[t], flg[t]);
             }
         }
-#undef PV_XS
-#undef PV_LO
-#undef PV_HI
-        PV_PHASE(2);
+        clk.mark(2);
         int lx = lane;
         asm volatile("" : "+v"(lx));
         const int colx = lx & 31, halfx = lx >> 5;
-        const bool padded = h0 + MH * 32 > P.hn;
-        flush_counts(bk, h0);
-        unsigned long long bal[MH];   // (one slot reservation per wave and item, as in the dense body)
-        int ncw = 0;
-#pragma unroll
-        for (int t = 0; t < MH; ++t) {
-            if (padded && h0 + t * 32 + colx >= P.hn) flg[t] = 0u;   // padding columns: nobody reads their counts
-            bal[t] = __ballot(flg[t] != 0u);
-            ncw += (int)__popcll(bal[t]);
-        }
-        if (ncw) {  // wave-uniform
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_ncell, ncw);
-            base = __builtin_amdgcn_readfirstlane(base);
-            const unsigned cell0 = (unsigned)(wave * MH * 32 + colx) | ((unsigned)halfx << 10);
-#pragma unroll
-            for (int t = 0; t < MH; ++t) {
-                if (bal[t]) {  // wave-uniform
-                    const int slot = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal[t] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal[t], 0u));
-                    if (flg[t] != 0u) s_cells[slot] = (cell0 + (unsigned)(t * 32)) | (flg[t] << 11);
-                    base += (int)__popcll(bal[t]);
-                }
-            }
-        }
+        flush_counts<MH>(P.cnts + it.bk * P.hn_pad + it.h0, cnt);
+        list_flagged_cells<MH>(P, flg, it.h0, lane, wave, colx, halfx, s_cells, &s_ncell);
         lds_barrier();
         // ---- flagged cells, decided by the reference's arithmetic: 16 lanes per cell, one gathered pixel each
         const int ncell = s_ncell;
@@ -347,7 +282,7 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
                 const unsigned cell = s_cells[e];
                 const int hl = (int)(cell & 1023u), hf = (int)((cell >> 10) & 1u);
                 unsigned m = cell >> 11;
-                const float2 hv = P.hyps[bk * P.hn_pad + hslice + hl];
+                const float2 hv = P.hyps[it.bk * P.hn_pad + it.hslice + hl];
                 const int j = hl >> 5;
                 const int nu = s_nu[j], ng = (nu + 31) >> 5;
                 const int row = (q >> 2) * 8 + hf * 4 + (q & 3);  // the 16 rows a lane of that half-wave holds
@@ -357,38 +292,22 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
                     m &= m - 1u;
                     const int slot = (ng - 1 - gb) * 32 + row;
                     if (slot < nu) {   // (beyond: the dead row)
-                        const int px = cg * CULL_NPX + (int)s_list[j * CULL_NPX + slot];   // < tpad: rows beyond it are zero rows, never uncertain
-                        const float4 r = P.rec[bk * P.cap + px];
+                        const int px = it.cg * CULL_NPX + (int)s_list[j * CULL_NPX + slot];   // < tpad: rows beyond it are zero rows, never uncertain
+                        const float4 r = P.rec[it.bk * P.cap + px];
                         votes += inlier_literal(r.x, r.y, r.z, r.w, hv.x, hv.y, P.thresh) ? 1 : 0;
                         ++ntests;
                     }
                 }
-                votes += (int)lane_xor((uint32_t)votes, 8);   // (DPP / ds_swizzle: no lane index, no address operand -- __shfl_xor's was
-                votes += (int)lane_xor((uint32_t)votes, 4);   //  kept in a register across the whole item loop)
-                votes += (int)lane_xor((uint32_t)votes, 2);
-                votes += (int)lane_xor((uint32_t)votes, 1);
-                if (q == 0 && votes > 0) atomicAdd(P.cnts + bk * P.hn_pad + hslice + hl, votes);
+                add_cell_votes(P.cnts + it.bk * P.hn_pad + it.hslice + hl, votes, q);
             }
-            if (P.flags & PVNET_F_BAND_STATS) {
-                if (tid2 == 0) atomicAdd(P.ctrl + P.b * CTRL_STRIDE + 4, ncell);
-                if (q == 0 && ntests > 0) atomicAdd(P.ctrl + P.b * CTRL_STRIDE + 5, ntests);
-            }
+            add_band_stats(P, tid2, q, ncell, ntests);
         }
     }
     if ((P.flags & PVNET_F_BAND_STATS) && lane == 0) {   // development aid: how much of the exact kernel's work was left
         atomicAdd(P.ctrl + P.b * CTRL_STRIDE + 1, (int)st_steps);
         atomicAdd(P.ctrl + P.b * CTRL_STRIDE + 7, (int)st_full);
     }
-    if (TIMED) {
-        lds_barrier();
-        PV_PHASE(3);
-        if (threadIdx.x == 0) {
-            stamps[2 * blockIdx.x + 1] = (unsigned long long)wall_clock64();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) stamps[2 * gridDim.x + 4 * blockIdx.x + i] = ph[i];
-        }
-    }
-#undef PV_PHASE
+    clk.finish(P);
 }
 // ONE launch for a call whose key-points K3 may split between the two scoring forms (P.cull = 2, the default where the layout supports
 // culling): every workgroup walks its work items twice -- the dense ones with the exact kernel's body, then the disc-culled ones.  A
@@ -402,7 +321,8 @@ __device__ __forceinline__ void score_cull_body(VoteParams P) {
         score_exact_body<8, 1, TIMED_ != 0, 1, RUNS_ != 0, true>(P);                                                      \
         if (any_culled || TIMED_) score_cull_body<TIMED_ != 0, true, RUNS_ != 0>(P);   /* (TIMED: the closing stamps) */  \
     }
-PV_DEF_SCORE_BOTH(0, 0, 120) PV_DEF_SCORE_BOTH(1, 0, 120) PV_DEF_SCORE_BOTH(0, 1, 128) PV_DEF_SCORE_BOTH(1, 1, 128)
+#define PV_SCORE_BOTH_SET(X) X(0, 0, 120) X(1, 0, 120) X(0, 1, 128) X(1, 1, 128)   // (TIMED, RUNS, the register budget)
+PV_SCORE_BOTH_SET(PV_DEF_SCORE_BOTH)
 #undef PV_DEF_SCORE_BOTH
 constexpr size_t CULL_LDS_BYTES = 9 * TILE_U4 * sizeof(uint4) + 4 * 8 * 64 * sizeof(unsigned) +
                                   32 * CULL_NPX * sizeof(uint8_t) + CULL_NPX * sizeof(float) + 64 * sizeof(int);
@@ -417,15 +337,14 @@ static_assert(4 * (BOTH_LDS_BYTES + 64) <= 160 * 1024, "four workgroups of the m
 }  // namespace
 
 int launch_score_both(const VoteParams& P, dim3 g, hipStream_t s, bool timed, bool runs) {
-    const dim3 t(256);
-    if (timed) {
-        if (runs) hipLaunchKernelGGL(score_exact_kernel_both_1_1, g, t, BOTH_LDS_BYTES, s, P);
-        else hipLaunchKernelGGL(score_exact_kernel_both_1_0, g, t, BOTH_LDS_BYTES, s, P);
-    } else {
-        if (runs) hipLaunchKernelGGL(score_exact_kernel_both_0_1, g, t, BOTH_LDS_BYTES, s, P);
-        else hipLaunchKernelGGL(score_exact_kernel_both_0_0, g, t, BOTH_LDS_BYTES, s, P);
+#define PV_TRY_SCORE_BOTH(TIMED_, RUNS_, NVGPR_)                                                                          \
+    if (timed == (TIMED_ != 0) && runs == (RUNS_ != 0)) {                                                                 \
+        hipLaunchKernelGGL(score_exact_kernel_both_##TIMED_##_##RUNS_, g, dim3(256), BOTH_LDS_BYTES, s, P);               \
+        return 0;                                                                                                         \
     }
-    return 0;
+    PV_SCORE_BOTH_SET(PV_TRY_SCORE_BOTH)
+#undef PV_TRY_SCORE_BOTH
+    return PVNET_E_UNSUPPORTED;   // (not reached: the set holds all four combinations)
 }
 
 }  // namespace pvd

@@ -46,7 +46,9 @@
 //   vote_common.h        parameter block, workspace conventions, the reference's arithmetic, bf16x3 operands, the rounding band
 //   k1_mask.hip          K1    k2_compact.hip  K2    k3_hypotheses.hip  K3 (+ plan, band origin, culling selection, sort)
 //   k4_score_valu.hip    K4 literal mode       k4_score_mfma.hip  K4 approximate mode
-//   k4_exact_body.h / k4_score_exact.hip   K4 exact mode, dense        k4_score_cull.hip  K4 exact mode, dense + disc-culled items in one launch
+//   k4_exact_body.h      K4 exact mode: the vote epilogue, the pieces both bodies share (OpenCell, PhaseClock, ItemHeader, flush_counts,
+//                        list_flagged_cells, add_cell_votes, add_band_stats) and the dense body
+//   k4_score_exact.hip   K4 exact mode, the dense kernels       k4_score_cull.hip  K4 exact mode, the culling body + dense and disc-culled items in one launch
 //   k5_refine.hip        K5    epilogues.hip   confidence / distribution / motion voting / the four ops / band margin + their C entries
 //   vote_host.hip        this file: rounding-band constant, tuning, layout, parameter block, the scoring-launch plan (plan_score), the
 //                        launch sequence, the C ABI of the layer (its four voting entries share PV_V3_PROLOGUE)
@@ -82,13 +84,12 @@ float band_constant(float thresh) {
     const double k_fast = u * (1.0 + tau) * (1.43 * 10.0 + 8.0);
     return (float)(k_lit + k_fast);
 }
-// cell size of the exact mode: one pixel tile (16 tests per lane; vote8x_open / vote8x_close, 40 VALU operations per step)
+// cell size of the exact mode: one pixel tile (16 tests per lane; vote_slow_open / vote_slow_close, 40 VALU operations per step)
 // by default; PVNET_EXACT_FOLD=0 selects one cell per work item (36 operations per step, but a flagged cell re-evaluates
 // 16 x tiles tests).  Measured at the benchmark shape (tools/exact_probe.py, profiles/r03_exact_probe.txt), item / tile
 // cells: thresh 0.9 -- 135 / 137 us; 0.99 -- 169 / 158 us; 0.999 -- 313 / 184 us (the threshold angle, 2.6 degrees, sits
 // inside the field's noise there: 6e-4 of the tests are re-evaluated); approximate mode on the same box: 90-102 us.
-int band_fold1(int forced, float thresh) {
-    (void)thresh;
+int band_fold1(int forced) {
     return forced == 0 ? 0 : 1;
 }
 
@@ -280,7 +281,7 @@ int fill_params(VoteParams& P, const void* mask, int mask_dtype, const int64_t* 
     if (!(flags & (PVNET_F_LITERAL | PVNET_F_APPROX)) && !L.reserved_) flags |= PVNET_F_LITERAL;
     P.exact = (!(flags & (PVNET_F_LITERAL | PVNET_F_APPROX)) && L.reserved_) ? 1 : 0;
     P.kband = P.exact ? band_constant(thresh) : 0.f;
-    P.fold1 = P.exact ? band_fold1(tuning().exact_fold, thresh) : 0;
+    P.fold1 = P.exact ? band_fold1(tuning().exact_fold) : 0;
     //  cells of one pixel tile list a flagged (hypothesis, half-wave) as a tile mask above 11 index bits: 21 tiles;
     // work items of more tiles (PVNET_SCORE_CHUNK 192 ... 480) use the cell = work item form, which has no such limit
     if (P.exact && P.fold1 && (L.wg_s * L.chunk) / 32 > 21) P.fold1 = 0;
