@@ -1,7 +1,8 @@
 """The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h), of libpvnet_head.so
 (include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``), of libpvnet_train.so (include/pvnet_train.h:
 ``TRAIN_PROTOTYPES``, ``load_train_library``), of libpvnet_targets.so (include/pvnet_targets.h: ``TARGETS_PROTOTYPES``,
-``load_targets_library``) and of libpvnet_augment.so (include/pvnet_augment.h: ``AUGMENT_PROTOTYPES``, ``load_augment_library``).
+``load_targets_library``), of libpvnet_augment.so (include/pvnet_augment.h: ``AUGMENT_PROTOTYPES``, ``load_augment_library``) and of
+libpvnet_color.so (include/pvnet_color.h: ``COLOR_PROTOTYPES``, ``load_color_library``).
 
 Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
 and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
@@ -169,12 +170,36 @@ AUGMENT_PROTOTYPES = {
     "pvnet_normalize": (_int, [_ptr, _i64p, _int, _int, _int, _cfgp, _ptr, _int, _ptr]),
 }
 
+# ---- libpvnet_color.so (include/pvnet_color.h): the colour jitter, alone or fused behind the augmentation; it takes the MASK_* codes,
+# the AUGMENT_OUT_* codes, AugmentConfigStruct and E_* above ---------------------------------------------------------------------------
+COLOR_LIB_PATH = os.path.join(_HERE, "libpvnet_color.so")
+COLOR_ABI_VERSION = 1
+COLOR_UNIFORMS = 5
+COLOR_STEP_B, COLOR_STEP_C, COLOR_STEP_S, COLOR_STEP_H = 0, 1, 2, 3
+
+
+class ColorConfigStruct(C.Structure):
+    """ctypes image of ``PvnetColorConfig`` (include/pvnet_color.h)."""
+    _fields_ = [(n, C.c_double) for n in ("brightness", "contrast", "saturation", "hue")] + [("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
+_ccfgp = C.POINTER(ColorConfigStruct)
+COLOR_PROTOTYPES = {
+    "pvnet_color_abi_version": (_int, []),
+    "pvnet_color_workspace_bytes": (_size, [_int] * 3),
+    # rgb + strides, uniforms, b, h, w, cfg, mask + dtype + strides, maskmul, image + dtype, workspace + bytes, stream
+    "pvnet_color_jitter": (_int, [_ptr, _i64p, _ptr, _int, _int, _int, _ccfgp, _ptr, _int, _i64p, _ptr, _ptr, _int, _ptr, _size, _ptr]),
+    # pvnet_augment's arguments through seed, then jitter, jitter_uniforms, then pvnet_augment's from image on
+    "pvnet_augment_jitter": (_int, AUGMENT_PROTOTYPES["pvnet_augment"][1][:15] + [_ccfgp, _ptr] + AUGMENT_PROTOTYPES["pvnet_augment"][1][15:]),
+}
+
 _lib = None
 _libs = {}   # path -> loaded library
 _head_lib = None
 _train_lib = None
 _targets_lib = None
 _augment_lib = None
+_color_lib = None
 
 
 def _wanted_library() -> str:
@@ -248,6 +273,12 @@ def load_augment_library() -> C.CDLL:
     """dlopen libpvnet_augment.so (the augmentation of a training batch); loud failure if it has not been built.  There is no CPU
     fallback."""
     return _load_side("augment")
+
+
+def load_color_library() -> C.CDLL:
+    """dlopen libpvnet_color.so (the colour jitter, alone or fused behind the augmentation); loud failure if it has not been built.
+    There is no CPU fallback."""
+    return _load_side("color")
 
 
 def reload_tuning():

@@ -118,27 +118,9 @@ def _check_rgb(rgb):
     return rgb.device, tuple(int(x) for x in rgb.shape[:3])
 
 
-def augment_workspace_bytes(b):
-    """the workspace ``augment_batch`` needs for b images (bytes)"""
-    return int(load_augment_library().pvnet_augment_workspace_bytes(int(b)))
-
-
-def augment_batch(rgb, mask, hcoords, height, width, cfg, uniforms, seed, out_dtype=torch.float32, mask_dtype=torch.uint8, out=None,
-                  workspace=None):
-    """The reference's ``augmentation`` + ``ToTensor`` + ``Normalize`` for a batch, on the current stream, without synchronising.
-
-    :param rgb:      [b,h,w,3] uint8 CUDA tensor, any strides with the channel stride 1
-    :param mask:     [b,h,w] uint8 / int32 / int64, any strides
-    :param hcoords:  [b,vn,3] float64
-    :param cfg:      ``AugmentConfig``
-    :param uniforms: ``draw_uniforms(b)`` (host, [b,12]) or ``pack_uniforms(...)`` of it (device, [b,14])
-    :param seed:     of the masked-out rectangle's fill
-    :param out:      None or ``(image, mask, hcoords', status)`` to write into (contiguous, of the shapes and types below)
-    :param workspace: None, or a uint8 CUDA tensor of at least ``augment_workspace_bytes(b)`` bytes
-    :return: ``image [b,3,height,width]`` of ``out_dtype`` (float32 / bfloat16 / float16), normalised; ``mask [b,height,width]`` of
-             ``mask_dtype`` (uint8 / int64); ``hcoords' [b,vn,3]`` float64, what ``HeadLoss.from_keypoints`` takes; ``status [b]``
-             int32 (``AUGMENT_S_*``)
-    """
+def _prepare_augment(rgb, mask, hcoords, height, width, cfg, uniforms, out_dtype, mask_dtype, out):
+    """the argument checks, the packed uniforms and the four outputs of ``augment_batch`` (shared with ``color.augment_jitter_batch``)
+    -> ``dev, (b, h, w), vn, hcoords (contiguous), packed uniforms, (image, mask, hcoords', status)``"""
     dev, (b, h, w) = _check_rgb(rgb)
     height, width = int(height), int(width)
     if not isinstance(cfg, AugmentConfig):
@@ -176,7 +158,33 @@ def augment_batch(rgb, mask, hcoords, height, width, cfg, uniforms, seed, out_dt
         for k, (t, (s, dt)) in enumerate(zip(out, shapes)):
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.shape == s and t.is_contiguous()):
                 raise RuntimeError(f"out[{k}] must be a contiguous {dt} CUDA tensor of shape {tuple(s)} on {dev}")
-    image, mask_o, hc_o, status = out
+    return dev, (b, h, w), vn, hc, packed, out
+
+
+def augment_workspace_bytes(b):
+    """the workspace ``augment_batch`` needs for b images (bytes)"""
+    return int(load_augment_library().pvnet_augment_workspace_bytes(int(b)))
+
+
+def augment_batch(rgb, mask, hcoords, height, width, cfg, uniforms, seed, out_dtype=torch.float32, mask_dtype=torch.uint8, out=None,
+                  workspace=None):
+    """The reference's ``augmentation`` + ``ToTensor`` + ``Normalize`` for a batch, on the current stream, without synchronising.
+
+    :param rgb:      [b,h,w,3] uint8 CUDA tensor, any strides with the channel stride 1
+    :param mask:     [b,h,w] uint8 / int32 / int64, any strides
+    :param hcoords:  [b,vn,3] float64
+    :param cfg:      ``AugmentConfig``
+    :param uniforms: ``draw_uniforms(b)`` (host, [b,12]) or ``pack_uniforms(...)`` of it (device, [b,14])
+    :param seed:     of the masked-out rectangle's fill
+    :param out:      None or ``(image, mask, hcoords', status)`` to write into (contiguous, of the shapes and types below)
+    :param workspace: None, or a uint8 CUDA tensor of at least ``augment_workspace_bytes(b)`` bytes
+    :return: ``image [b,3,height,width]`` of ``out_dtype`` (float32 / bfloat16 / float16), normalised; ``mask [b,height,width]`` of
+             ``mask_dtype`` (uint8 / int64); ``hcoords' [b,vn,3]`` float64, what ``HeadLoss.from_keypoints`` takes; ``status [b]``
+             int32 (``AUGMENT_S_*``)
+    """
+    height, width = int(height), int(width)
+    dev, (b, h, w), vn, hc, packed, (image, mask_o, hc_o, status) = _prepare_augment(rgb, mask, hcoords, height, width, cfg, uniforms,
+                                                                                   out_dtype, mask_dtype, out)
     lib = load_augment_library()
     nbytes = lib.pvnet_augment_workspace_bytes(b)
     if workspace is None:

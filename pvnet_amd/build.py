@@ -1,6 +1,7 @@
 """Builds libpvnet_vote.so (the C-ABI HIP library), libpvnet_head.so (the head metrics, a library of its own), libpvnet_train.so
-(the head losses' backward, likewise), libpvnet_targets.so (the targets from key-points and the head fused with them, likewise) and
-libpvnet_augment.so (the augmentation of a training batch, likewise) in-tree for gfx950 with hipcc.
+(the head losses' backward, likewise), libpvnet_targets.so (the targets from key-points and the head fused with them, likewise),
+libpvnet_augment.so (the augmentation of a training batch, likewise) and libpvnet_color.so (the colour jitter, alone or fused behind
+that augmentation, likewise) in-tree for gfx950 with hipcc.
 
     python -m pvnet_amd.build            # build if sources are newer than the library
     python -m pvnet_amd.build --force
@@ -29,13 +30,20 @@ LIB = os.path.join(HERE, "libpvnet_vote.so")          # release: the knobs are c
 DEV_LIB = os.path.join(HERE, "libpvnet_vote_dev.so")  # -DPVNET_DEV: environment knobs + every kernel variant (knob tests, fuzz, tuning tools)
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
-# the head behind the backbone: three libraries of one translation unit each, beside libpvnet_vote.so, whose ABI stays as it is.
+# the head behind the backbone and the inputs in front of it: libraries of one translation unit each, beside libpvnet_vote.so, whose ABI stays as it is.
 # name -> (translation units, its header under include/ beyond pvnet_head.h, the register checker's option)
 SIDE_LIBRARIES = {
     "head": (["head_metrics.hip"], "pvnet_head.h", "--head"),          # the head metrics of a validation step
     "train": (["head_grad.hip"], "pvnet_train.h", "--train"),          # the backward of the head losses of a training step
     "targets": (["head_targets.hip"], "pvnet_targets.h", "--targets"),  # the targets from key-points, the head fused with them
     "augment": (["augment.hip"], "pvnet_augment.h", "--augment"),       # the inputs of a training step: warp, normalise, key-points
+    "color": (["color_jitter.hip"], "pvnet_color.h", "--color"),        # the colour jitter, alone or fused behind that warp
+}
+# what a library's translation unit includes beyond its own header and the common ones: augment_warp.h is the one copy of the plan and
+# the warp that the augment and the colour library both compile, so both rebuild when it changes
+SIDE_EXTRA_DEPS = {
+    "augment": [os.path.join(CSRC, "augment_warp.h")],
+    "color": [os.path.join(CSRC, "augment_warp.h"), os.path.join(ROOT, "include", "pvnet_augment.h")],
 }
 
 
@@ -44,7 +52,7 @@ def _side(name):
     tu, header, _ = SIDE_LIBRARIES[name]
     src = [os.path.join(CSRC, f) for f in tu]
     deps = src + [os.path.join(CSRC, f) for f in ("head_common.h", "vote_common.h", "pvnet_rng.h")] + \
-        [os.path.join(ROOT, "include", f) for f in sorted({header, "pvnet_head.h", "pvnet_vote.h"})]
+        [os.path.join(ROOT, "include", f) for f in sorted({header, "pvnet_head.h", "pvnet_vote.h"})] + SIDE_EXTRA_DEPS.get(name, [])
     return src, deps, os.path.join(HERE, f"libpvnet_{name}.so")
 
 
@@ -54,6 +62,8 @@ TRAIN_SRC, TRAIN_DEPS, TRAIN_LIB = _side("train")
 TARGETS_SRC, TARGETS_DEPS, TARGETS_LIB = _side("targets")
 AUGMENT_TU = SIDE_LIBRARIES["augment"][0]
 AUGMENT_SRC, AUGMENT_DEPS, AUGMENT_LIB = _side("augment")
+COLOR_TU = SIDE_LIBRARIES["color"][0]
+COLOR_SRC, COLOR_DEPS, COLOR_LIB = _side("color")
 # host-side pose refinement (plain C++, g++): include/pvnet_pnp.h
 PNP_SRC = os.path.join(HERE, "csrc", "pvnet_pnp.cpp")
 PNP_DEPS = [PNP_SRC, os.path.join(ROOT, "include", "pvnet_pnp.h")]
@@ -158,6 +168,10 @@ def build_targets(force: bool = False, verbose: bool = False) -> str:
 
 def build_augment(force: bool = False, verbose: bool = False) -> str:
     return build_side("augment", force, verbose)
+
+
+def build_color(force: bool = False, verbose: bool = False) -> str:
+    return build_side("color", force, verbose)
 
 
 # the reference's compiled extension module `ransac_voting` (src/ransac_voting.cpp) on this library: host-only C++ against
@@ -270,6 +284,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_train(force, verbose)
     build_targets(force, verbose)
     build_augment(force, verbose)
+    build_color(force, verbose)
     build_ext(force, verbose)
     build_canary(force, verbose)
     return LIB
