@@ -10,6 +10,8 @@ import torch
 from pvnet_amd import evaluation as E
 from pvnet_amd import pnp as P
 from pvnet_amd import synth, voting
+from tests import pose_cases
+from tests.pose_cases import problems
 
 pytestmark = pytest.mark.gpu
 
@@ -25,40 +27,9 @@ def dev():
     return torch.device("cuda:0")
 
 
-def problems(n, seed=11, pn=9):
-    """random problems built like tests/test_pnp.py: rotations up to 2.8 rad, 0.4 px noise"""
-    rng = np.random.default_rng(seed)
-    X = rng.uniform(-0.08, 0.08, size=(pn, 3))
-    x2, poses = [], []
-    for _ in range(n):
-        r = rng.normal(size=3)
-        r *= rng.uniform(0.1, 2.8) / np.linalg.norm(r)
-        pose = np.concatenate([P.rodrigues(r), np.array([[rng.uniform(-0.2, 0.2)], [rng.uniform(-0.2, 0.2)],
-                                                         [rng.uniform(0.5, 1.5)]])], 1)
-        poses.append(pose)
-        x2.append(P.project(X, pose, P.LINEMOD_K) + rng.normal(size=(pn, 2)) * 0.4)
-    return X, np.stack(x2), np.stack(poses)
-
-
 def host_solve(X, x2, K, W=None):
     """pvnet_pnp_solve image by image: (poses [n,3,4] as pnp_batch gives them, status [n] = its return values)"""
-    lib = P.load_pnp_library()
-    n = x2.shape[0]
-    rt = np.zeros((n, 6))
-    status = np.zeros(n, np.int32)
-    X = np.ascontiguousarray(X, np.float64)
-    for i in range(n):
-        Ki = np.ascontiguousarray(K[i] if K.ndim == 3 else K, np.float64)
-        xi = np.ascontiguousarray(x2[i], np.float64)
-        Wi = None if W is None else np.ascontiguousarray(W[i], np.float64)
-        out = np.zeros(6)
-        status[i] = lib.pvnet_pnp_solve(P._dptr(xi), P._dptr(X), None if Wi is None else P._dptr(Wi), P._dptr(Ki),
-                                        P._dptr(out), X.shape[0])
-        if status[i] >= 0:
-            rt[i] = out
-    poses = np.empty((n, 3, 4))
-    lib.pvnet_pnp_poses_from_rt(P._dptr(rt), P._dptr(poses), n)
-    return poses, status
+    return pose_cases.host_solve(X, x2, K, W)[:2]
 
 
 def device(X, x2, K, **kw):
