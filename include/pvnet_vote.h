@@ -122,7 +122,8 @@ typedef struct PvnetVoteLayout {
     size_t off_counts;      /* int32  [b][vn][hn_pad]      inlier count of every hypothesis                 */
     size_t off_win;         /* int32  [b][vn][2]           (winner index, winner count)                     */
     size_t off_seg;         /* int32  [2][b][nseg]         ([1] = foreground count of every 4096-pixel segment), then,
-                             *                              if max_num < h*w, uint16 [b][nseg][1024] cumulative histograms   */
+                             *                              if max_num < h*w, uint16 [b][nseg][1536] cumulative histograms of the
+                             *                              thinning bins (THIN_BINS of vote_common.h: pvnet_thin_bin's 1424, padded) */
     size_t off_items;       /* int32x4 [max items]         scoring work items (image, kp, chunk group, slice) */
     size_t off_hypb;        /* uint4  [b][vn][hn_pad][2]   fast mode: hypotheses as bf16x3 MFMA B operands         */
     size_t total_bytes;
@@ -183,6 +184,22 @@ int pvnet_vote_v3_logits(const float* seg_pred, const int64_t seg_strides[4], in
                          uint64_t seed, int image_base, const int32_t* idxs, uint32_t flags,
                          float* out_kpts, int32_t* out_status,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* The layer from its second kernel on, over a workspace whose mask-kernel products the CALLER filled: `bits` (off_bits), the segment
+ * counts (the second array behind off_seg) and, where max_num < h*w, the cumulative thinning histograms behind them, for b images.
+ * The same launch sequence as pvnet_vote_v3 without its first launch, the same arguments without the mask.  Image i gathers its
+ * vectors from vertex[i / src_div]; everything else -- pixel lists, records, hypotheses, counts, the RNG streams image_base + i,
+ * idxs, out_kpts [b,vn,2], out_status [b,vn] -- is indexed by i.  With src_div = num_classes - 1 and a workspace filled by
+ * pvnet_class_split of include/pvnet_classes.h (libpvnet_classes.so) the b = images * src_div "virtual images" are the classes of
+ * a label mask: the reference's ransac_voting_layer_v2 (ransac_voting_gpu.py:99-215), with the result pvnet_vote_v3 gives for the
+ * masks `labels[i / src_div] == i % src_div + 1` and the field of every image repeated src_div times.  The epilogues below work on
+ * that workspace per virtual image.  PVNET_E_BADARG when src_div < 1 or b is no multiple of it; otherwise as pvnet_vote_v3. */
+int pvnet_vote_v3_prepared(const float* vertex, const int64_t vertex_strides[5],
+                           int b, int src_div, int h, int w, int vn, int hn,
+                           float inlier_thresh, int min_num, int max_num,
+                           uint64_t seed, int image_base, const int32_t* idxs, uint32_t flags,
+                           float* out_kpts, int32_t* out_status,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* Same call, timed stage by stage with hipEvents on `stream`; synchronises the stream before returning.
  * stage_ms (host, PVNET_NUM_STAGES floats) receives the GPU time of each stage of this call. bench/profiling only. */

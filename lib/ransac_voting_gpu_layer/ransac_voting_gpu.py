@@ -5,9 +5,9 @@ tools/train_linemod.py:8-9 of zju3dv/pvnet) resolves here when this repository p
 ``sys.path``; like the reference tree there is no ``__init__.py`` (implicit namespace packages), so the rest of
 ``lib.*`` keeps resolving to the reference checkout.
 
-Native (HIP) here: ``ransac_voting_layer_v3`` / ``_v5``, ``estimate_voting_distribution_with_mean``,
+Native (HIP) here: ``ransac_voting_layer_v2`` / ``_v3`` / ``_v5``, ``estimate_voting_distribution_with_mean``,
 ``ransac_motion_voting``, ``generate_hypothesis`` -- the functions the reference's tools call.  Every OTHER name of
-the reference module (``ransac_voting_layer``, ``_v2`` / ``_v4`` / ``_v6``, ``ransac_voting_center``,
+the reference module (``ransac_voting_layer``, ``_v4`` / ``_v6``, ``ransac_voting_center``,
 ``estimate_voting_distribution``, ``ransac_voting_hypothesis``, ``b_inv``, ...) is resolved lazily by the module
 ``__getattr__`` below: the reference's own ``ransac_voting_gpu.py`` is loaded from the reference checkout further
 down ``sys.path`` with its extension import (``ransac_voting``, :2) bound to the HIP ops, so those functions run their
@@ -23,12 +23,12 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from pvnet_amd.voting import (estimate_voting_distribution_with_mean, ransac_motion_voting,  # noqa: E402,F401
-                              ransac_voting_layer_v3, ransac_voting_layer_v5)
+                              ransac_voting_layer_v2, ransac_voting_layer_v3, ransac_voting_layer_v5)
 from pvnet_amd.voting import generate_hypothesis_counts as generate_hypothesis  # noqa: E402,F401  (:983-1034)
 from pvnet_amd import voting as ransac_voting  # noqa: E402,F401  (the op module the reference imports at :2)
 
 
-_NATIVE = ("ransac_voting_layer_v3", "ransac_voting_layer_v5", "estimate_voting_distribution_with_mean",
+_NATIVE = ("ransac_voting_layer_v2", "ransac_voting_layer_v3", "ransac_voting_layer_v5", "estimate_voting_distribution_with_mean",
            "ransac_motion_voting", "generate_hypothesis")
 _upstream = None
 

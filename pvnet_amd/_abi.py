@@ -2,7 +2,8 @@
 (include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``), of libpvnet_train.so (include/pvnet_train.h:
 ``TRAIN_PROTOTYPES``, ``load_train_library``), of libpvnet_targets.so (include/pvnet_targets.h: ``TARGETS_PROTOTYPES``,
 ``load_targets_library``), of libpvnet_augment.so (include/pvnet_augment.h: ``AUGMENT_PROTOTYPES``, ``load_augment_library``) and of
-libpvnet_color.so (include/pvnet_color.h: ``COLOR_PROTOTYPES``, ``load_color_library``).
+libpvnet_color.so (include/pvnet_color.h: ``COLOR_PROTOTYPES``, ``load_color_library``) and of libpvnet_classes.so (include/pvnet_classes.h: ``CLASSES_PROTOTYPES``,
+``load_classes_library``).
 
 Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
 and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
@@ -70,6 +71,8 @@ PROTOTYPES = {
     "pvnet_vote_workspace_bytes": (_size, [_int] * 6),
     "pvnet_vote_v3": (_int, _V3),
     "pvnet_vote_v3_logits": (_int, [_ptr, _i64p, _int, _ptr, _i64p] + _V3[5:]),
+    # pvnet_vote_v3 without its mask part, src_div behind b: the layer from its second kernel on, over a workspace the caller filled
+    "pvnet_vote_v3_prepared": (_int, _V3[3:6] + [_int] + _V3[6:]),
     "pvnet_vote_v3_profiled": (_int, _V3 + [C.POINTER(_f32)]),
     "pvnet_vote_v3_stage_repeat": (_int, _V3 + [_int, _int, C.POINTER(_f32)]),
     "pvnet_vote_band_margin": (_int, [_f32, _ptr] + _WS_TAIL),
@@ -193,8 +196,23 @@ COLOR_PROTOTYPES = {
     "pvnet_augment_jitter": (_int, AUGMENT_PROTOTYPES["pvnet_augment"][1][:15] + [_ccfgp, _ptr] + AUGMENT_PROTOTYPES["pvnet_augment"][1][15:]),
 }
 
+# ---- libpvnet_classes.so (include/pvnet_classes.h): the voting layer's first kernel for a mask of class labels; it takes the MASK_*
+# codes and E_* above and fills the workspace pvnet_vote_v3_prepared runs on ------------------------------------------------------------
+CLASSES_LIB_PATH = os.path.join(_HERE, "libpvnet_classes.so")
+CLASSES_ABI_VERSION = 1
+CLASSES_MAX = 64   # classes including the background
+CLASSES_LOGITS_F32, CLASSES_LOGITS_F16, CLASSES_LOGITS_BF16 = 0, 1, 2
+# source + type + strides, num_classes, b, h, w, max_num, seed, image_base, bits, seg0, cum, stream
+_CLASS_SPLIT = [_ptr, _int, _i64p] + [_int] * 5 + [C.c_uint64, _int, _ptr, _ptr, _ptr, _ptr]
+CLASSES_PROTOTYPES = {
+    "pvnet_classes_abi_version": (_int, []),
+    "pvnet_class_split": (_int, _CLASS_SPLIT),
+    "pvnet_class_split_logits": (_int, _CLASS_SPLIT),
+}
+
 _lib = None
 _libs = {}   # path -> loaded library
+_classes_lib = None
 _head_lib = None
 _train_lib = None
 _targets_lib = None
@@ -279,6 +297,12 @@ def load_color_library() -> C.CDLL:
     """dlopen libpvnet_color.so (the colour jitter, alone or fused behind the augmentation); loud failure if it has not been built.
     There is no CPU fallback."""
     return _load_side("color")
+
+
+def load_classes_library() -> C.CDLL:
+    """dlopen libpvnet_classes.so (class labels -> the bit masks of every class); loud failure if it has not been built.  There is no
+    CPU fallback."""
+    return _load_side("classes")
 
 
 def reload_tuning():

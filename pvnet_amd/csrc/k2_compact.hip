@@ -125,6 +125,7 @@ __global__ __launch_bounds__(256) void compact_kernel(VoteParams P) {
             }
         }
     };
+    const int64_t vimg = (int64_t)(bi / P.src_div) * P.vs0;  // the image's field (scalar; src_div = 1 unless the images are classes of one)
     for (int t0 = threadIdx.x; t0 < T; t0 += 512) {
         const int t1 = t0 + 256;
         const bool has1 = t1 < T;
@@ -133,8 +134,8 @@ __global__ __launch_bounds__(256) void compact_kernel(VoteParams P) {
         if (has1) locate(t1, pos1, p1);
         const int y0 = p0 / P.w, x0 = p0 - y0 * P.w;
         const int y1 = p1 / P.w, x1 = p1 - y1 * P.w;
-        const int64_t v0 = (int64_t)bi * P.vs0 + (int64_t)y0 * P.vs1 + (int64_t)x0 * P.vs2;  // element offsets
-        const int64_t v1 = (int64_t)bi * P.vs0 + (int64_t)y1 * P.vs1 + (int64_t)x1 * P.vs2;
+        const int64_t v0 = vimg + (int64_t)y0 * P.vs1 + (int64_t)x0 * P.vs2;  // element offsets
+        const int64_t v1 = vimg + (int64_t)y1 * P.vs1 + (int64_t)x1 * P.vs2;
         float ux0[K2_KG], uy0[K2_KG], ux1[K2_KG], uy1[K2_KG];
 #pragma unroll
         for (int kk = 0; kk < K2_KG; ++kk) {

@@ -118,6 +118,8 @@ struct VoteParams {
                          // kernel 90 us, r06b; K5 returns them to caller order)
     uint4* hypc;         // [b][vn][hn_pad / 32][2] B column of every 32-hypothesis tile's CENTRE, scaled by 1 / (radius + band)
     float* hypg;         // [b][vn][hn_pad / 32]    g = radius term / (radius term + band term) of the tile (0: every pixel uncertain)
+    int src_div;         // image bi gathers its vectors from field bi / src_div: 1 on every path but pvnet_vote_v3_prepared, whose b images
+                         // are the src_div classes of b / src_div source images (class_split.hip); everything else is indexed by bi
 };
 
 // per-call flags: int32 [8] behind the culling marks.  CF_ANY_CULLED: some image of this call is disc-culled -- zeroed by K2 (the block of

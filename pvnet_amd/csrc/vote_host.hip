@@ -260,6 +260,7 @@ int fill_params(VoteParams& P, const void* mask, int mask_dtype, const int64_t* 
     P.ms_c = 0; P.num_classes = 1;  // only the logits entry point sets these
     P.mask_dtype = mask_dtype;
     P.mask_linear = (ms[2] == 1 && ms[1] == w) ? 1 : 0;
+    P.src_div = 1;  // only pvnet_vote_v3_prepared sets another
     P.vertex = vertex; P.vs0 = vs[0]; P.vs1 = vs[1]; P.vs2 = vs[2]; P.vs3 = vs[3]; P.vs4 = vs[4];
     if ((flags & PVNET_F_VERTEX_F16) && (flags & PVNET_F_VERTEX_BF16)) return PVNET_E_BADARG;
     if ((flags & PVNET_F_LOGITS_F16) && (flags & PVNET_F_LOGITS_BF16)) return PVNET_E_BADARG;
@@ -460,6 +461,18 @@ int pvnet_vote_v3_logits(const float* seg_pred, const int64_t seg_strides[4], in
     P.ms_c = seg_strides[1];
     P.num_classes = num_classes;
     return launch_all(P, s, nullptr);
+}
+
+int pvnet_vote_v3_prepared(const float* vertex, const int64_t vertex_strides[5], int b, int src_div, int h, int w, int vn, int hn,
+                           float inlier_thresh, int min_num, int max_num, uint64_t seed, int image_base, const int32_t* idxs,
+                           uint32_t flags, float* out_kpts, int32_t* out_status, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    if (src_div < 1 || b < 1 || b % src_div != 0) return PVNET_E_BADARG;
+    // the mask kernel's products are in the workspace already: no mask (fill_params wants a pointer, nothing reads it)
+    static const int64_t no_strides[3] = {0, 0, 1};
+    PV_V3_PROLOGUE(workspace, PVNET_MASK_U8, no_strides);
+    P.src_div = src_div;
+    return launch_all(P, s, nullptr, tuning().dev_stages & ~1);   // K2 .. K5
 }
 
 int pvnet_vote_v3_profiled(const void* mask, int mask_dtype, const int64_t mask_strides[3], const float* vertex,

@@ -3,6 +3,8 @@
 Mirrors (same names, argument meaning, defaults and error behaviour):
 
 * ``ransac_voting_layer_v3``  -- lib/ransac_voting_gpu_layer/ransac_voting_gpu.py:514-598
+* ``ransac_voting_layer_v2``  -- :99-215, one vote per class of a label mask (the first kernel: libpvnet_classes.so,
+  pvnet_amd/csrc/class_split.hip, include/pvnet_classes.h)
 * ``generate_hypothesis`` / ``voting_for_hypothesis`` ops -- lib/ransac_voting_gpu_layer/src/ransac_voting.cpp:20-55,
   exported by the pybind module ``ransac_voting`` (:102-107)
 
@@ -22,8 +24,8 @@ import torch
 
 # the C ABI -- library paths, loading, prototypes, PvnetVoteLayout, error codes, the header's constants -- is bound in _abi.py; the names
 # below stay reachable as voting.<name> (bench.py, tools/, the tests)
-from ._abi import (DEV_LIB_PATH, LIB_PATH, TUNING_KNOBS, Layout, _check, _wanted_library, load_library,  # noqa: F401
-                   reload_tuning, vote_layout)
+from ._abi import (CLASSES_MAX, DEV_LIB_PATH, LIB_PATH, TUNING_KNOBS, Layout, _check, _wanted_library, load_classes_library,  # noqa: F401
+                   load_library, reload_tuning, vote_layout)
 from ._abi import (F_APPROX, F_BAND_STATS, F_CONCURRENT, F_CULL_ALL, F_CULL_NONE, F_LITERAL, F_LOGITS_BF16,  # noqa: F401
                    F_LOGITS_F16, F_NO_REFINE, F_VERTEX_BF16, F_VERTEX_F16, MASK_F32, MASK_I16, MASK_I32, MASK_I64, MASK_U8,
                    NUM_STAGES, S_NO_INLIER, S_OVERFLOW, S_SINGULAR, S_SKIPPED, STAGE_NAMES)
@@ -440,6 +442,150 @@ def ransac_voting_layer_v3_from_logits(seg_pred, vertex, round_hyp_num, inlier_t
                       max_num, seed, image_offset, idxs, flags, out, None, ws, L.total_bytes,
                       torch.cuda.current_stream(dev).cuda_stream)), "pvnet_vote_v3_logits")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# one vote per class: a mask of class labels through the layer (ransac_voting_gpu.py:99-215)
+# ---------------------------------------------------------------------------------------------------------
+_CLASS_LOGITS_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # PVNET_CLASSES_LOGITS_*
+
+
+def _vote_per_class(split, src, vertex, class_num, round_hyp_num, inlier_thresh, min_num, max_num, refine_iter_num, idxs, seed,
+                    image_offset, literal, approx, refine, return_status, return_debug, workspace, out):
+    """what ``ransac_voting_layer_v2`` and its logits form share.  ``src`` [b,h,w] (labels) or [b,C,h,w] (logits); ``split(args)`` calls
+    the entry of libpvnet_classes.so that fills the workspace of the B = b (class_num - 1) virtual images -- image i, label k + 1 is
+    virtual image i (class_num - 1) + k -- and ``pvnet_vote_v3_prepared`` runs the layer's other launches on it: two enqueues on the
+    current stream, nothing else."""
+    if int(refine_iter_num) != 1:
+        raise NotImplementedError("refine_iter_num must be 1: the layer refines once, as ransac_voting_layer_v3 does")
+    cn = int(class_num)
+    if not 2 <= cn <= CLASSES_MAX:
+        raise RuntimeError(f"class_num must lie in 2 .. {CLASSES_MAX} (it counts the background), got {cn}")
+    lib, clib = load_library(), load_classes_library()
+    nk = cn - 1
+    b0 = vertex.shape[0] if isinstance(vertex, torch.Tensor) and vertex.dim() == 5 else 0
+    if idxs is not None and idxs.dim() == 5:   # [b, cn-1, hn, vn, 2]: one draw per (image, class)
+        if tuple(idxs.shape[:2]) != (b0, nk):
+            raise RuntimeError(f"idxs must be [b,cn-1,hn,vn,2] with (b, cn-1) = {(b0, nk)}, got {tuple(idxs.shape)}")
+        idxs = idxs.reshape(b0 * nk, *idxs.shape[2:])
+    elif idxs is not None and idxs.dim() == 4:
+        raise RuntimeError("idxs must be [b,cn-1,hn,vn,2] or [hn,vn,2]")
+    fake_mask = src if src.dim() == 3 else src[:, 0]   # shape / device checks
+    _, vertex, b, h, w, vn, hn, max_num, _ = _prepare(fake_mask, vertex, round_hyp_num, max_num, None, convert_mask=False)
+    B = b * nk
+    dev = vertex.device
+    if idxs is not None:
+        if not idxs.is_cuda or idxs.device != dev:
+            raise RuntimeError("idxs must be a CUDA tensor on the inputs' device")
+        if idxs.dim() == 3:
+            idxs = idxs.unsqueeze(0).expand(B, -1, -1, -1)
+        if tuple(idxs.shape) != (B, hn, vn, 2):
+            raise RuntimeError(f"idxs must be [b,cn-1,hn,vn,2]={(b, nk, hn, vn, 2)}, got {tuple(idxs.shape)}")
+        idxs = idxs.to(torch.int32).contiguous()
+    seed = _draw_seed(seed)
+    literal = effective_literal(literal, inlier_thresh)
+    flags = mode_flags(literal, approx, inlier_thresh) | (0 if refine else F_NO_REFINE) | _FIELD_FLAGS[vertex.dtype]
+    L = vote_layout(B, h, w, vn, hn, max_num)
+    with torch.cuda.device(dev):
+        ws = _workspace(workspace, L, dev)
+        if out is None:
+            out = torch.empty((b, nk, vn, 2), dtype=torch.float32, device=dev)
+        elif not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and
+                  tuple(out.shape) == (b, nk, vn, 2)):
+            raise RuntimeError(f"out must be a contiguous float32 CUDA tensor of shape {(b, nk, vn, 2)} on {dev}")
+        status = torch.empty((b, nk, vn), dtype=torch.int32, device=dev) if (return_status or return_debug) else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        # the mask kernel's part of the workspace (PvnetVoteLayout): bit words; the segment counts, second of the two arrays behind
+        # off_seg; the thinning histograms behind both
+        base = ws.data_ptr()
+        seg0 = base + L.off_seg + 4 * B * L.nseg
+        cum = base + L.off_seg + (8 * B * L.nseg + 15) // 16 * 16
+        split(clib, [cn, b, h, w, max_num, C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(image_offset), C.c_void_p(base + L.off_bits),
+                     C.c_void_p(seg0), C.c_void_p(cum), C.c_void_p(stream)])
+        _check(lib.pvnet_vote_v3_prepared(
+            *_v3_args((), vertex, (B, nk, h, w, vn, hn), inlier_thresh, min_num, max_num, seed, image_offset, idxs, flags, out, status,
+                      ws, L.total_bytes, stream)), "pvnet_vote_v3_prepared")
+    extras = []
+    if return_status:
+        extras.append(status)
+    if return_debug:   # v3's dict over the B virtual images: vote_confidence and pvnet_vote_distribution work on it per class
+        d = _debug_views(ws, L)
+        d["literal"] = bool(literal)
+        d["mode"] = "literal" if (literal or (not approx and not L.reserved_)) else ("approx" if approx else "exact")
+        d["concurrent"] = False
+        if not (d["mode"] == "exact" and L.cull):
+            d["cull"] = False
+            d["cull_bits"] = torch.zeros((B, vn), dtype=torch.int32, device=dev)
+        d["status"] = status.view(B, vn)
+        d["seed"] = seed
+        d["workspace"] = ws
+        d["max_num"] = max_num
+        d["class_num"] = cn
+        extras.append(d)
+    return (out, *extras) if extras else out
+
+
+def ransac_voting_layer_v2(mask, vertex, class_num, round_hyp_num, inlier_thresh=0.999, confidence=0.99, max_iter=20, min_num=5,
+                           max_num=30000, refine_iter_num=1, *, idxs: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                           image_offset: int = 0, literal: bool = False, approx: bool = False, refine: bool = True,
+                           return_status: bool = False, return_debug: bool = False, workspace: Optional[torch.Tensor] = None,
+                           out: Optional[torch.Tensor] = None):
+    """Drop-in for the reference's ``ransac_voting_layer_v2`` (ransac_voting_gpu.py:99-215): ``mask`` [b,h,w] holds class LABELS and
+    every class k + 1 = 1 .. class_num - 1 votes on its own pixels ``mask[i] == k + 1`` of the one field ``vertex`` [b,h,w,vn,2].
+    :return: [b, class_num-1, vn, 2] float32; zeros for a class with fewer than ``min_num`` pixels in an image, as the reference.
+
+    Labels are compared on their full integer value (any integer / bool dtype, any strides, read once; a float mask: the value has
+    to equal the label): label 0, negative labels and labels >= ``class_num`` belong to no class.  ``confidence`` and ``max_iter``
+    are accepted and ignored, as in ``ransac_voting_layer_v3``; ``refine_iter_num`` other than 1 raises ``NotImplementedError``.
+
+    THE RESULT IS that of ``ransac_voting_layer_v3`` called once on the materialised batch of B = b (class_num - 1) images -- masks
+    ``mask[i] == k + 1`` in the order (i, k), the field of image i repeated class_num - 1 times -- with the same keyword arguments,
+    bit for bit: a class of an image is a virtual image of the voting library (RNG stream ``image_offset + i (class_num - 1) + k``).
+    One launch (libpvnet_classes.so, pvnet_amd/csrc/class_split.hip) classifies every pixel once and writes one bit mask per class;
+    the compaction gathers a virtual image's vectors from its source image; the rest of the layer never sees the difference.
+
+    Keyword-only arguments as ``ransac_voting_layer_v3``'s; ``idxs`` [b,cn-1,hn,vn,2] (or [hn,vn,2]); ``out`` [b,cn-1,vn,2];
+    ``return_status`` adds the PVNET_S_* bits [b,cn-1,vn]; ``return_debug`` adds v3's debug dict over the B virtual images
+    (``vote_confidence`` and the device part of ``estimate_voting_distribution_with_mean`` take it: [B,vn,...] per class);
+    ``workspace``: >= ``vote_layout(B, h, w, vn, hn, max_num).total_bytes`` bytes.  Two enqueues on the current stream, no host
+    synchronisation: capturable in a graph with a caller-owned workspace."""
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError("mask and vertex must be torch tensors")
+    if not mask.is_cuda:
+        raise RuntimeError("mask must be a CUDA tensor")
+    if mask.dim() != 3:
+        raise RuntimeError(f"mask must be [b,h,w], got {tuple(mask.shape)}")
+    if mask.dtype not in _MASK_CODES:
+        mask = mask.float()   # float16 / bfloat16 / float64 labels: an integer label survives the conversion
+
+    def split(clib, tail):
+        _check(clib.pvnet_class_split(*_mask_part(mask), *tail), "pvnet_class_split")
+
+    return _vote_per_class(split, mask, vertex, class_num, round_hyp_num, inlier_thresh, min_num, max_num, refine_iter_num, idxs, seed,
+                           image_offset, literal, approx, refine, return_status, return_debug, workspace, out)
+
+
+def ransac_voting_layer_v2_from_logits(seg_pred, vertex, round_hyp_num, inlier_thresh=0.999, confidence=0.99, max_iter=20, min_num=5,
+                                       max_num=30000, refine_iter_num=1, *, idxs=None, seed=None, image_offset=0, literal=False,
+                                       approx=False, refine=True, return_status=False, return_debug=False, workspace=None, out=None):
+    """``ransac_voting_layer_v2(torch.argmax(seg_pred, 1), vertex, C, ...)`` for class logits ``seg_pred [b,C,h,w]`` with the arg-max
+    fused into the classifying kernel: float32 / float16 / bfloat16 logits are read in place (any strides) and the int64 label mask
+    never exists.  Same result as the two-step call, ties and NaN logits included (the first maximum wins, a NaN counts as the
+    maximum).  Other dtypes take the two-step call itself."""
+    if not (isinstance(seg_pred, torch.Tensor) and seg_pred.is_cuda and seg_pred.dim() == 4):
+        raise RuntimeError("seg_pred must be a CUDA tensor [b,C,h,w]")
+    kw = dict(idxs=idxs, seed=seed, image_offset=image_offset, literal=literal, approx=approx, refine=refine,
+              return_status=return_status, return_debug=return_debug, workspace=workspace, out=out)
+    if seg_pred.dtype not in _CLASS_LOGITS_CODES:
+        return ransac_voting_layer_v2(torch.argmax(seg_pred, 1), vertex, seg_pred.shape[1], round_hyp_num, inlier_thresh, confidence,
+                                      max_iter, min_num, max_num, refine_iter_num, **kw)
+
+    def split(clib, tail):
+        _check(clib.pvnet_class_split_logits(C.c_void_p(seg_pred.data_ptr()), _CLASS_LOGITS_CODES[seg_pred.dtype], _strides(seg_pred, 4),
+                                             *tail), "pvnet_class_split_logits")
+
+    return _vote_per_class(split, seg_pred, vertex, seg_pred.shape[1], round_hyp_num, inlier_thresh, min_num, max_num, refine_iter_num,
+                           **kw)
 
 
 def _field_view(vertex_pred):
