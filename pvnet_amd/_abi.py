@@ -3,7 +3,7 @@
 ``TRAIN_PROTOTYPES``, ``load_train_library``), of libpvnet_targets.so (include/pvnet_targets.h: ``TARGETS_PROTOTYPES``,
 ``load_targets_library``), of libpvnet_augment.so (include/pvnet_augment.h: ``AUGMENT_PROTOTYPES``, ``load_augment_library``) and of
 libpvnet_color.so (include/pvnet_color.h: ``COLOR_PROTOTYPES``, ``load_color_library``) and of libpvnet_classes.so (include/pvnet_classes.h: ``CLASSES_PROTOTYPES``,
-``load_classes_library``).
+``load_classes_library``) and of libpvnet_raster.so (include/pvnet_raster.h: ``RASTER_PROTOTYPES``, ``load_raster_library``).
 
 Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
 and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
@@ -210,6 +210,24 @@ CLASSES_PROTOTYPES = {
     "pvnet_class_split_logits": (_int, _CLASS_SPLIT),
 }
 
+# ---- libpvnet_raster.so (include/pvnet_raster.h): poses and meshes -> silhouettes and label images; it takes E_* above ---------------
+RASTER_LIB_PATH = os.path.join(_HERE, "libpvnet_raster.so")
+RASTER_ABI_VERSION = 1
+RASTER_LANE_PIXELS = 64      # pixels of a triangle's box a single lane walks; larger boxes take the cooperative path
+RASTER_MAX_INSTANCES, RASTER_MAX_MESHES, RASTER_MAX_IMAGES, RASTER_MAX_SIDE = 768, 64, 65535, 32768
+RASTER_S_NONFINITE, RASTER_S_BEHIND, RASTER_S_BADFACE = 1, 2, 4
+_i32p = C.POINTER(C.c_int32)   # host arrays: offsets, mesh ids, image ids, labels
+RASTER_PROTOTYPES = {
+    "pvnet_raster_abi_version": (_int, []),
+    "pvnet_raster_workspace_bytes": (_size, [_int] * 6),   # q, P, T, b, h, w
+    # tri, n, tn, h, w, mask_out, status_out, workspace + bytes, stream
+    "pvnet_raster_triangles": (_int, [_ptr] + [_int] * 4 + [_ptr, _ptr, _ptr, _size, _ptr]),
+    # vertices, faces, vertex_offset, face_offset (host), M, P, T, q, mesh_id (host), poses, K, k_per_instance, image_id, label (host),
+    # order, b, h, w, out, tri_out, status_out, workspace + bytes, stream
+    "pvnet_render": (_int, [_ptr, _ptr, _i32p, _i32p] + [_int] * 4 + [_i32p, _ptr, _ptr, _int, _i32p, _i32p, _ptr] + [_int] * 3 +
+                     [_ptr, _ptr, _ptr, _ptr, _size, _ptr]),
+}
+
 _lib = None
 _libs = {}   # path -> loaded library
 _classes_lib = None
@@ -218,6 +236,7 @@ _train_lib = None
 _targets_lib = None
 _augment_lib = None
 _color_lib = None
+_raster_lib = None
 
 
 def _wanted_library() -> str:
@@ -303,6 +322,12 @@ def load_classes_library() -> C.CDLL:
     """dlopen libpvnet_classes.so (class labels -> the bit masks of every class); loud failure if it has not been built.  There is no
     CPU fallback."""
     return _load_side("classes")
+
+
+def load_raster_library() -> C.CDLL:
+    """dlopen libpvnet_raster.so (silhouettes and label images of posed meshes); loud failure if it has not been built.  There is no
+    CPU fallback."""
+    return _load_side("raster")
 
 
 def reload_tuning():

@@ -1,7 +1,8 @@
 """Builds libpvnet_vote.so (the C-ABI HIP library), libpvnet_head.so (the head metrics, a library of its own), libpvnet_train.so
 (the head losses' backward, likewise), libpvnet_targets.so (the targets from key-points and the head fused with them, likewise),
 libpvnet_augment.so (the augmentation of a training batch, likewise), libpvnet_color.so (the colour jitter, alone or fused behind
-that augmentation, likewise) and libpvnet_classes.so (class labels to the bit masks of every class, likewise) in-tree for gfx950 with hipcc.
+that augmentation, likewise), libpvnet_classes.so (class labels to the bit masks of every class, likewise) and libpvnet_raster.so
+(silhouettes and label images of posed meshes, likewise) in-tree for gfx950 with hipcc.
 
     python -m pvnet_amd.build            # build if sources are newer than the library
     python -m pvnet_amd.build --force
@@ -39,6 +40,7 @@ SIDE_LIBRARIES = {
     "augment": (["augment.hip"], "pvnet_augment.h", "--augment"),       # the inputs of a training step: warp, normalise, key-points
     "color": (["color_jitter.hip"], "pvnet_color.h", "--color"),        # the colour jitter, alone or fused behind that warp
     "classes": (["class_split.hip"], "pvnet_classes.h", "--classes"),   # class labels -> the bit masks the voting layer runs on
+    "raster": (["raster.hip"], "pvnet_raster.h", "--raster"),           # poses and meshes -> silhouettes and label images
 }
 # what a library's translation unit includes beyond its own header and the common ones: augment_warp.h is the one copy of the plan and
 # the warp that the augment and the colour library both compile, so both rebuild when it changes
@@ -67,6 +69,8 @@ COLOR_TU = SIDE_LIBRARIES["color"][0]
 COLOR_SRC, COLOR_DEPS, COLOR_LIB = _side("color")
 CLASSES_TU = SIDE_LIBRARIES["classes"][0]
 CLASSES_SRC, CLASSES_DEPS, CLASSES_LIB = _side("classes")
+RASTER_TU = SIDE_LIBRARIES["raster"][0]
+RASTER_SRC, RASTER_DEPS, RASTER_LIB = _side("raster")
 # host-side pose refinement (plain C++, g++): include/pvnet_pnp.h
 PNP_SRC = os.path.join(HERE, "csrc", "pvnet_pnp.cpp")
 PNP_DEPS = [PNP_SRC, os.path.join(ROOT, "include", "pvnet_pnp.h")]
@@ -181,6 +185,10 @@ def build_classes(force: bool = False, verbose: bool = False) -> str:
     return build_side("classes", force, verbose)
 
 
+def build_raster(force: bool = False, verbose: bool = False) -> str:
+    return build_side("raster", force, verbose)
+
+
 # the reference's compiled extension module `ransac_voting` (src/ransac_voting.cpp) on this library: host-only C++ against
 # the torch headers, placed where the reference's driver imports it from
 EXT_SRC = os.path.join(HERE, "csrc", "ransac_voting_ext.cpp")
@@ -293,6 +301,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_augment(force, verbose)
     build_color(force, verbose)
     build_classes(force, verbose)
+    build_raster(force, verbose)
     build_ext(force, verbose)
     build_canary(force, verbose)
     return LIB

@@ -1,19 +1,20 @@
 """Build-time check of every kernel's register accounting (the translation units of libpvnet_vote.so, release and development build,
 the one of libpvnet_head.so, the one of libpvnet_train.so, the one of libpvnet_targets.so, the one of libpvnet_augment.so, the one of
-libpvnet_color.so and the one of libpvnet_classes.so).
+libpvnet_color.so, the one of libpvnet_classes.so and the one of libpvnet_raster.so).
 
 Rule: a kernel must not use the last VGPR granule of its allocation -- `.amdhsa_next_free_vgpr` has to exceed the highest
 VGPR an instruction names by at least 8 (PVNET_SPARE_VGPRS in the sources provides the slack).  Background: round 2's
 compaction flake (profiles/r02_compaction_flake_investigation.txt): identical code failed in 98 % of the runs with an
 allocation that was used to the top and never with one granule more.
 
-    python tools/check_kernel_resources.py            # compiles the sources of the seven libraries to assembly (hipcc -S) and checks them
+    python tools/check_kernel_resources.py            # compiles the sources of the eight libraries to assembly (hipcc -S) and checks them
     python tools/check_kernel_resources.py --head     # libpvnet_head.so's translation unit only (its build)
     python tools/check_kernel_resources.py --train    # libpvnet_train.so's translation unit only (its build)
     python tools/check_kernel_resources.py --targets  # libpvnet_targets.so's translation unit only (its build)
     python tools/check_kernel_resources.py --augment  # libpvnet_augment.so's translation unit only (its build)
     python tools/check_kernel_resources.py --color    # libpvnet_color.so's translation unit only (its build)
     python tools/check_kernel_resources.py --classes  # libpvnet_classes.so's translation unit only (its build)
+    python tools/check_kernel_resources.py --raster   # libpvnet_raster.so's translation unit only (its build)
     python tools/check_kernel_resources.py a.s b.s
 
 Second rule: the kernels whose budget is set with `amdgpu_num_vgpr` (hypothesis_kernel, score_exact_kernel_*) rely on
@@ -132,6 +133,10 @@ def classes_assembly():
     return side_assembly("classes")
 
 
+def raster_assembly():
+    return side_assembly("raster")
+
+
 def kernel_code(text):
     """{kernel: (instruction stream, .amdhsa_* descriptor fields)} of one assembly file -- comments and directives stripped, local
     labels (.LBB3_7, .Ltmp12, ...) renamed in order of appearance, so two compilations of one kernel compare equal however the rest of
@@ -179,10 +184,13 @@ def main(argv):
         texts = [t for _, t in color_assembly()]
     elif argv == ["--classes"]:
         texts = [t for _, t in classes_assembly()]
+    elif argv == ["--raster"]:
+        texts = [t for _, t in raster_assembly()]
     else:
         texts = [open(a).read() for a in argv] if argv else \
             [t for _, _, t in assembly()] + [t for _, t in head_assembly()] + [t for _, t in train_assembly()] + \
-            [t for _, t in targets_assembly()] + [t for _, t in augment_assembly()] + [t for _, t in color_assembly()] + [t for _, t in classes_assembly()]
+            [t for _, t in targets_assembly()] + [t for _, t in augment_assembly()] + [t for _, t in color_assembly()] + [t for _, t in classes_assembly()] + \
+            [t for _, t in raster_assembly()]
     bad = 0
     n = 0
     done = set()
