@@ -1,9 +1,6 @@
-"""The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h), of libpvnet_head.so
-(include/pvnet_head.h: ``HEAD_PROTOTYPES``, ``load_head_library``), of libpvnet_train.so (include/pvnet_train.h:
-``TRAIN_PROTOTYPES``, ``load_train_library``), of libpvnet_targets.so (include/pvnet_targets.h: ``TARGETS_PROTOTYPES``,
-``load_targets_library``), of libpvnet_augment.so (include/pvnet_augment.h: ``AUGMENT_PROTOTYPES``, ``load_augment_library``) and of
-libpvnet_color.so (include/pvnet_color.h: ``COLOR_PROTOTYPES``, ``load_color_library``) and of libpvnet_classes.so (include/pvnet_classes.h: ``CLASSES_PROTOTYPES``,
-``load_classes_library``) and of libpvnet_raster.so (include/pvnet_raster.h: ``RASTER_PROTOTYPES``, ``load_raster_library``).
+"""The one ctypes binding of libpvnet_vote.so (C ABI: include/pvnet_vote.h, include/pvnet_nn.h) and of the side libraries beside it, each
+with a header, a prototype table and an ABI version of its own: ``SIDE_LIBRARIES`` has one row per library (name -> path, version,
+table; ``pvnet_amd.build.SIDE_LIBRARIES`` holds the same names' build facts) and ``load_<name>_library()`` loads one.
 
 Owns what the Python front end mirrors of that ABI, each stated once: the library paths and the release / development choice, loading
 and the ABI-version check, the prototype of EVERY exported function (``PROTOTYPES``, applied once per loaded library), the image of
@@ -13,7 +10,9 @@ here; tests/test_abi_mirror.py holds every row against the two headers.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpvnet_vote.so")          # release build: the tuning knobs are constants
@@ -228,15 +227,28 @@ RASTER_PROTOTYPES = {
                      [_ptr, _ptr, _ptr, _ptr, _size, _ptr]),
 }
 
+
+
+class SideLibrary(NamedTuple):
+    path: str
+    abi_version: int      # what pvnet_<name>_abi_version() must answer (PVNET_<NAME>_ABI_VERSION of include/pvnet_<name>.h)
+    prototypes: dict      # name -> (restype, argtypes) of every function that header declares
+
+
+# one row per side library, under the name pvnet_amd.build.SIDE_LIBRARIES builds it by; read when a library is loaded
+SIDE_LIBRARIES = {
+    "head": SideLibrary(HEAD_LIB_PATH, HEAD_ABI_VERSION, HEAD_PROTOTYPES),
+    "train": SideLibrary(TRAIN_LIB_PATH, TRAIN_ABI_VERSION, TRAIN_PROTOTYPES),
+    "targets": SideLibrary(TARGETS_LIB_PATH, TARGETS_ABI_VERSION, TARGETS_PROTOTYPES),
+    "augment": SideLibrary(AUGMENT_LIB_PATH, AUGMENT_ABI_VERSION, AUGMENT_PROTOTYPES),
+    "color": SideLibrary(COLOR_LIB_PATH, COLOR_ABI_VERSION, COLOR_PROTOTYPES),
+    "classes": SideLibrary(CLASSES_LIB_PATH, CLASSES_ABI_VERSION, CLASSES_PROTOTYPES),
+    "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
+}
+
 _lib = None
-_libs = {}   # path -> loaded library
-_classes_lib = None
-_head_lib = None
-_train_lib = None
-_targets_lib = None
-_augment_lib = None
-_color_lib = None
-_raster_lib = None
+_libs = {}        # path -> loaded vote library
+_side_libs = {}   # name -> loaded side library
 
 
 def _wanted_library() -> str:
@@ -255,79 +267,46 @@ def load_library() -> C.CDLL:
     return _lib
 
 
-def _load(lib_path: str) -> C.CDLL:
-    if lib_path in _libs:
-        return _libs[lib_path]
+def _bound(lib_path: str, prototypes: dict) -> C.CDLL:
+    """dlopen a library and give every function of its table its prototype; loud failure if it has not been built"""
     if not os.path.exists(lib_path):
         raise RuntimeError(f"pvnet_amd: HIP library {lib_path} is missing -- build it with "
                            f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
     lib = C.CDLL(lib_path)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
-    if lib.pvnet_vote_abi_version() != ABI_VERSION:
-        raise RuntimeError("pvnet_amd: libpvnet_vote.so ABI version mismatch; rebuild it")
-    _libs[lib_path] = lib
     return lib
 
 
+def _load(lib_path: str) -> C.CDLL:
+    if lib_path not in _libs:
+        lib = _bound(lib_path, PROTOTYPES)
+        if lib.pvnet_vote_abi_version() != ABI_VERSION:
+            raise RuntimeError("pvnet_amd: libpvnet_vote.so ABI version mismatch; rebuild it")
+        _libs[lib_path] = lib
+    return _libs[lib_path]
+
+
 def _load_side(name: str) -> C.CDLL:
-    """dlopen one of the head's libraries, bind its table, check its ABI version -- once.  Its path, table, version and cache are this
-    module's ``<NAME>_LIB_PATH``, ``<NAME>_PROTOTYPES``, ``<NAME>_ABI_VERSION`` and ``_<name>_lib``, read when called."""
-    g = globals()
-    if g[f"_{name}_lib"] is None:
-        path = g[f"{name.upper()}_LIB_PATH"]
-        if not os.path.exists(path):
-            raise RuntimeError(f"pvnet_amd: HIP library {path} is missing -- build it with "
-                               f"`python -m pvnet_amd.build` (hipcc, gfx950). There is no CPU fallback.")
-        lib = C.CDLL(path)
-        for fn_name, (restype, argtypes) in g[f"{name.upper()}_PROTOTYPES"].items():
-            fn = getattr(lib, fn_name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if getattr(lib, f"pvnet_{name}_abi_version")() != g[f"{name.upper()}_ABI_VERSION"]:
+    """dlopen one of SIDE_LIBRARIES, bind its table, check its ABI version -- once"""
+    if name not in _side_libs:
+        path, version, prototypes = SIDE_LIBRARIES[name]
+        lib = _bound(path, prototypes)
+        if getattr(lib, f"pvnet_{name}_abi_version")() != version:
             raise RuntimeError(f"pvnet_amd: libpvnet_{name}.so ABI version mismatch; rebuild it")
-        g[f"_{name}_lib"] = lib
-    return g[f"_{name}_lib"]
+        _side_libs[name] = lib
+    return _side_libs[name]
 
 
-def load_head_library() -> C.CDLL:
-    """dlopen libpvnet_head.so (the head metrics); loud failure if it has not been built.  There is no CPU fallback."""
-    return _load_side("head")
-
-
-def load_train_library() -> C.CDLL:
-    """dlopen libpvnet_train.so (the head losses' backward); loud failure if it has not been built.  There is no CPU fallback."""
-    return _load_side("train")
-
-
-def load_targets_library() -> C.CDLL:
-    """dlopen libpvnet_targets.so (targets from key-points, the head fused with them); loud failure if it has not been built.  There is
-    no CPU fallback."""
-    return _load_side("targets")
-
-
-def load_augment_library() -> C.CDLL:
-    """dlopen libpvnet_augment.so (the augmentation of a training batch); loud failure if it has not been built.  There is no CPU
-    fallback."""
-    return _load_side("augment")
-
-
-def load_color_library() -> C.CDLL:
-    """dlopen libpvnet_color.so (the colour jitter, alone or fused behind the augmentation); loud failure if it has not been built.
-    There is no CPU fallback."""
-    return _load_side("color")
-
-
-def load_classes_library() -> C.CDLL:
-    """dlopen libpvnet_classes.so (class labels -> the bit masks of every class); loud failure if it has not been built.  There is no
-    CPU fallback."""
-    return _load_side("classes")
-
-
-def load_raster_library() -> C.CDLL:
-    """dlopen libpvnet_raster.so (silhouettes and label images of posed meshes); loud failure if it has not been built.  There is no
-    CPU fallback."""
-    return _load_side("raster")
+# the public spelling, one per row of SIDE_LIBRARIES: loud failure if the library has not been built.  There is no CPU fallback.
+load_head_library = functools.partial(_load_side, "head")
+load_train_library = functools.partial(_load_side, "train")
+load_targets_library = functools.partial(_load_side, "targets")
+load_augment_library = functools.partial(_load_side, "augment")
+load_color_library = functools.partial(_load_side, "color")
+load_classes_library = functools.partial(_load_side, "classes")
+load_raster_library = functools.partial(_load_side, "raster")
 
 
 def reload_tuning():

@@ -24,6 +24,7 @@ import torch
 from ._abi import (AUGMENT_F_CROP, AUGMENT_F_FLIP, AUGMENT_F_MASK, AUGMENT_F_ROTATION, AUGMENT_F_USE_MASK_OUT, AUGMENT_OUT_BF16,
                    AUGMENT_OUT_F16, AUGMENT_OUT_F32, AUGMENT_S_DEGENERATE, AUGMENT_S_EMPTIED, AUGMENT_S_NO_FOREGROUND,  # noqa: F401
                    AUGMENT_S_RANGE, AUGMENT_UNIFORMS, MASK_I32, MASK_I64, MASK_U8, AugmentConfigStruct, _check, load_augment_library)
+from ._marshal import nbytes as _nbytes, ptr as _ptr, stream as _stream, strides as _strides, workspace as _workspace
 
 N_UNIFORMS = 12   # u0 .. u11 of include/pvnet_augment.h
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)   # the reference's Normalize (linemod_dataset.py:188-189)
@@ -106,10 +107,6 @@ def pack_uniforms(uniforms, cfg, device):
     return torch.tensor(rows, dtype=torch.float64).reshape(-1, AUGMENT_UNIFORMS).to(device)
 
 
-def _strides(t, dims):
-    return (C.c_int64 * len(dims))(*[int(t.stride(d)) for d in dims])
-
-
 def _check_rgb(rgb):
     if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda):
         raise RuntimeError("rgb must be a CUDA tensor (there is no CPU fallback)")
@@ -186,20 +183,14 @@ def augment_batch(rgb, mask, hcoords, height, width, cfg, uniforms, seed, out_dt
     dev, (b, h, w), vn, hc, packed, (image, mask_o, hc_o, status) = _prepare_augment(rgb, mask, hcoords, height, width, cfg, uniforms,
                                                                                    out_dtype, mask_dtype, out)
     lib = load_augment_library()
-    nbytes = lib.pvnet_augment_workspace_bytes(b)
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
-    elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
-        raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
+    workspace = _workspace(workspace, lib.pvnet_augment_workspace_bytes(b), dev, least=8)
     struct = cfg.struct()
     with torch.cuda.device(dev):
         _check(lib.pvnet_augment(
-            C.c_void_p(rgb.data_ptr()), _strides(rgb, (0, 1, 2)), C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype],
-            _strides(mask, (0, 1, 2)), C.c_void_p(hc.data_ptr()), C.c_void_p(packed.data_ptr()), b, h, w, vn, height, width,
-            C.byref(struct), int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(image.data_ptr()), _OUT_CODES[out_dtype],
-            C.c_void_p(mask_o.data_ptr()), _MASK_OUT_CODES[mask_dtype], C.c_void_p(hc_o.data_ptr()), C.c_void_p(status.data_ptr()),
-            C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_augment")
+            _ptr(rgb), _strides(rgb, (0, 1, 2)), _ptr(mask), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)), _ptr(hc), _ptr(packed),
+            b, h, w, vn, height, width, C.byref(struct), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(image), _OUT_CODES[out_dtype],
+            _ptr(mask_o), _MASK_OUT_CODES[mask_dtype], _ptr(hc_o), _ptr(status), _ptr(workspace), _nbytes(workspace), _stream(dev)),
+            "pvnet_augment")
     return image, mask_o, hc_o, status
 
 
@@ -217,6 +208,6 @@ def normalize_batch(rgb, out_dtype=torch.float32, out=None):
     struct = AugmentConfig.identity().struct()
     with torch.cuda.device(dev):
         _check(load_augment_library().pvnet_normalize(
-            C.c_void_p(rgb.data_ptr()), _strides(rgb, (0, 1, 2)), b, h, w, C.byref(struct), C.c_void_p(out.data_ptr()),
-            _OUT_CODES[out_dtype], C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_normalize")
+            _ptr(rgb), _strides(rgb, (0, 1, 2)), b, h, w, C.byref(struct), _ptr(out), _OUT_CODES[out_dtype], _stream(dev)),
+            "pvnet_normalize")
     return out

@@ -1,8 +1,5 @@
-"""Builds libpvnet_vote.so (the C-ABI HIP library), libpvnet_head.so (the head metrics, a library of its own), libpvnet_train.so
-(the head losses' backward, likewise), libpvnet_targets.so (the targets from key-points and the head fused with them, likewise),
-libpvnet_augment.so (the augmentation of a training batch, likewise), libpvnet_color.so (the colour jitter, alone or fused behind
-that augmentation, likewise), libpvnet_classes.so (class labels to the bit masks of every class, likewise) and libpvnet_raster.so
-(silhouettes and label images of posed meshes, likewise) in-tree for gfx950 with hipcc.
+"""Builds libpvnet_vote.so (the C-ABI HIP library) and the side libraries beside it (``SIDE_LIBRARIES``: one row per library, one
+``libpvnet_<name>.so`` each) in-tree for gfx950 with hipcc.
 
     python -m pvnet_amd.build            # build if sources are newer than the library
     python -m pvnet_amd.build --force
@@ -31,46 +28,31 @@ LIB = os.path.join(HERE, "libpvnet_vote.so")          # release: the knobs are c
 DEV_LIB = os.path.join(HERE, "libpvnet_vote_dev.so")  # -DPVNET_DEV: environment knobs + every kernel variant (knob tests, fuzz, tuning tools)
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
-# the head behind the backbone and the inputs in front of it: libraries of one translation unit each, beside libpvnet_vote.so, whose ABI stays as it is.
-# name -> (translation units, its header under include/ beyond pvnet_head.h, the register checker's option)
+# the head behind the backbone and the inputs in front of it: libraries of one translation unit each, beside libpvnet_vote.so, whose ABI
+# stays as it is.  One row per library, under the name pvnet_amd._abi.SIDE_LIBRARIES binds it by:
+# name -> (translation units, its header under include/, what they include beyond that header and the common ones)
+_AUGMENT_WARP = os.path.join(CSRC, "augment_warp.h")   # the one copy of the plan and the warp: the two libraries that compile it rebuild with it
 SIDE_LIBRARIES = {
-    "head": (["head_metrics.hip"], "pvnet_head.h", "--head"),          # the head metrics of a validation step
-    "train": (["head_grad.hip"], "pvnet_train.h", "--train"),          # the backward of the head losses of a training step
-    "targets": (["head_targets.hip"], "pvnet_targets.h", "--targets"),  # the targets from key-points, the head fused with them
-    "augment": (["augment.hip"], "pvnet_augment.h", "--augment"),       # the inputs of a training step: warp, normalise, key-points
-    "color": (["color_jitter.hip"], "pvnet_color.h", "--color"),        # the colour jitter, alone or fused behind that warp
-    "classes": (["class_split.hip"], "pvnet_classes.h", "--classes"),   # class labels -> the bit masks the voting layer runs on
-    "raster": (["raster.hip"], "pvnet_raster.h", "--raster"),           # poses and meshes -> silhouettes and label images
-}
-# what a library's translation unit includes beyond its own header and the common ones: augment_warp.h is the one copy of the plan and
-# the warp that the augment and the colour library both compile, so both rebuild when it changes
-SIDE_EXTRA_DEPS = {
-    "augment": [os.path.join(CSRC, "augment_warp.h")],
-    "color": [os.path.join(CSRC, "augment_warp.h"), os.path.join(ROOT, "include", "pvnet_augment.h")],
+    "head": (["head_metrics.hip"], "pvnet_head.h", []),          # the head metrics of a validation step
+    "train": (["head_grad.hip"], "pvnet_train.h", []),           # the backward of the head losses of a training step
+    "targets": (["head_targets.hip"], "pvnet_targets.h", []),    # the targets from key-points, the head fused with them
+    "augment": (["augment.hip"], "pvnet_augment.h", [_AUGMENT_WARP]),   # the inputs of a training step: warp, normalise, key-points
+    "color": (["color_jitter.hip"], "pvnet_color.h",              # the colour jitter, alone or fused behind that warp
+              [_AUGMENT_WARP, os.path.join(ROOT, "include", "pvnet_augment.h")]),
+    "classes": (["class_split.hip"], "pvnet_classes.h", []),     # class labels -> the bit masks the voting layer runs on
+    "raster": (["raster.hip"], "pvnet_raster.h", []),            # poses and meshes -> silhouettes and label images
 }
 
 
 def _side(name):
     """(sources, what they depend on, the library) of one of SIDE_LIBRARIES"""
-    tu, header, _ = SIDE_LIBRARIES[name]
+    tu, header, extra = SIDE_LIBRARIES[name]
     src = [os.path.join(CSRC, f) for f in tu]
     deps = src + [os.path.join(CSRC, f) for f in ("head_common.h", "vote_common.h", "pvnet_rng.h")] + \
-        [os.path.join(ROOT, "include", f) for f in sorted({header, "pvnet_head.h", "pvnet_vote.h"})] + SIDE_EXTRA_DEPS.get(name, [])
+        [os.path.join(ROOT, "include", f) for f in sorted({header, "pvnet_head.h", "pvnet_vote.h"})] + extra
     return src, deps, os.path.join(HERE, f"libpvnet_{name}.so")
 
 
-HEAD_TU, TRAIN_TU, TARGETS_TU = (SIDE_LIBRARIES[n][0] for n in ("head", "train", "targets"))
-HEAD_SRC, HEAD_DEPS, HEAD_LIB = _side("head")
-TRAIN_SRC, TRAIN_DEPS, TRAIN_LIB = _side("train")
-TARGETS_SRC, TARGETS_DEPS, TARGETS_LIB = _side("targets")
-AUGMENT_TU = SIDE_LIBRARIES["augment"][0]
-AUGMENT_SRC, AUGMENT_DEPS, AUGMENT_LIB = _side("augment")
-COLOR_TU = SIDE_LIBRARIES["color"][0]
-COLOR_SRC, COLOR_DEPS, COLOR_LIB = _side("color")
-CLASSES_TU = SIDE_LIBRARIES["classes"][0]
-CLASSES_SRC, CLASSES_DEPS, CLASSES_LIB = _side("classes")
-RASTER_TU = SIDE_LIBRARIES["raster"][0]
-RASTER_SRC, RASTER_DEPS, RASTER_LIB = _side("raster")
 # host-side pose refinement (plain C++, g++): include/pvnet_pnp.h
 PNP_SRC = os.path.join(HERE, "csrc", "pvnet_pnp.cpp")
 PNP_DEPS = [PNP_SRC, os.path.join(ROOT, "include", "pvnet_pnp.h")]
@@ -91,9 +73,27 @@ def flags():
             "-I", os.path.join(ROOT, "include"), "-I", os.path.join(HERE, "csrc"), "-Wall"]
 
 
+def fresh(target, deps) -> bool:
+    """the target exists and is no older than any of deps"""
+    return os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(d) for d in deps)
+
+
 def up_to_date(lib=None) -> bool:
-    lib = lib or LIB
-    return os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(d) for d in DEPS)
+    return fresh(lib or LIB, DEPS)
+
+
+def install(lib, make, check=None) -> None:
+    """make(path) builds the library beside its place, check() judges the build, and only then does it replace the previous one: a
+    failing compiler or check -- or a broken checker environment -- must not take a working library away"""
+    tmp = lib + ".new"
+    try:
+        make(tmp)
+        if check is not None:
+            check()
+        os.replace(tmp, lib)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
 
 
 def compile_link(out: str, dev: bool, verbose: bool = False) -> None:
@@ -129,7 +129,7 @@ def compile_link(out: str, dev: bool, verbose: bool = False) -> None:
 
 
 def build_pnp(force: bool = False, verbose: bool = False) -> str:
-    if not force and os.path.exists(PNP_LIB) and all(os.path.getmtime(PNP_LIB) >= os.path.getmtime(d) for d in PNP_DEPS):
+    if not force and fresh(PNP_LIB, PNP_DEPS):
         return PNP_LIB
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
     if not cxx:
@@ -143,50 +143,17 @@ def build_pnp(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_side(name: str, force: bool = False, verbose: bool = False) -> str:
-    """hipcc -> one of SIDE_LIBRARIES; like the vote library it replaces the previous one only after the register check passed"""
+    """hipcc -> one of SIDE_LIBRARIES, checked by the register tool for that library alone before it replaces the previous one"""
     src, deps, lib = _side(name)
-    if not force and os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(d) for d in deps):
-        return lib
-    tmp = lib + ".new"
-    try:
-        cmd = [hipcc_path()] + flags() + src + ["-o", tmp]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        check_resources(("check_kernel_resources.py",), [SIDE_LIBRARIES[name][2]])
-        os.replace(tmp, lib)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
+    if force or not fresh(lib, deps):
+        def make(out):
+            cmd = [hipcc_path()] + flags() + src + ["-o", out]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd)
+
+        install(lib, make, lambda: check_resources(("check_kernel_resources.py",), ["--" + name]))
     return lib
-
-
-def build_head(force: bool = False, verbose: bool = False) -> str:
-    return build_side("head", force, verbose)
-
-
-def build_train(force: bool = False, verbose: bool = False) -> str:
-    return build_side("train", force, verbose)
-
-
-def build_targets(force: bool = False, verbose: bool = False) -> str:
-    return build_side("targets", force, verbose)
-
-
-def build_augment(force: bool = False, verbose: bool = False) -> str:
-    return build_side("augment", force, verbose)
-
-
-def build_color(force: bool = False, verbose: bool = False) -> str:
-    return build_side("color", force, verbose)
-
-
-def build_classes(force: bool = False, verbose: bool = False) -> str:
-    return build_side("classes", force, verbose)
-
-
-def build_raster(force: bool = False, verbose: bool = False) -> str:
-    return build_side("raster", force, verbose)
 
 
 # the reference's compiled extension module `ransac_voting` (src/ransac_voting.cpp) on this library: host-only C++ against
@@ -207,7 +174,7 @@ def build_ext(force: bool = False, verbose: bool = False):
     import sysconfig
     out = ext_path()
     deps = [EXT_SRC, os.path.join(ROOT, "include", "pvnet_vote.h"), LIB]
-    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps if os.path.exists(d)):
+    if not force and fresh(out, [d for d in deps if os.path.exists(d)]):
         return out
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
     try:
@@ -250,7 +217,7 @@ CANARY_BINS = {"tight": os.path.join(ROOT, "tools", "experiments", "k2_flake", "
 
 def build_canary(force: bool = False, verbose: bool = False):
     for kind, out in CANARY_BINS.items():
-        if not force and os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(CANARY_SRC):
+        if not force and fresh(out, [CANARY_SRC]):
             continue
         cmd = [hipcc_path(), "-O3", f"--offload-arch={ARCH}", "-w", CANARY_SRC, "-o", out] + (["-DV_SPARE"] if kind == "spare" else [])
         if verbose:
@@ -277,31 +244,12 @@ def check_resources(tools=("check_kernel_resources.py", "check_mfma_hazard.py"),
 
 def build(force: bool = False, verbose: bool = False) -> str:
     build_pnp(force, verbose)
-    fresh = force or not up_to_date(LIB)
-    if fresh:
-        tmp = LIB + ".new"
-        try:
-            compile_link(tmp, dev=False, verbose=verbose)
-            check_resources()
-            os.replace(tmp, LIB)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-    if force or not up_to_date(DEV_LIB):
-        tmp = DEV_LIB + ".new"
-        try:
-            compile_link(tmp, dev=True, verbose=verbose)
-            os.replace(tmp, DEV_LIB)
-        finally:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-    build_head(force, verbose)
-    build_train(force, verbose)
-    build_targets(force, verbose)
-    build_augment(force, verbose)
-    build_color(force, verbose)
-    build_classes(force, verbose)
-    build_raster(force, verbose)
+    if force or not up_to_date(LIB):        # release: both checkers judge it
+        install(LIB, lambda out: compile_link(out, dev=False, verbose=verbose), check_resources)
+    if force or not up_to_date(DEV_LIB):    # development: not checked
+        install(DEV_LIB, lambda out: compile_link(out, dev=True, verbose=verbose))
+    for name in SIDE_LIBRARIES:
+        build_side(name, force, verbose)
     build_ext(force, verbose)
     build_canary(force, verbose)
     return LIB

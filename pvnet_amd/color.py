@@ -27,7 +27,8 @@ import dataclasses
 import torch
 
 from ._abi import COLOR_UNIFORMS, ColorConfigStruct, _check, load_color_library
-from .augment import _MASK_CODES, _MASK_OUT_CODES, _OUT_CODES, MEAN, STD, AugmentConfig, _check_rgb, _prepare_augment, _strides
+from ._marshal import nbytes as _nbytes, ptr as _ptr, stream as _stream, strides as _strides, workspace as _workspace
+from .augment import _MASK_CODES, _MASK_OUT_CODES, _OUT_CODES, MEAN, STD, AugmentConfig, _check_rgb, _prepare_augment
 
 
 @dataclasses.dataclass
@@ -89,14 +90,6 @@ def color_workspace_bytes(b, height=0, width=0):
     return int(load_color_library().pvnet_color_workspace_bytes(int(b), int(height), int(width)))
 
 
-def _workspace(workspace, nbytes, dev):
-    if workspace is None:
-        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
-        raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
-    return workspace
-
-
 def jitter_batch(rgb, cfg, uniforms, out_dtype=torch.float32, mask=None, maskmul=None, out=None, workspace=None):
     """The reference's ``ColorJitter`` + ``ToTensor`` + ``Normalize`` for a batch, on the current stream, without synchronising.
 
@@ -125,8 +118,7 @@ def jitter_batch(rgb, cfg, uniforms, out_dtype=torch.float32, mask=None, maskmul
         if tuple(maskmul.shape) != (b,) or maskmul.is_floating_point():
             raise RuntimeError(f"maskmul must be [b]={b} integers")
         maskmul = maskmul.to(device=dev, dtype=torch.int32).contiguous()
-        mask_ptr, mask_code, mask_strides, mul_ptr = C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)), \
-            C.c_void_p(maskmul.data_ptr())
+        mask_ptr, mask_code, mask_strides, mul_ptr = _ptr(mask), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)), _ptr(maskmul)
     packed = _device_jitter_uniforms(uniforms, b, dev)
     if out is None:
         out = torch.empty((b, 3, h, w), dtype=out_dtype, device=dev)
@@ -134,13 +126,12 @@ def jitter_batch(rgb, cfg, uniforms, out_dtype=torch.float32, mask=None, maskmul
               tuple(out.shape) == (b, 3, h, w) and out.is_contiguous()):
         raise RuntimeError(f"out must be a contiguous {out_dtype} CUDA tensor of shape {(b, 3, h, w)} on {dev}")
     lib = load_color_library()
-    workspace = _workspace(workspace, lib.pvnet_color_workspace_bytes(b, 0, 0), dev)
+    workspace = _workspace(workspace, lib.pvnet_color_workspace_bytes(b, 0, 0), dev, least=16)
     struct = cfg.struct()
     with torch.cuda.device(dev):
         _check(lib.pvnet_color_jitter(
-            C.c_void_p(rgb.data_ptr()), _strides(rgb, (0, 1, 2)), C.c_void_p(packed.data_ptr()), b, h, w, C.byref(struct), mask_ptr,
-            mask_code, mask_strides, mul_ptr, C.c_void_p(out.data_ptr()), _OUT_CODES[out_dtype], C.c_void_p(workspace.data_ptr()),
-            workspace.numel() * workspace.element_size(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_color_jitter")
+            _ptr(rgb), _strides(rgb, (0, 1, 2)), _ptr(packed), b, h, w, C.byref(struct), mask_ptr, mask_code, mask_strides, mul_ptr,
+            _ptr(out), _OUT_CODES[out_dtype], _ptr(workspace), _nbytes(workspace), _stream(dev)), "pvnet_color_jitter")
     return out
 
 
@@ -161,14 +152,12 @@ def augment_jitter_batch(rgb, mask, hcoords, height, width, cfg, jitter_cfg, uni
                                                                                    out_dtype, mask_dtype, out)
     jpacked = _device_jitter_uniforms(jitter_uniforms, b, dev)
     lib = load_color_library()
-    workspace = _workspace(workspace, lib.pvnet_color_workspace_bytes(b, height, width), dev)
+    workspace = _workspace(workspace, lib.pvnet_color_workspace_bytes(b, height, width), dev, least=16)
     struct, jstruct = cfg.struct(), jitter_cfg.struct()
     with torch.cuda.device(dev):
         _check(lib.pvnet_augment_jitter(
-            C.c_void_p(rgb.data_ptr()), _strides(rgb, (0, 1, 2)), C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype],
-            _strides(mask, (0, 1, 2)), C.c_void_p(hc.data_ptr()), C.c_void_p(packed.data_ptr()), b, h, w, vn, height, width,
-            C.byref(struct), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(jstruct), C.c_void_p(jpacked.data_ptr()),
-            C.c_void_p(image.data_ptr()), _OUT_CODES[out_dtype], C.c_void_p(mask_o.data_ptr()), _MASK_OUT_CODES[mask_dtype],
-            C.c_void_p(hc_o.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(workspace.data_ptr()),
-            workspace.numel() * workspace.element_size(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_augment_jitter")
+            _ptr(rgb), _strides(rgb, (0, 1, 2)), _ptr(mask), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)), _ptr(hc), _ptr(packed),
+            b, h, w, vn, height, width, C.byref(struct), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(jstruct), _ptr(jpacked),
+            _ptr(image), _OUT_CODES[out_dtype], _ptr(mask_o), _MASK_OUT_CODES[mask_dtype], _ptr(hc_o), _ptr(status),
+            _ptr(workspace), _nbytes(workspace), _stream(dev)), "pvnet_augment_jitter")
     return image, mask_o, hc_o, status

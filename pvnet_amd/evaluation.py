@@ -28,6 +28,7 @@ import numpy as np
 
 from . import pnp as P
 from ._abi import METRIC_SYM_PROJECTION, _check, load_library
+from ._marshal import nbytes as _nbytes, ptr as _ptr, stream as _stream, workspace as _workspace
 
 SYMMETRIC_CLASSES = ("eggbox", "glue")  # evaluation_utils.py:153,196,215
 
@@ -56,9 +57,8 @@ def nearest_point_idx(ref_pts, que_pts, exclude_self=False):
     with torch.cuda.device(ref.device):
         nbytes = lib.pvnet_nearest_workspace_bytes(b, pn2)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=ref.device)
-        _check(lib.pvnet_nearest_point_idx(ref.data_ptr(), que.data_ptr(), idxs.data_ptr(), b, pn1, pn2, dim,
-                                           1 if exclude_self else 0, ws.data_ptr(), nbytes,
-                                           torch.cuda.current_stream(ref.device).cuda_stream), "pvnet_nearest_point_idx")
+        _check(lib.pvnet_nearest_point_idx(_ptr(ref), _ptr(que), _ptr(idxs), b, pn1, pn2, dim, 1 if exclude_self else 0, _ptr(ws), nbytes,
+                                           _stream(ref.device)), "pvnet_nearest_point_idx")
     return idxs[0] if squeeze else idxs
 
 
@@ -180,19 +180,11 @@ def pose_metrics_device(pose_pred, pose_targets, K, models, class_ids=None, sym_
                     raise RuntimeError(f"{name} must be a contiguous {dt} CUDA tensor of shape {shape} on {dev}")
         if n == 0:
             return errors, passed, status
-        nbytes = lib.pvnet_pose_metrics_workspace_bytes(n, models.max_points, flags)
-        if workspace is None:
-            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
-            raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
+        workspace = _workspace(workspace, lib.pvnet_pose_metrics_workspace_bytes(n, models.max_points, flags), dev)
         _check(lib.pvnet_pose_metrics(
-            C.c_void_p(pred.data_ptr()), C.c_void_p(tgt.data_ptr()), int(tgt.dtype == torch.float64),
-            C.c_void_p(models.points.data_ptr()), C.c_void_p(models.offsets.data_ptr()), C.c_void_p(models.diameters.data_ptr()),
-            C.c_void_p(models.symmetric.data_ptr()), len(models), models.max_points,
-            C.c_void_p(ids.data_ptr()) if ids is not None else None, C.c_void_p(Kd.data_ptr()), per_image, n, flags, th,
-            C.c_void_p(errors.data_ptr()), C.c_void_p(passed.data_ptr()), C.c_void_p(status.data_ptr()),
-            C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size(),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_pose_metrics")
+            _ptr(pred), _ptr(tgt), int(tgt.dtype == torch.float64), _ptr(models.points), _ptr(models.offsets), _ptr(models.diameters),
+            _ptr(models.symmetric), len(models), models.max_points, _ptr(ids), _ptr(Kd), per_image, n, flags, th,
+            _ptr(errors), _ptr(passed), _ptr(status), _ptr(workspace), _nbytes(workspace), _stream(dev)), "pvnet_pose_metrics")
     return errors, passed, status
 
 

@@ -27,6 +27,7 @@ import torch
 
 from ._abi import (RASTER_MAX_IMAGES, RASTER_MAX_INSTANCES, RASTER_MAX_MESHES, RASTER_S_BADFACE, RASTER_S_BEHIND,  # noqa: F401
                    RASTER_S_NONFINITE, _check, load_raster_library)
+from ._marshal import nbytes as _nbytes, ptr as _ptr, stream as _stream, workspace as _workspace
 
 
 # ---- small synthetic meshes (numpy; vertices float64 [P,3], faces int32 [T,3]) -------------------------------------------------------
@@ -137,17 +138,6 @@ def raster_workspace_bytes(q, h, w, meshes=None, b=None):
     return n
 
 
-def _workspace(workspace, nbytes, dev):
-    if workspace is None:
-        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()
-            and workspace.data_ptr() % 16 == 0):
-        raise RuntimeError(f"workspace must be a contiguous, 16-byte aligned CUDA tensor on {dev}")
-    if workspace.numel() * workspace.element_size() < nbytes:
-        raise RuntimeError(f"workspace too small: {workspace.numel() * workspace.element_size()} < {nbytes} bytes")
-    return workspace
-
-
 def _out(out, shape, dev):
     if out is None:
         return torch.empty(shape, dtype=torch.uint8, device=dev)
@@ -155,14 +145,6 @@ def _out(out, shape, dev):
             tuple(out.shape) == tuple(shape) and out.is_contiguous()):
         raise RuntimeError(f"out must be a contiguous uint8 CUDA tensor of shape {tuple(shape)} on {dev}")
     return out
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def rasterize_triangles(triangles_2d, h, w, out=None, workspace=None, return_status=False):
@@ -187,9 +169,9 @@ def rasterize_triangles(triangles_2d, h, w, out=None, workspace=None, return_sta
     with torch.cuda.device(dev):
         for i0 in range(0, n, RASTER_MAX_IMAGES):
             k = min(RASTER_MAX_IMAGES, n - i0)
-            ws = _workspace(workspace, raster_workspace_bytes(k, h, w), dev)
+            ws = _workspace(workspace, raster_workspace_bytes(k, h, w), dev, align=16, sized=True)
             _check(lib.pvnet_raster_triangles(_ptr(tri[i0:]), k, tn, h, w, _ptr(out[i0:]), _ptr(status[i0:]) if return_status else None,
-                                              _ptr(ws), ws.numel() * ws.element_size(), _stream(dev)), "pvnet_raster_triangles")
+                                              _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_raster_triangles")
     res = out[0] if single else out
     return (res, status) if return_status else res
 
@@ -235,7 +217,8 @@ def _render(meshes, dev, mesh_ids, image_ids, labels, poses, K, k_per_instance, 
             i0 = 0 if ci == 0 else image_ids[s]
             i1 = b if ci == len(cuts) - 1 else image_ids[e]
             n = e - s
-            ws = _workspace(workspace, raster_workspace_bytes(n, h, w, meshes, i1 - i0) if h >= 2 and w >= 2 else 16, dev)
+            ws = _workspace(workspace, raster_workspace_bytes(n, h, w, meshes, i1 - i0) if h >= 2 and w >= 2 else 16, dev, align=16,
+                            sized=True)
             arr = lambda vals: (C.c_int32 * max(n, 1))(*vals)   # noqa: E731
             ntri = sum(meshes.face_count(m) for m in mesh_ids[s:e])
             _check(lib.pvnet_render(
@@ -243,7 +226,7 @@ def _render(meshes, dev, mesh_ids, image_ids, labels, poses, K, k_per_instance, 
                 arr(mesh_ids[s:e]), _ptr(poses[s:]), _ptr(K[s:] if k_per_instance else K), 1 if k_per_instance else 0,
                 arr([i - i0 for i in image_ids[s:e]]), arr(labels[s:e]), _ptr(order[s:]) if order is not None else None, i1 - i0, h, w,
                 _ptr(out[i0:]) if out is not None else None, _ptr(tri_out[tri0:]) if tri_out is not None else None,
-                _ptr(status[s:]) if status is not None else None, _ptr(ws), ws.numel() * ws.element_size(), _stream(dev)), "pvnet_render")
+                _ptr(status[s:]) if status is not None else None, _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_render")
             tri0 += ntri
 
 

@@ -20,21 +20,17 @@ PyTorch is plumbing only.  There is NO CPU fallback: without the library, or wit
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from ._abi import (HEAD_F_LOGITS_BF16, HEAD_F_LOGITS_F16, HEAD_F_NT_ALL, HEAD_F_NT_NONE, HEAD_F_VERTEX_BF16,  # noqa: F401
                    HEAD_F_VERTEX_F16, HEAD_S_BAD_LABEL, MASK_I32, MASK_I64, MASK_U8, TARGETS_F_MOTION, _check, load_head_library,
                    load_targets_library, load_train_library)
+from ._marshal import nbytes as _nbytes, opt_strides as _opt_strides, ptr as _ptr, stream as _stream, strides as _strides, \
+    workspace as _workspace
 
 _VERTEX_FLAGS = {torch.float32: 0, torch.float16: HEAD_F_VERTEX_F16, torch.bfloat16: HEAD_F_VERTEX_BF16}
 _LOGITS_FLAGS = {torch.float32: 0, torch.float16: HEAD_F_LOGITS_F16, torch.bfloat16: HEAD_F_LOGITS_BF16}
 _MASK_CODES = {torch.uint8: MASK_U8, torch.bool: MASK_U8, torch.int32: MASK_I32, torch.int64: MASK_I64}
-
-
-def _strides(t, dims):
-    return (C.c_int64 * len(dims))(*[int(t.stride(d)) for d in dims])
 
 
 def _head_inputs(seg_pred, vertex_pred, mask, vertex, vertex_weights, flags):
@@ -83,15 +79,6 @@ def _metric_outputs(out, b, dev):
     return losses, counts, status
 
 
-def _workspace(workspace, nbytes, dev):
-    """-> (pointer, bytes) of the caller's workspace, or of a new one of ``nbytes``"""
-    if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    elif not (workspace.is_cuda and workspace.device == dev and workspace.is_contiguous()):
-        raise RuntimeError(f"workspace must be a contiguous CUDA tensor on {dev}")
-    return C.c_void_p(workspace.data_ptr()), workspace.numel() * workspace.element_size()
-
-
 def _grad_outputs(seg_pred, vertex_pred, upstream, need, out, b, dev):
     """the checks of ``upstream``, ``need`` and ``out`` -> (grad_seg, grad_vertex, status): new tensors or the caller's, None for a
     half that is not wanted"""
@@ -113,14 +100,6 @@ def _grad_outputs(seg_pred, vertex_pred, upstream, need, out, b, dev):
             raise RuntimeError(f"{name} must be a {pred.dtype} CUDA tensor of shape {tuple(pred.shape)} on {dev}")
         grads.append(g)
     return grads[0], grads[1], torch.empty((b,), dtype=torch.int32, device=dev)
-
-
-def _opt_ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _opt_strides(t, dims):
-    return None if t is None else _strides(t, dims)
 
 
 def head_metrics_workspace_bytes(b, h, w):
@@ -148,16 +127,16 @@ def head_metrics_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, sig
         losses, counts, status = _metric_outputs(out, b, dev)
         if b == 0:
             return losses, counts, status
+        ws = _workspace(workspace, lib.pvnet_head_metrics_workspace_bytes(b, h, w), dev)
         _check(lib.pvnet_head_metrics(
-            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
-            C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
-            C.c_void_p(vertex.data_ptr()), _strides(vertex, (0, 1, 2, 3)),
-            C.c_void_p(vertex_weights.data_ptr()), _strides(vertex_weights, (0, 2, 3)),
-            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
+            _ptr(seg_pred), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            _ptr(vertex_pred), _strides(vertex_pred, (0, 1, 2, 3)),
+            _ptr(vertex), _strides(vertex, (0, 1, 2, 3)),
+            _ptr(vertex_weights), _strides(vertex_weights, (0, 2, 3)),
+            _ptr(mask), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
             b, h, w, planes // 2, float(sigma), flags,
-            C.c_void_p(losses.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(status.data_ptr()),
-            *_workspace(workspace, lib.pvnet_head_metrics_workspace_bytes(b, h, w), dev),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_metrics")
+            _ptr(losses), _ptr(counts), _ptr(status),
+            _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_head_metrics")
     return losses, counts, status
 
 
@@ -208,16 +187,16 @@ def head_grad_device(seg_pred, vertex_pred, mask, vertex, vertex_weights, upstre
         grad_seg, grad_vertex, status = _grad_outputs(seg_pred, vertex_pred, upstream, need, out, b, dev)
         if b == 0:
             return grad_seg, grad_vertex, status
+        ws = _workspace(workspace, lib.pvnet_head_grad_workspace_bytes(b, h, w), dev)
         _check(lib.pvnet_head_grad(
-            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
-            C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
-            C.c_void_p(vertex.data_ptr()), _strides(vertex, (0, 1, 2, 3)),
-            C.c_void_p(vertex_weights.data_ptr()), _strides(vertex_weights, (0, 2, 3)),
-            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
-            b, h, w, planes // 2, float(sigma), flags, C.c_void_p(upstream.data_ptr()),
-            _opt_ptr(grad_seg), _opt_strides(grad_seg, (0, 1, 2, 3)), _opt_ptr(grad_vertex), _opt_strides(grad_vertex, (0, 1, 2, 3)),
-            C.c_void_p(status.data_ptr()), *_workspace(workspace, lib.pvnet_head_grad_workspace_bytes(b, h, w), dev),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_grad")
+            _ptr(seg_pred), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            _ptr(vertex_pred), _strides(vertex_pred, (0, 1, 2, 3)),
+            _ptr(vertex), _strides(vertex, (0, 1, 2, 3)),
+            _ptr(vertex_weights), _strides(vertex_weights, (0, 2, 3)),
+            _ptr(mask), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
+            b, h, w, planes // 2, float(sigma), flags, _ptr(upstream),
+            _ptr(grad_seg), _opt_strides(grad_seg, (0, 1, 2, 3)), _ptr(grad_vertex), _opt_strides(grad_vertex, (0, 1, 2, 3)),
+            _ptr(status), _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_head_grad")
     return grad_seg, grad_vertex, status
 
 
@@ -276,10 +255,10 @@ def vertex_targets_device(mask, hcoords, weight_scale=None, use_motion=False, ou
         if b == 0:
             return vertex, weights
         _check(lib.pvnet_vertex_targets(
-            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)), C.c_void_p(hc.data_ptr()),
-            _opt_ptr(weight_scale), b, h, w, vn, TARGETS_F_MOTION if use_motion else 0,
-            _opt_ptr(vertex), _opt_strides(vertex, (0, 1, 2, 3)), _opt_ptr(weights), _opt_strides(weights, (0, 2, 3)),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_vertex_targets")
+            _ptr(mask), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)), _ptr(hc),
+            _ptr(weight_scale), b, h, w, vn, TARGETS_F_MOTION if use_motion else 0,
+            _ptr(vertex), _opt_strides(vertex, (0, 1, 2, 3)), _ptr(weights), _opt_strides(weights, (0, 2, 3)),
+            _stream(dev)), "pvnet_vertex_targets")
     return vertex, weights
 
 
@@ -312,15 +291,15 @@ def head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_sca
         losses, counts, status = _metric_outputs(out, b, dev)
         if b == 0:
             return losses, counts, status
+        ws = _workspace(workspace, lib.pvnet_head_metrics_kp_workspace_bytes(b, h, w), dev)
         _check(lib.pvnet_head_metrics_kp(
-            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
-            C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
-            C.c_void_p(hc.data_ptr()), _opt_ptr(weight_scale),
-            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
+            _ptr(seg_pred), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            _ptr(vertex_pred), _strides(vertex_pred, (0, 1, 2, 3)),
+            _ptr(hc), _ptr(weight_scale),
+            _ptr(mask), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
             b, h, w, vn, float(sigma), flags,
-            C.c_void_p(losses.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(status.data_ptr()),
-            *_workspace(workspace, lib.pvnet_head_metrics_kp_workspace_bytes(b, h, w), dev),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_metrics_kp")
+            _ptr(losses), _ptr(counts), _ptr(status),
+            _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_head_metrics_kp")
     return losses, counts, status
 
 
@@ -334,15 +313,15 @@ def head_grad_from_keypoints(seg_pred, vertex_pred, mask, hcoords, upstream, wei
         grad_seg, grad_vertex, status = _grad_outputs(seg_pred, vertex_pred, upstream, need, out, b, dev)
         if b == 0:
             return grad_seg, grad_vertex, status
+        ws = _workspace(workspace, lib.pvnet_head_grad_kp_workspace_bytes(b, h, w), dev)
         _check(lib.pvnet_head_grad_kp(
-            C.c_void_p(seg_pred.data_ptr()), _strides(seg_pred, (0, 1, 2, 3)), nc,
-            C.c_void_p(vertex_pred.data_ptr()), _strides(vertex_pred, (0, 1, 2, 3)),
-            C.c_void_p(hc.data_ptr()), _opt_ptr(weight_scale),
-            C.c_void_p(mask.data_ptr()), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
-            b, h, w, vn, float(sigma), flags, C.c_void_p(upstream.data_ptr()),
-            _opt_ptr(grad_seg), _opt_strides(grad_seg, (0, 1, 2, 3)), _opt_ptr(grad_vertex), _opt_strides(grad_vertex, (0, 1, 2, 3)),
-            C.c_void_p(status.data_ptr()), *_workspace(workspace, lib.pvnet_head_grad_kp_workspace_bytes(b, h, w), dev),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_head_grad_kp")
+            _ptr(seg_pred), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            _ptr(vertex_pred), _strides(vertex_pred, (0, 1, 2, 3)),
+            _ptr(hc), _ptr(weight_scale),
+            _ptr(mask), _MASK_CODES[mask.dtype], _strides(mask, (0, 1, 2)),
+            b, h, w, vn, float(sigma), flags, _ptr(upstream),
+            _ptr(grad_seg), _opt_strides(grad_seg, (0, 1, 2, 3)), _ptr(grad_vertex), _opt_strides(grad_vertex, (0, 1, 2, 3)),
+            _ptr(status), _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_head_grad_kp")
     return grad_seg, grad_vertex, status
 
 

@@ -29,6 +29,7 @@ from ._abi import (CLASSES_MAX, DEV_LIB_PATH, LIB_PATH, TUNING_KNOBS, Layout, _c
 from ._abi import (F_APPROX, F_BAND_STATS, F_CONCURRENT, F_CULL_ALL, F_CULL_NONE, F_LITERAL, F_LOGITS_BF16,  # noqa: F401
                    F_LOGITS_F16, F_NO_REFINE, F_VERTEX_BF16, F_VERTEX_F16, MASK_F32, MASK_I16, MASK_I32, MASK_I64, MASK_U8,
                    NUM_STAGES, S_NO_INLIER, S_OVERFLOW, S_SINGULAR, S_SKIPPED, STAGE_NAMES)
+from ._marshal import strides as _strides   # _strides(t, n): a tensor's n strides (tools/ and the tests take it from here too)
 
 _FIELD_FLAGS = {torch.float32: 0, torch.float16: F_VERTEX_F16, torch.bfloat16: F_VERTEX_BF16}
 _LOGITS_FLAGS = {torch.float32: 0, torch.float16: F_LOGITS_F16, torch.bfloat16: F_LOGITS_BF16}
@@ -71,10 +72,6 @@ def _prepare(mask, vertex, round_hyp_num, max_num, idxs, convert_mask=True):
             raise RuntimeError(f"idxs must be [b,hn,vn,2]={(b, hn, vn, 2)}, got {tuple(idxs.shape)}")
         idxs = idxs.to(torch.int32).contiguous()
     return mask, vertex, b, h, w, vn, hn, max_num, idxs
-
-
-def _strides(t, n):
-    return (C.c_int64 * n)(*[int(s) for s in t.stride()])
 
 
 def _draw_seed(seed: Optional[int]) -> int:

@@ -1,12 +1,13 @@
 """CPU-only checks of the augmentation on the device (include/pvnet_augment.h, libpvnet_augment.so): the header's exports against the
 prototype table of pvnet_amd/_abi.py, the built library, every bad argument rejected with the documented code before any HIP call,
 the register rule for the new kernels, the configuration's defaults against the reference's JSON, and the float64 restatement
-(tests/augment_restatement.py) against what the reference's own ``augmentation`` returned (tests/golden/augment.npz), bit for bit."""
+(tests/augment_restatement.py) against what the reference's own ``augmentation`` returned (tests/golden/augment.npz), bit for bit.
+What holds for every side library alike (header against table, the built library's symbols, the register tool's selection, the loud
+failure without it) is in tests/test_side_libraries_cpu.py."""
 import ctypes as C
 import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -33,20 +34,11 @@ def lib():
 
 def test_header_declares_the_exports_and_every_one_has_a_prototype():
     returns = dict((n, t) for t, n in re.findall(r"^(int|size_t)\s+(pvnet_[a-z0-9_]+)\s*\(", HDR, re.M))
-    assert set(returns) == EXPORTS == set(_abi.AUGMENT_PROTOTYPES)
-    want = {"int": C.c_int, "size_t": C.c_size_t}
-    for name, (restype, argtypes) in _abi.AUGMENT_PROTOTYPES.items():
-        assert restype is want[returns[name]], name
-        decl = re.search(r"^(?:int|size_t)\s+%s\s*\((.*?)\);" % name, HDR, re.M | re.S).group(1)
-        n = 0 if decl.strip() == "void" else len(decl.split(","))
-        assert len(argtypes) == n, name   # one argument type per declared parameter
+    assert set(returns) == EXPORTS
     decl = re.search(r"^int pvnet_augment\s*\((.*?)\);", HDR, re.M | re.S).group(1).split(",")
     args = _abi.AUGMENT_PROTOTYPES["pvnet_augment"][1]
     assert "size_t workspace_bytes" in decl[-2] and args[-2] is C.c_size_t
     assert "uint64_t seed" in decl[14] and args[14] is C.c_uint64
-    # a table of its own: the other tables share no name with it
-    assert not set(_abi.AUGMENT_PROTOTYPES) & (set(_abi.PROTOTYPES) | set(_abi.HEAD_PROTOTYPES) | set(_abi.TRAIN_PROTOTYPES) |
-                                                set(_abi.TARGETS_PROTOTYPES))
     # every constant of the header is mirrored by value
     consts = dict((n, int(v)) for n, v in re.findall(r"^#define\s+PVNET_AUGMENT_(\w+)\s+(\d+)", HDR, re.M))
     assert consts.pop("ABI_VERSION") == _abi.AUGMENT_ABI_VERSION == 1
@@ -62,21 +54,11 @@ def test_header_declares_the_exports_and_every_one_has_a_prototype():
 
 
 def test_library_is_built_for_gfx950_and_exports_the_symbols(lib):
-    assert os.path.exists(_abi.AUGMENT_LIB_PATH) and _abi.AUGMENT_LIB_PATH.endswith("libpvnet_augment.so")
-    raw = C.CDLL(_abi.AUGMENT_LIB_PATH)
-    for name, (restype, argtypes) in _abi.AUGMENT_PROTOTYPES.items():
-        assert hasattr(raw, name), name
-        fn = getattr(lib, name)   # bound once, at load
-        assert fn.restype is restype and list(fn.argtypes or []) == argtypes, name
-    assert lib.pvnet_augment_abi_version() == _abi.AUGMENT_ABI_VERSION
     blob = open(_abi.AUGMENT_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob and all(k.encode() in blob for k in KERNELS)
-    assert build.AUGMENT_TU == ["augment.hip"] and build.SIDE_LIBRARIES["augment"][1:] == ("pvnet_augment.h", "--augment")
-    # the other libraries' shapes have not moved, and none of them exports the new names
-    assert build.HEAD_TU == ["head_metrics.hip"] and build.TRAIN_TU == ["head_grad.hip"] and build.TARGETS_TU == ["head_targets.hip"]
-    for path in (_abi.HEAD_LIB_PATH, _abi.TRAIN_LIB_PATH, _abi.TARGETS_LIB_PATH, _abi.LIB_PATH):
-        other = C.CDLL(path)
-        assert not any(hasattr(other, n) for n in EXPORTS)
+    assert all(k.encode() in blob for k in KERNELS)
+    assert build.SIDE_LIBRARIES["augment"][:2] == (["augment.hip"], "pvnet_augment.h")
+    # the other libraries' shapes have not moved
+    assert [build.SIDE_LIBRARIES[n][0] for n in ("head", "train", "targets")] == [["head_metrics.hip"], ["head_grad.hip"], ["head_targets.hip"]]
     assert lib.pvnet_augment_workspace_bytes(0) == 0 and lib.pvnet_augment_workspace_bytes(65536) == 0
     assert lib.pvnet_augment_workspace_bytes(-1) == 0
     assert 0 < lib.pvnet_augment_workspace_bytes(1) and lib.pvnet_augment_workspace_bytes(32) == 32 * lib.pvnet_augment_workspace_bytes(1)
@@ -140,23 +122,17 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
 
 
 def test_register_check_covers_the_new_translation_unit(lib):
-    tool = os.path.join(ROOT, "tools", "check_kernel_resources.py")
-    r = subprocess.run([sys.executable, tool, "--augment"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert all(k in r.stdout for k in KERNELS)
-    assert "head_" not in r.stdout and "vertex_targets" not in r.stdout   # --augment selects this library alone
-    assert int(re.search(r"checked (\d+) kernels, 0 without", r.stdout).group(1)) == 7   # the plan, 3 element types x 2 store paths
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_kernel_resources as chk
-    (src, text), = chk.augment_assembly()
+    (src, text), = chk.side_assembly("augment")
     assert src.endswith("augment.hip")
-    for name, nfv, vmax, scratch in chk.kernels(text):
+    ks = chk.kernels(text)
+    assert len(ks) == 7 and all(any(k in name for name, _, _, _ in ks) for k in KERNELS)   # the plan, 3 element types x 2 store paths
+    assert not any("head_" in chk.short(name) or "vertex_targets" in chk.short(name) for name, _, _, _ in ks)
+    for name, nfv, vmax, scratch in ks:
         assert nfv - (vmax + 1) >= chk.SLACK and scratch == 0, name
     # the vector path stores 16 bytes at a time
     assert "global_store_dwordx4" in text
-    # the no-argument run includes the new library
-    src_tool = open(tool).read()
-    assert "augment_assembly()]" in src_tool.split("def main")[1]
 
 
 def test_config_defaults_are_the_references():
@@ -206,13 +182,6 @@ def test_python_entries_refuse_host_tensors_and_bad_uniforms():
         A.pack_uniforms(torch.ones((1, 12), dtype=torch.float64), A.AugmentConfig(), "cpu")
     with pytest.raises(RuntimeError):
         A.pack_uniforms(u.float(), A.AugmentConfig(), "cpu")
-
-
-def test_missing_library_fails_loudly(monkeypatch, tmp_path):
-    monkeypatch.setattr(_abi, "_augment_lib", None)
-    monkeypatch.setattr(_abi, "AUGMENT_LIB_PATH", str(tmp_path / "nope.so"))
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        _abi.load_augment_library()
 
 
 def test_restatement_equals_the_reference_bit_for_bit():

@@ -2,7 +2,9 @@
 voting.ransac_voting_layer_v2): the new library's exports, ABI version and header constants against pvnet_amd/_abi.py, every bad
 argument of the new entry points rejected before any HIP call, the overlay module's export under the reference's name and positional
 signature, the voting library's kernel count and ABI version unchanged, the register rule for the new kernels, and the numpy
-restatement of the split (tests/class_split_restatement.py) against hand-made label images."""
+restatement of the split (tests/class_split_restatement.py) against hand-made label images.
+What holds for every side library alike (header against table, the built library's symbols, the register tool's selection, the loud
+failure without it) is in tests/test_side_libraries_cpu.py."""
 import ast
 import ctypes as C
 import inspect
@@ -39,11 +41,7 @@ def libs():
 
 def test_header_exports_constants_and_prototypes():
     returns = dict((n, t) for t, n in re.findall(r"^(int|size_t)\s+(pvnet_[a-z0-9_]+)\s*\(", HDR, re.M))
-    assert set(returns) == EXPORTS == set(_abi.CLASSES_PROTOTYPES)
-    for name, (restype, argtypes) in _abi.CLASSES_PROTOTYPES.items():
-        assert restype is C.c_int, name
-        decl = re.search(r"^int\s+%s\s*\((.*?)\);" % name, HDR, re.M | re.S).group(1)
-        assert len(argtypes) == (0 if decl.strip() == "void" else len(decl.split(","))), name
+    assert set(returns) == EXPORTS and set(returns.values()) == {"int"}
     decl = re.search(r"^int pvnet_class_split\s*\((.*?)\);", HDR, re.M | re.S).group(1).split(",")
     args = _abi.CLASSES_PROTOTYPES["pvnet_class_split"][1]
     assert "uint64_t seed" in decl[8] and args[8] is C.c_uint64 and "num_classes" in decl[3] and "max_num" in decl[7]
@@ -54,9 +52,6 @@ def test_header_exports_constants_and_prototypes():
     assert len(consts) == 3
     for name, value in consts.items():
         assert getattr(_abi, "CLASSES_" + name) == value, name
-    # a table of its own
-    assert not set(_abi.CLASSES_PROTOTYPES) & (set(_abi.PROTOTYPES) | set(_abi.HEAD_PROTOTYPES) | set(_abi.TRAIN_PROTOTYPES) |
-                                                set(_abi.TARGETS_PROTOTYPES) | set(_abi.AUGMENT_PROTOTYPES) | set(_abi.COLOR_PROTOTYPES))
     # the voting header declares the second half and no longer misstates the histogram length
     assert "pvnet_vote_v3_prepared" in _abi.PROTOTYPES and re.search(r"^int pvnet_vote_v3_prepared\(", VOTE_HDR, re.M)
     assert "[b][nseg][1024]" not in VOTE_HDR and "[b][nseg][%d]" % RS.THIN_BINS in VOTE_HDR
@@ -66,21 +61,15 @@ def test_header_exports_constants_and_prototypes():
 
 def test_libraries_are_built_and_the_vote_library_keeps_its_abi_and_kernel_count(libs):
     clib, vlib = libs
-    assert os.path.exists(_abi.CLASSES_LIB_PATH) and _abi.CLASSES_LIB_PATH.endswith("libpvnet_classes.so")
     raw = C.CDLL(_abi.CLASSES_LIB_PATH)
-    for name, (restype, argtypes) in _abi.CLASSES_PROTOTYPES.items():
-        assert hasattr(raw, name), name
-        fn = getattr(clib, name)
-        assert fn.restype is restype and list(fn.argtypes or []) == argtypes, name
     assert clib.pvnet_classes_abi_version() == 1
-    blob = open(_abi.CLASSES_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob and b"class_split_kernel" in blob
-    assert build.CLASSES_TU == ["class_split.hip"] and build.SIDE_LIBRARIES["classes"][1:] == ("pvnet_classes.h", "--classes")
+    assert b"class_split_kernel" in open(_abi.CLASSES_LIB_PATH, "rb").read()
+    assert build.SIDE_LIBRARIES["classes"][:2] == (["class_split.hip"], "pvnet_classes.h")
     # it links nothing from the vote library, and neither exports the other's functions
     assert not hasattr(raw, "pvnet_vote_v3") and not hasattr(raw, "pvnet_vote_v3_prepared") and not hasattr(raw, "pvnet_vote_layout")
     for path in (_abi.LIB_PATH, _abi.DEV_LIB_PATH):
         other = C.CDLL(path)
-        assert not any(hasattr(other, n) for n in EXPORTS) and hasattr(other, "pvnet_vote_v3_prepared")
+        assert hasattr(other, "pvnet_vote_v3_prepared")
         assert b"class_split_kernel" not in open(path, "rb").read()
     assert vlib.pvnet_vote_abi_version() == _abi.ABI_VERSION == 9
     info = C.CDLL(_abi.LIB_PATH).pvnet_vote_build_info

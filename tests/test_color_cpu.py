@@ -1,12 +1,13 @@
 """CPU-only checks of the colour jitter on the device (include/pvnet_color.h, libpvnet_color.so): the header's exports against the
 prototype table of pvnet_amd/_abi.py, the built library, every bad argument rejected with the documented code before any HIP call,
 the register rule for the new kernels, the configuration's defaults against the reference's JSON, the reference's configuration
-loading as it stands, and the properties of the numpy restatement (tests/color_restatement.py) that follow from the definition."""
+loading as it stands, and the properties of the numpy restatement (tests/color_restatement.py) that follow from the definition.
+What holds for every side library alike (header against table, the built library's symbols, the register tool's selection, the loud
+failure without it) is in tests/test_side_libraries_cpu.py."""
 import ctypes as C
 import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -32,13 +33,7 @@ def lib():
 
 def test_header_declares_the_exports_and_every_one_has_a_prototype():
     returns = dict((n, t) for t, n in re.findall(r"^(int|size_t)\s+(pvnet_[a-z0-9_]+)\s*\(", HDR, re.M))
-    assert set(returns) == EXPORTS == set(_abi.COLOR_PROTOTYPES)
-    want = {"int": C.c_int, "size_t": C.c_size_t}
-    for name, (restype, argtypes) in _abi.COLOR_PROTOTYPES.items():
-        assert restype is want[returns[name]], name
-        decl = re.search(r"^(?:int|size_t)\s+%s\s*\((.*?)\);" % name, HDR, re.M | re.S).group(1)
-        n = 0 if decl.strip() == "void" else len(decl.split(","))
-        assert len(argtypes) == n, name   # one argument type per declared parameter
+    assert set(returns) == EXPORTS
     decl = re.search(r"^int pvnet_augment_jitter\s*\((.*?)\);", HDR, re.M | re.S).group(1).split(",")
     args = _abi.COLOR_PROTOTYPES["pvnet_augment_jitter"][1]
     assert "size_t workspace_bytes" in decl[-2] and args[-2] is C.c_size_t
@@ -48,9 +43,6 @@ def test_header_declares_the_exports_and_every_one_has_a_prototype():
     assert args[:15] + args[17:] == _abi.AUGMENT_PROTOTYPES["pvnet_augment"][1]
     decl = re.search(r"^int pvnet_color_jitter\s*\((.*?)\);", HDR, re.M | re.S).group(1).split(",")
     assert "size_t workspace_bytes" in decl[-2] and _abi.COLOR_PROTOTYPES["pvnet_color_jitter"][1][-2] is C.c_size_t
-    # a table of its own: the other tables share no name with it
-    assert not set(_abi.COLOR_PROTOTYPES) & (set(_abi.PROTOTYPES) | set(_abi.HEAD_PROTOTYPES) | set(_abi.TRAIN_PROTOTYPES) |
-                                              set(_abi.TARGETS_PROTOTYPES) | set(_abi.AUGMENT_PROTOTYPES))
     # every constant of the header is mirrored by value
     consts = dict((n, int(v)) for n, v in re.findall(r"^#define\s+PVNET_COLOR_(\w+)\s+(\d+)", HDR, re.M))
     assert consts.pop("ABI_VERSION") == _abi.COLOR_ABI_VERSION == 1
@@ -70,27 +62,12 @@ def test_header_declares_the_exports_and_every_one_has_a_prototype():
 
 
 def test_library_is_built_for_gfx950_and_exports_the_symbols(lib):
-    assert os.path.exists(_abi.COLOR_LIB_PATH) and _abi.COLOR_LIB_PATH.endswith("libpvnet_color.so")
-    raw = C.CDLL(_abi.COLOR_LIB_PATH)
-    for name, (restype, argtypes) in _abi.COLOR_PROTOTYPES.items():
-        assert hasattr(raw, name), name
-        fn = getattr(lib, name)   # bound once, at load
-        assert fn.restype is restype and list(fn.argtypes or []) == argtypes, name
-    assert lib.pvnet_color_abi_version() == _abi.COLOR_ABI_VERSION
     blob = open(_abi.COLOR_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob and all(k.encode() in blob for k in KERNELS)
-    assert build.COLOR_TU == ["color_jitter.hip"] and build.SIDE_LIBRARIES["color"][1:] == ("pvnet_color.h", "--color")
-    # the shared header is a dependency of both libraries that compile it, and of no other
-    shared = os.path.join(build.CSRC, "augment_warp.h")
-    assert shared in build.COLOR_DEPS and shared in build._side("augment")[1]
-    assert all(shared not in build._side(n)[1] for n in ("head", "train", "targets"))
-    # the augment library still holds its own kernels under their names, and neither library exports the other's functions
+    assert all(k.encode() in blob for k in KERNELS)
+    assert build.SIDE_LIBRARIES["color"][:2] == (["color_jitter.hip"], "pvnet_color.h")
+    # the augment library still holds its own kernels under their names, and none of this library's
     aug = open(_abi.AUGMENT_LIB_PATH, "rb").read()
     assert b"augment_plan_kernel" in aug and b"augment_warp_kernel" in aug and not any(k.encode() in aug for k in KERNELS)
-    for path in (_abi.HEAD_LIB_PATH, _abi.TRAIN_LIB_PATH, _abi.TARGETS_LIB_PATH, _abi.AUGMENT_LIB_PATH, _abi.LIB_PATH):
-        other = C.CDLL(path)
-        assert not any(hasattr(other, n) for n in EXPORTS)
-    assert not hasattr(raw, "pvnet_augment") and not hasattr(raw, "pvnet_normalize")
     ws = lib.pvnet_color_workspace_bytes
     assert ws(0, 0, 0) == 0 and ws(65536, 0, 0) == 0 and ws(-1, 0, 0) == 0 and ws(1, -1, 4) == 0 and ws(1, 0, 4) == 0
     assert ws(1, 0, 0) == 16 and ws(3, 0, 0) == 32                       # S_L: 8 bytes per image, rounded up to 16
@@ -181,24 +158,18 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
 
 
 def test_register_check_covers_the_new_translation_unit(lib):
-    tool = os.path.join(ROOT, "tools", "check_kernel_resources.py")
-    r = subprocess.run([sys.executable, tool, "--color"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert all(k in r.stdout for k in KERNELS)
-    assert "head_" not in r.stdout and "augment_" not in r.stdout   # --color selects this library alone
-    # the zeroing, the statistics, 3 element types x 2 store paths of the apply, the plan, 2 store paths of the warp
-    assert int(re.search(r"checked (\d+) kernels, 0 without", r.stdout).group(1)) == 11
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_kernel_resources as chk
-    (src, text), = chk.color_assembly()
+    (src, text), = chk.side_assembly("color")
     assert src.endswith("color_jitter.hip")
-    for name, nfv, vmax, scratch in chk.kernels(text):
+    ks = chk.kernels(text)
+    # the zeroing, the statistics, 3 element types x 2 store paths of the apply, the plan, 2 store paths of the warp
+    assert len(ks) == 11 and all(any(k in name for name, _, _, _ in ks) for k in KERNELS)
+    assert not any("head_" in chk.short(name) or "augment_" in chk.short(name) for name, _, _, _ in ks)
+    for name, nfv, vmax, scratch in ks:
         assert nfv - (vmax + 1) >= chk.SLACK and scratch == 0, name
     # the vector path stores 16 bytes at a time
     assert "global_store_dwordx4" in text
-    # the no-argument run includes the new library, and still the augment library
-    main = open(tool).read().split("def main")[1]
-    assert "color_assembly()]" in main and "augment_assembly()]" in main
 
 
 def test_config_defaults_are_the_references_and_its_file_loads_as_it_stands():
@@ -247,13 +218,6 @@ def test_python_entries_refuse_host_tensors_and_bad_uniforms():
     for bad in (torch.ones((3, 5), dtype=torch.float64), u.float(), u[:2], u[:, :4]):
         with pytest.raises(RuntimeError):
             K._device_jitter_uniforms(bad, 3, torch.device("cpu"))
-
-
-def test_missing_library_fails_loudly(monkeypatch, tmp_path):
-    monkeypatch.setattr(_abi, "_color_lib", None)
-    monkeypatch.setattr(_abi, "COLOR_LIB_PATH", str(tmp_path / "nope.so"))
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        _abi.load_color_library()
 
 
 # ---- the restatement's properties ----------------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 """CPU-only checks of the head losses' backward (include/pvnet_train.h, libpvnet_train.so): the header's exports against the prototype
 table of pvnet_amd/_abi.py, the built library, every bad argument rejected with the documented code before any HIP call, the register
 rule, the Python entry's refusal of host tensors, and the float64 restatement against the fixture's recorded columns, the reference's
-recorded float32 gradients and a finite difference of the forward's restatement."""
+recorded float32 gradients and a finite difference of the forward's restatement.
+What holds for every side library alike (header against table, the built library's symbols, the register tool's selection, the loud
+failure without it) is in tests/test_side_libraries_cpu.py."""
 import ctypes as C
 import os
 import re
@@ -29,42 +31,24 @@ def lib():
 def test_header_declares_the_exports_and_every_one_has_a_prototype():
     returns = dict((n, t) for t, n in re.findall(r"^(int|size_t)\s+(pvnet_[a-z0-9_]+)\s*\(", HDR, re.M))
     assert set(returns) == {"pvnet_train_abi_version", "pvnet_head_grad_workspace_bytes", "pvnet_head_grad"}
-    assert set(returns) == set(_abi.TRAIN_PROTOTYPES)
-    want = {"int": C.c_int, "size_t": C.c_size_t}
-    for name, (restype, argtypes) in _abi.TRAIN_PROTOTYPES.items():
-        assert restype is want[returns[name]], name
     assert _abi.TRAIN_PROTOTYPES["pvnet_head_grad_workspace_bytes"][0] is C.c_size_t   # a byte count is not cut to 32 bits
-    # one argument type per declared parameter
-    for name in _abi.TRAIN_PROTOTYPES:
-        decl = re.search(r"^(?:int|size_t)\s+%s\s*\((.*?)\);" % name, HDR, re.M | re.S).group(1)
-        n = 0 if decl.strip() == "void" else len(decl.split(","))
-        assert len(_abi.TRAIN_PROTOTYPES[name][1]) == n, name
     args = _abi.TRAIN_PROTOTYPES["pvnet_head_grad"][1]
     decl = re.search(r"^int pvnet_head_grad\s*\((.*?)\);", HDR, re.M | re.S).group(1)
     assert len(args) == 27 and args[25] is C.c_size_t and "size_t workspace_bytes" in decl and args[16] is C.c_double
     # the forward's inputs, in the forward's order and types
     assert args[:18] == _abi.HEAD_PROTOTYPES["pvnet_head_metrics"][1][:18]
-    # a table of its own: the two other libraries' stay as they are
-    assert not set(_abi.TRAIN_PROTOTYPES) & (set(_abi.PROTOTYPES) | set(_abi.HEAD_PROTOTYPES))
     # no second family of flags: the header defines its version and nothing else, and includes pvnet_head.h for the rest
     assert re.findall(r"^#define\s+(PVNET_\w+)\s+\d+", HDR, re.M) == ["PVNET_TRAIN_ABI_VERSION"]
     assert '#include "pvnet_head.h"' in HDR
-    assert int(re.search(r"^#define\s+PVNET_TRAIN_ABI_VERSION\s+(\d+)", HDR, re.M).group(1)) == _abi.TRAIN_ABI_VERSION
 
 
 def test_library_is_built_for_gfx950_and_exports_the_symbols(lib):
-    assert os.path.exists(_abi.TRAIN_LIB_PATH) and _abi.TRAIN_LIB_PATH.endswith("libpvnet_train.so")
-    raw = C.CDLL(_abi.TRAIN_LIB_PATH)
-    for name, (restype, argtypes) in _abi.TRAIN_PROTOTYPES.items():
-        assert hasattr(raw, name), name
-        fn = getattr(lib, name)   # bound once, at load
-        assert fn.restype is restype and list(fn.argtypes or []) == argtypes, name
     assert lib.pvnet_train_abi_version() == _abi.TRAIN_ABI_VERSION == 1
     blob = open(_abi.TRAIN_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob and all(k.encode() in blob for k in KERNELS)
-    assert build.TRAIN_TU == ["head_grad.hip"]
-    assert "head_grad.hip" not in build.VOTE_TU and "head_grad.hip" not in build.HEAD_TU
-    assert build.HEAD_TU == ["head_metrics.hip"]   # the head library's shape has not moved
+    assert all(k.encode() in blob for k in KERNELS)
+    assert build.SIDE_LIBRARIES["train"][0] == ["head_grad.hip"]
+    assert "head_grad.hip" not in build.VOTE_TU and "head_grad.hip" not in build.SIDE_LIBRARIES["head"][0]
+    assert build.SIDE_LIBRARIES["head"][0] == ["head_metrics.hip"]   # the head library's shape has not moved
 
 
 def test_workspace_bytes(lib):
@@ -121,17 +105,12 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
 
 def test_register_check_covers_the_new_translation_unit(lib):
     tool = os.path.join(ROOT, "tools", "check_kernel_resources.py")
-    r = subprocess.run([sys.executable, tool, "--train"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert all(k in r.stdout for k in KERNELS)
-    assert "head_partial_kernel" not in r.stdout                   # --train selects this library alone
-    assert int(re.search(r"checked (\d+) kernels, 0 without", r.stdout).group(1)) >= 5
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_kernel_resources as chk
-    (src, text), = chk.train_assembly()
+    (src, text), = chk.side_assembly("train")
     assert src.endswith("head_grad.hip")
     ks = chk.kernels(text)
-    assert len(ks) >= 5
+    assert len(ks) >= 5 and all(any(k in name for name, _, _, _ in ks) for k in KERNELS)
     for name, nfv, vmax, scratch in ks:
         assert nfv - (vmax + 1) >= chk.SLACK and scratch == 0, name
     # the rule bites: the gradient kernel with its allocation cut to what it uses is rejected
@@ -146,15 +125,6 @@ def test_register_check_covers_the_new_translation_unit(lib):
         assert r.returncode == 1 and "uses its last granule" in r.stdout
     finally:
         os.remove(tight_file)
-    # the head library's selection is still its one translation unit
-    (hsrc, _), = chk.head_assembly()
-    assert hsrc.endswith("head_metrics.hip")
-
-
-def test_no_argument_run_includes_the_train_library():
-    src = open(os.path.join(ROOT, "tools", "check_kernel_resources.py")).read()
-    body = src[src.index("def main(argv):"):]
-    assert body.count("train_assembly()") == 2   # --train, and the no-argument run beside assembly() and head_assembly()
 
 
 def test_python_entry_refuses_host_tensors_and_imports_no_oracle():
@@ -174,10 +144,8 @@ def test_python_entry_refuses_host_tensors_and_imports_no_oracle():
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
-    monkeypatch.setattr(_abi, "_train_lib", None)
-    monkeypatch.setattr(_abi, "TRAIN_LIB_PATH", str(tmp_path / "nope.so"))
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        _abi.load_train_library()
+    monkeypatch.delitem(_abi._side_libs, "train", raising=False)
+    monkeypatch.setitem(_abi.SIDE_LIBRARIES, "train", _abi.SIDE_LIBRARIES["train"]._replace(path=str(tmp_path / "nope.so")))
     from pvnet_amd import validation as V
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         V.head_grad_workspace_bytes(1, 8, 8)

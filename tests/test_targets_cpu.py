@@ -1,11 +1,12 @@
 """CPU-only checks of the targets from key-points (include/pvnet_targets.h, libpvnet_targets.so): the header's exports against the
 prototype table of pvnet_amd/_abi.py, the built library, every bad argument rejected with the documented code before any HIP call,
 the register rule for every new kernel, the Python entries' refusal of host tensors, and the float64 restatement against what the
-reference's own compute_vertex_hcoords returned (tests/golden/vertex_targets.npz), bit for bit."""
+reference's own compute_vertex_hcoords returned (tests/golden/vertex_targets.npz), bit for bit.
+What holds for every side library alike (header against table, the built library's symbols, the register tool's selection, the loud
+failure without it) is in tests/test_side_libraries_cpu.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -32,13 +33,7 @@ def lib():
 
 def test_header_declares_the_exports_and_every_one_has_a_prototype():
     returns = dict((n, t) for t, n in re.findall(r"^(int|size_t)\s+(pvnet_[a-z0-9_]+)\s*\(", HDR, re.M))
-    assert set(returns) == EXPORTS == set(_abi.TARGETS_PROTOTYPES)
-    want = {"int": C.c_int, "size_t": C.c_size_t}
-    for name, (restype, argtypes) in _abi.TARGETS_PROTOTYPES.items():
-        assert restype is want[returns[name]], name
-        decl = re.search(r"^(?:int|size_t)\s+%s\s*\((.*?)\);" % name, HDR, re.M | re.S).group(1)
-        n = 0 if decl.strip() == "void" else len(decl.split(","))
-        assert len(argtypes) == n, name   # one argument type per declared parameter
+    assert set(returns) == EXPORTS
     # byte counts are size_t, in and out
     assert _abi.TARGETS_PROTOTYPES["pvnet_head_metrics_kp_workspace_bytes"][0] is C.c_size_t
     assert _abi.TARGETS_PROTOTYPES["pvnet_head_grad_kp_workspace_bytes"][0] is C.c_size_t
@@ -51,12 +46,9 @@ def test_header_declares_the_exports_and_every_one_has_a_prototype():
     grad, kpg = _abi.TRAIN_PROTOTYPES["pvnet_head_grad"][1], _abi.TARGETS_PROTOTYPES["pvnet_head_grad_kp"][1]
     assert len(kpg) == len(grad) - 2 and kpg[:5] == grad[:5] and kpg[7:] == grad[9:]
     assert kp[14] is C.c_double and kpg[14] is C.c_double   # sigma
-    # a table of its own: the three other tables share no name with it
-    assert not set(_abi.TARGETS_PROTOTYPES) & (set(_abi.PROTOTYPES) | set(_abi.HEAD_PROTOTYPES) | set(_abi.TRAIN_PROTOTYPES))
     # it defines only what is new and includes pvnet_head.h for the rest
     assert re.findall(r"^#define\s+(PVNET_\w+)\s+\d+", HDR, re.M) == ["PVNET_TARGETS_ABI_VERSION", "PVNET_TARGETS_F_MOTION"]
     assert '#include "pvnet_head.h"' in HDR
-    assert int(re.search(r"^#define\s+PVNET_TARGETS_ABI_VERSION\s+(\d+)", HDR, re.M).group(1)) == _abi.TARGETS_ABI_VERSION
     motion = int(re.search(r"^#define\s+PVNET_TARGETS_F_MOTION\s+(\d+)", HDR, re.M).group(1))
     assert motion == _abi.TARGETS_F_MOTION
     head_flags = [int(v) for v in re.findall(r"^#define\s+PVNET_HEAD_F_\w+\s+(\d+)", open(os.path.join(ROOT, "include", "pvnet_head.h")).read(), re.M)]
@@ -64,23 +56,13 @@ def test_header_declares_the_exports_and_every_one_has_a_prototype():
 
 
 def test_library_is_built_for_gfx950_and_exports_the_symbols(lib):
-    assert os.path.exists(_abi.TARGETS_LIB_PATH) and _abi.TARGETS_LIB_PATH.endswith("libpvnet_targets.so")
-    raw = C.CDLL(_abi.TARGETS_LIB_PATH)
-    for name, (restype, argtypes) in _abi.TARGETS_PROTOTYPES.items():
-        assert hasattr(raw, name), name
-        fn = getattr(lib, name)   # bound once, at load
-        assert fn.restype is restype and list(fn.argtypes or []) == argtypes, name
     assert lib.pvnet_targets_abi_version() == _abi.TARGETS_ABI_VERSION == 1
     blob = open(_abi.TARGETS_LIB_PATH, "rb").read()
-    assert b"gfx950" in blob and all(k.encode() in blob for k in KERNELS)
-    assert build.TARGETS_TU == ["head_targets.hip"]
-    assert not set(build.TARGETS_TU) & (set(build.VOTE_TU) | set(build.HEAD_TU) | set(build.TRAIN_TU))
-    assert build.HEAD_TU == ["head_metrics.hip"] and build.TRAIN_TU == ["head_grad.hip"]   # the other libraries' shapes have not moved
-    # the other libraries do not export the new names, nor this one theirs
-    for path in (_abi.HEAD_LIB_PATH, _abi.TRAIN_LIB_PATH):
-        other = C.CDLL(path)
-        assert not any(hasattr(other, n) for n in EXPORTS)
-    assert not hasattr(raw, "pvnet_head_metrics") and not hasattr(raw, "pvnet_head_grad")
+    assert all(k.encode() in blob for k in KERNELS)
+    tu = {n: build.SIDE_LIBRARIES[n][0] for n in ("head", "train", "targets")}
+    assert tu["targets"] == ["head_targets.hip"]
+    assert not set(tu["targets"]) & (set(build.VOTE_TU) | set(tu["head"]) | set(tu["train"]))
+    assert tu["head"] == ["head_metrics.hip"] and tu["train"] == ["head_grad.hip"]   # the other libraries' shapes have not moved
 
 
 def test_workspace_bytes(lib):
@@ -160,41 +142,19 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
 
 
 def test_register_check_covers_the_new_translation_unit(lib):
-    tool = os.path.join(ROOT, "tools", "check_kernel_resources.py")
-    r = subprocess.run([sys.executable, tool, "--targets"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert all(k in r.stdout for k in KERNELS)
-    assert "head_partial_kernel" not in r.stdout and "head_grad_kernel" not in r.stdout   # --targets selects this library alone
-    assert int(re.search(r"checked (\d+) kernels, 0 without", r.stdout).group(1)) >= len(KERNELS)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_kernel_resources as chk
-    (src, text), = chk.targets_assembly()
+    (src, text), = chk.side_assembly("targets")
     assert src.endswith("head_targets.hip")
     ks = chk.kernels(text)
     for k in KERNELS:
         assert any(k in name for name, _, _, _ in ks), k
+    assert len(ks) >= len(KERNELS)
     for name, nfv, vmax, scratch in ks:
         assert nfv - (vmax + 1) >= chk.SLACK and scratch == 0, name
-    # the no-argument run includes the new library (the other libraries' assembly is left out here: their own tests compile it)
-    import contextlib
-    import io
-    saved = chk.assembly, chk.head_assembly, chk.train_assembly, chk.targets_assembly
-    chk.assembly = chk.head_assembly = chk.train_assembly = lambda: []
-    chk.targets_assembly = lambda: [(src, text)]
-    try:
-        buf = io.StringIO()
-        with contextlib.redirect_stdout(buf):
-            assert chk.main([]) == 0
-    finally:
-        chk.assembly, chk.head_assembly, chk.train_assembly, chk.targets_assembly = saved
-    assert all(k in buf.getvalue() for k in KERNELS)
-    # the two head libraries still pass with the shared header
-    for flag, names in (("--head", ("head_partial_kernel", "head_partial_general_kernel", "head_final_kernel")),
-                        ("--train", ("head_grad_wsum_kernel", "head_grad_final_kernel", "head_grad_kernel", "head_grad_general_kernel",
-                                     "head_grad_status_kernel"))):
-        r = subprocess.run([sys.executable, tool, flag], capture_output=True, text=True)
-        assert r.returncode == 0 and all(n in r.stdout for n in names), r.stdout[-2000:]
-        assert "_kp_" not in r.stdout
+    # the two head libraries hold none of these kernels
+    for other in ("head", "train"):
+        assert not any("_kp_" in name for _, asm in chk.side_assembly(other) for name, _, _, _ in chk.kernels(asm))
 
 
 def test_python_entries_refuse_host_tensors():
@@ -215,13 +175,6 @@ def test_python_entries_refuse_host_tensors():
     assert callable(V.ValStep.enqueue_from_keypoints)
     src = open(os.path.join(ROOT, "pvnet_amd", "validation.py")).read()
     assert not re.search(r"^\s*(from|import)\s+oracle", src, re.M)
-
-
-def test_missing_library_fails_loudly(monkeypatch, tmp_path):
-    monkeypatch.setattr(_abi, "_targets_lib", None)
-    monkeypatch.setattr(_abi, "TARGETS_LIB_PATH", str(tmp_path / "nope.so"))
-    with pytest.raises(RuntimeError, match="no CPU fallback"):
-        _abi.load_targets_library()
 
 
 def test_restatement_equals_the_reference_bit_for_bit():

@@ -1,20 +1,13 @@
-"""Build-time check of every kernel's register accounting (the translation units of libpvnet_vote.so, release and development build,
-the one of libpvnet_head.so, the one of libpvnet_train.so, the one of libpvnet_targets.so, the one of libpvnet_augment.so, the one of
-libpvnet_color.so, the one of libpvnet_classes.so and the one of libpvnet_raster.so).
+"""Build-time check of every kernel's register accounting: the translation units of libpvnet_vote.so, release and development build,
+and those of every side library (the rows of pvnet_amd.build.SIDE_LIBRARIES, one build each).
 
 Rule: a kernel must not use the last VGPR granule of its allocation -- `.amdhsa_next_free_vgpr` has to exceed the highest
 VGPR an instruction names by at least 8 (PVNET_SPARE_VGPRS in the sources provides the slack).  Background: round 2's
 compaction flake (profiles/r02_compaction_flake_investigation.txt): identical code failed in 98 % of the runs with an
 allocation that was used to the top and never with one granule more.
 
-    python tools/check_kernel_resources.py            # compiles the sources of the eight libraries to assembly (hipcc -S) and checks them
-    python tools/check_kernel_resources.py --head     # libpvnet_head.so's translation unit only (its build)
-    python tools/check_kernel_resources.py --train    # libpvnet_train.so's translation unit only (its build)
-    python tools/check_kernel_resources.py --targets  # libpvnet_targets.so's translation unit only (its build)
-    python tools/check_kernel_resources.py --augment  # libpvnet_augment.so's translation unit only (its build)
-    python tools/check_kernel_resources.py --color    # libpvnet_color.so's translation unit only (its build)
-    python tools/check_kernel_resources.py --classes  # libpvnet_classes.so's translation unit only (its build)
-    python tools/check_kernel_resources.py --raster   # libpvnet_raster.so's translation unit only (its build)
+    python tools/check_kernel_resources.py            # compiles the sources of all of them to assembly (hipcc -S) and checks them
+    python tools/check_kernel_resources.py --<name>   # one side library's translation units only (its build), e.g. --head
     python tools/check_kernel_resources.py a.s b.s
 
 Second rule: the kernels whose budget is set with `amdgpu_num_vgpr` (hypothesis_kernel, score_exact_kernel_*) rely on
@@ -97,8 +90,7 @@ def assembly():
 
 
 def side_assembly(name):
-    """[(translation unit, assembly text)] of one of build.SIDE_LIBRARIES (libpvnet_head.so, libpvnet_train.so, libpvnet_targets.so:
-    one build each, no development variant)"""
+    """[(translation unit, assembly text)] of one of build.SIDE_LIBRARIES (one build each, no development variant)"""
     sys.path.insert(0, ROOT)
     from pvnet_amd import build as B
     out = []
@@ -107,34 +99,6 @@ def side_assembly(name):
             compile_to_asm(src, os.path.join(d, f"{name}{k}.s"))
             out.append((src, open(os.path.join(d, f"{name}{k}.s")).read()))
     return out
-
-
-def head_assembly():
-    return side_assembly("head")
-
-
-def train_assembly():
-    return side_assembly("train")
-
-
-def targets_assembly():
-    return side_assembly("targets")
-
-
-def augment_assembly():
-    return side_assembly("augment")
-
-
-def color_assembly():
-    return side_assembly("color")
-
-
-def classes_assembly():
-    return side_assembly("classes")
-
-
-def raster_assembly():
-    return side_assembly("raster")
 
 
 def kernel_code(text):
@@ -172,25 +136,14 @@ def release_differs_from_dev(pairs):
 
 
 def main(argv):
-    if argv == ["--head"]:
-        texts = [t for _, t in head_assembly()]
-    elif argv == ["--train"]:
-        texts = [t for _, t in train_assembly()]
-    elif argv == ["--targets"]:
-        texts = [t for _, t in targets_assembly()]
-    elif argv == ["--augment"]:
-        texts = [t for _, t in augment_assembly()]
-    elif argv == ["--color"]:
-        texts = [t for _, t in color_assembly()]
-    elif argv == ["--classes"]:
-        texts = [t for _, t in classes_assembly()]
-    elif argv == ["--raster"]:
-        texts = [t for _, t in raster_assembly()]
+    sys.path.insert(0, ROOT)
+    from pvnet_amd import build as B
+    if len(argv) == 1 and argv[0].startswith("--") and argv[0][2:] in B.SIDE_LIBRARIES:
+        texts = [t for _, t in side_assembly(argv[0][2:])]
+    elif argv:
+        texts = [open(a).read() for a in argv]
     else:
-        texts = [open(a).read() for a in argv] if argv else \
-            [t for _, _, t in assembly()] + [t for _, t in head_assembly()] + [t for _, t in train_assembly()] + \
-            [t for _, t in targets_assembly()] + [t for _, t in augment_assembly()] + [t for _, t in color_assembly()] + [t for _, t in classes_assembly()] + \
-            [t for _, t in raster_assembly()]
+        texts = [t for _, _, t in assembly()] + [t for name in B.SIDE_LIBRARIES for _, t in side_assembly(name)]
     bad = 0
     n = 0
     done = set()
