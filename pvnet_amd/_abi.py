@@ -227,6 +227,20 @@ RASTER_PROTOTYPES = {
                      [_ptr, _ptr, _ptr, _ptr, _size, _ptr]),
 }
 
+# ---- libpvnet_depth.so (include/pvnet_depth.h): poses and meshes -> depth, occlusion-correct labels, visible pixel counts -------------
+DEPTH_LIB_PATH = os.path.join(_HERE, "libpvnet_depth.so")
+DEPTH_ABI_VERSION = 1
+DEPTH_LANE_PIXELS = 64       # as RASTER_LANE_PIXELS
+DEPTH_MAX_INSTANCES, DEPTH_MAX_MESHES, DEPTH_MAX_IMAGES, DEPTH_MAX_SIDE = 768, 64, 65535, 32768   # the limits of pvnet_render
+DEPTH_S_NONFINITE, DEPTH_S_BEHIND, DEPTH_S_BADFACE = 1, 2, 4
+DEPTH_PROTOTYPES = {
+    "pvnet_depth_abi_version": (_int, []),
+    "pvnet_depth_workspace_bytes": (_size, [_int] * 6),   # q, P, T, b, h, w
+    # vertices, faces, vertex_offset, face_offset (host), M, P, T, q, mesh_id (host), poses, K, k_per_instance, image_id, label (host),
+    # b, h, w, far, depth_out, label_out, visible_out, status_out, workspace + bytes, stream
+    "pvnet_render_depth": (_int, [_ptr, _ptr, _i32p, _i32p] + [_int] * 4 + [_i32p, _ptr, _ptr, _int, _i32p, _i32p] + [_int] * 3 +
+                           [_f32, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr]),
+}
 
 
 class SideLibrary(NamedTuple):
@@ -244,6 +258,7 @@ SIDE_LIBRARIES = {
     "color": SideLibrary(COLOR_LIB_PATH, COLOR_ABI_VERSION, COLOR_PROTOTYPES),
     "classes": SideLibrary(CLASSES_LIB_PATH, CLASSES_ABI_VERSION, CLASSES_PROTOTYPES),
     "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
+    "depth": SideLibrary(DEPTH_LIB_PATH, DEPTH_ABI_VERSION, DEPTH_PROTOTYPES),
 }
 
 _lib = None
@@ -307,6 +322,7 @@ load_augment_library = functools.partial(_load_side, "augment")
 load_color_library = functools.partial(_load_side, "color")
 load_classes_library = functools.partial(_load_side, "classes")
 load_raster_library = functools.partial(_load_side, "raster")
+load_depth_library = functools.partial(_load_side, "depth")
 
 
 def reload_tuning():

@@ -32,6 +32,7 @@ ARCH = "gfx950"
 # stays as it is.  One row per library, under the name pvnet_amd._abi.SIDE_LIBRARIES binds it by:
 # name -> (translation units, its header under include/, what they include beyond that header and the common ones)
 _AUGMENT_WARP = os.path.join(CSRC, "augment_warp.h")   # the one copy of the plan and the warp: the two libraries that compile it rebuild with it
+_RASTER_COMMON = os.path.join(CSRC, "raster_common.h")   # the one copy of the projection and the coverage predicate, likewise
 SIDE_LIBRARIES = {
     "head": (["head_metrics.hip"], "pvnet_head.h", []),          # the head metrics of a validation step
     "train": (["head_grad.hip"], "pvnet_train.h", []),           # the backward of the head losses of a training step
@@ -40,7 +41,8 @@ SIDE_LIBRARIES = {
     "color": (["color_jitter.hip"], "pvnet_color.h",              # the colour jitter, alone or fused behind that warp
               [_AUGMENT_WARP, os.path.join(ROOT, "include", "pvnet_augment.h")]),
     "classes": (["class_split.hip"], "pvnet_classes.h", []),     # class labels -> the bit masks the voting layer runs on
-    "raster": (["raster.hip"], "pvnet_raster.h", []),            # poses and meshes -> silhouettes and label images
+    "raster": (["raster.hip"], "pvnet_raster.h", [_RASTER_COMMON]),   # poses and meshes -> silhouettes and label images
+    "depth": (["depth.hip"], "pvnet_depth.h", [_RASTER_COMMON]),      # ... -> depth, occlusion-correct labels, visible pixel counts
 }
 
 
