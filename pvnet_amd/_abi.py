@@ -242,6 +242,24 @@ DEPTH_PROTOTYPES = {
                            [_f32, _ptr, _ptr, _ptr, _ptr, _ptr, _size, _ptr]),
 }
 
+# ---- libpvnet_shade.so (include/pvnet_shade.h): poses and coloured meshes -> shaded images over a background, with depth's outputs -----
+SHADE_LIB_PATH = os.path.join(_HERE, "libpvnet_shade.so")
+SHADE_ABI_VERSION = 1
+SHADE_LANE_PIXELS = 64       # as DEPTH_LANE_PIXELS
+SHADE_MAX_INSTANCES, SHADE_MAX_MESHES, SHADE_MAX_IMAGES, SHADE_MAX_SIDE = 768, 64, 65535, 32768   # the limits of pvnet_render_depth
+SHADE_MAX_FACES = 1 << 22    # faces of one mesh: the face index has 22 bits of the z-buffer's word
+SHADE_S_NONFINITE, SHADE_S_BEHIND, SHADE_S_BADFACE = 1, 2, 4
+SHADE_NONE, SHADE_FLAT, SHADE_PHONG = 0, 1, 2
+_u8p = C.POINTER(C.c_uint8)   # host array: the background colour
+SHADE_PROTOTYPES = {
+    "pvnet_shade_abi_version": (_int, []),
+    "pvnet_shade_workspace_bytes": (_size, [_int] * 6),   # q, P, T, b, h, w
+    # pvnet_render_depth's arguments through far, then colors, normals, shading, ambient, bg_color (host), bg_image, rgb_out, then
+    # depth_out, label_out, visible_out, status_out, workspace + bytes, stream
+    "pvnet_render_color": (_int, DEPTH_PROTOTYPES["pvnet_render_depth"][1][:18] + [_ptr, _ptr, _int, _f32, _u8p, _ptr, _ptr] +
+                           DEPTH_PROTOTYPES["pvnet_render_depth"][1][18:]),
+}
+
 
 class SideLibrary(NamedTuple):
     path: str
@@ -259,6 +277,7 @@ SIDE_LIBRARIES = {
     "classes": SideLibrary(CLASSES_LIB_PATH, CLASSES_ABI_VERSION, CLASSES_PROTOTYPES),
     "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
     "depth": SideLibrary(DEPTH_LIB_PATH, DEPTH_ABI_VERSION, DEPTH_PROTOTYPES),
+    "shade": SideLibrary(SHADE_LIB_PATH, SHADE_ABI_VERSION, SHADE_PROTOTYPES),
 }
 
 _lib = None
@@ -323,6 +342,7 @@ load_color_library = functools.partial(_load_side, "color")
 load_classes_library = functools.partial(_load_side, "classes")
 load_raster_library = functools.partial(_load_side, "raster")
 load_depth_library = functools.partial(_load_side, "depth")
+load_shade_library = functools.partial(_load_side, "shade")
 
 
 def reload_tuning():

@@ -33,6 +33,8 @@ ARCH = "gfx950"
 # name -> (translation units, its header under include/, what they include beyond that header and the common ones)
 _AUGMENT_WARP = os.path.join(CSRC, "augment_warp.h")   # the one copy of the plan and the warp: the two libraries that compile it rebuild with it
 _RASTER_COMMON = os.path.join(CSRC, "raster_common.h")   # the one copy of the projection and the coverage predicate, likewise
+_MESH_STAGES = os.path.join(CSRC, "mesh_stages.h")       # ... whose bodies live here: raster_common.h includes it, shade.hip directly
+_DEPTH_PLANE = os.path.join(CSRC, "depth_plane.h")       # the one copy of the depth of a covered pixel: depth.hip and shade.hip
 SIDE_LIBRARIES = {
     "head": (["head_metrics.hip"], "pvnet_head.h", []),          # the head metrics of a validation step
     "train": (["head_grad.hip"], "pvnet_train.h", []),           # the backward of the head losses of a training step
@@ -41,8 +43,10 @@ SIDE_LIBRARIES = {
     "color": (["color_jitter.hip"], "pvnet_color.h",              # the colour jitter, alone or fused behind that warp
               [_AUGMENT_WARP, os.path.join(ROOT, "include", "pvnet_augment.h")]),
     "classes": (["class_split.hip"], "pvnet_classes.h", []),     # class labels -> the bit masks the voting layer runs on
-    "raster": (["raster.hip"], "pvnet_raster.h", [_RASTER_COMMON]),   # poses and meshes -> silhouettes and label images
-    "depth": (["depth.hip"], "pvnet_depth.h", [_RASTER_COMMON]),      # ... -> depth, occlusion-correct labels, visible pixel counts
+    "raster": (["raster.hip"], "pvnet_raster.h", [_RASTER_COMMON, _MESH_STAGES]),   # poses and meshes -> silhouettes and label images
+    "depth": (["depth.hip"], "pvnet_depth.h", [_RASTER_COMMON, _MESH_STAGES, _DEPTH_PLANE]),   # ... -> depth, occlusion-correct labels,
+                                                                                               # visible pixel counts
+    "shade": (["shade.hip"], "pvnet_shade.h", [_MESH_STAGES, _DEPTH_PLANE]),   # ... -> shaded vertex-colour images over a background
 }
 
 

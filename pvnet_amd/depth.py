@@ -51,6 +51,13 @@ def _out(out, shape, dtype, dev, what):
     return out
 
 
+def _image_stretches(b, m, limit):
+    """(first image, end) of every stretch of whole images with at most ``limit`` instances, m per image: one library call each
+    (``shade.render_color`` splits the same way)"""
+    images = max(1, limit // m) if m else max(b, 1)
+    return [(i0, min(b, i0 + images)) for i0 in range(0, b, images)]
+
+
 def _render(meshes, mesh_ids, labels, poses, K, h, w, far, depth, label, visible, status, workspace):
     """one pvnet_render_depth call per stretch of whole images with at most DEPTH_MAX_INSTANCES instances; ``poses`` [b,m,3,4]"""
     lib = load_depth_library()
@@ -59,10 +66,8 @@ def _render(meshes, mesh_ids, labels, poses, K, h, w, far, depth, label, visible
     Kd, per = _camera(K, dev, (b, m))
     vertices, faces, _ = meshes.on(dev)
     flat = poses.view(-1, 3, 4)
-    images = max(1, DEPTH_MAX_INSTANCES // m) if m else max(b, 1)   # images per call
     with torch.cuda.device(dev):
-        for i0 in range(0, b, images):
-            i1 = min(b, i0 + images)
+        for i0, i1 in _image_stretches(b, m, DEPTH_MAX_INSTANCES):
             nb, n = i1 - i0, (i1 - i0) * m
             s = i0 * m
             ws = _workspace(workspace, depth_workspace_bytes(n, nb, h, w, meshes), dev, align=16, sized=True)
@@ -76,7 +81,7 @@ def _render(meshes, mesh_ids, labels, poses, K, h, w, far, depth, label, visible
                 _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_render_depth")
 
 
-def _checked(meshes, mesh_ids, labels, poses, h, w, far):
+def _checked(meshes, mesh_ids, labels, poses, h, w, far, limit=DEPTH_MAX_INSTANCES):
     if not isinstance(meshes, DeviceMeshes):
         raise RuntimeError("meshes must be a DeviceMeshes")
     dev = poses.device if isinstance(poses, torch.Tensor) else None
@@ -89,8 +94,8 @@ def _checked(meshes, mesh_ids, labels, poses, h, w, far):
         raise RuntimeError("labels must lie in 1 .. 255")
     if h < 2 or w < 2:
         raise RuntimeError("h and w must be at least 2")
-    if m > DEPTH_MAX_INSTANCES:
-        raise RuntimeError(f"at most {DEPTH_MAX_INSTANCES} instances per image")
+    if m > limit:
+        raise RuntimeError(f"at most {limit} instances per image")
     if math.isnan(far) or not float(np.float32(far)) > 0:
         raise RuntimeError("far must be a positive float32 (not NaN)")
     return mesh_ids, labels, poses, h, w, far
