@@ -10,4 +10,13 @@ from .voting import (estimate_voting_distribution_with_mean, generate_hypothesis
                      generate_hypothesis_counts, load_library, ransac_motion_voting, ransac_voting_layer_v3,
                      ransac_voting_layer_v5, voting_for_hypothesis)
 
-__all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library"]
+_TEXTURE = ("TexturedMeshes", "render_textured", "read_textured_ply", "texture_workspace_bytes")   # pvnet_amd.texture, on first use
+
+__all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE]
+
+
+def __getattr__(name):
+    if name in _TEXTURE:
+        from . import texture
+        return getattr(texture, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -260,6 +260,25 @@ SHADE_PROTOTYPES = {
                            DEPTH_PROTOTYPES["pvnet_render_depth"][1][18:]),
 }
 
+# ---- libpvnet_texture.so (include/pvnet_texture.h): pvnet_render_color with UV-mapped textures; a mesh without one is shaded as there ----
+TEXTURE_LIB_PATH = os.path.join(_HERE, "libpvnet_texture.so")
+TEXTURE_ABI_VERSION = 1
+TEXTURE_LANE_PIXELS = 64     # as SHADE_LANE_PIXELS
+TEXTURE_MAX_INSTANCES, TEXTURE_MAX_MESHES, TEXTURE_MAX_IMAGES, TEXTURE_MAX_IMAGE_SIDE = 768, 64, 65535, 32768   # pvnet_render_color's
+TEXTURE_MAX_FACES = 1 << 22  # as SHADE_MAX_FACES
+TEXTURE_MAX_SIDE = 16384     # texels along one side of one texture; the table holds fewer than 2^31 texels
+TEXTURE_S_NONFINITE, TEXTURE_S_BEHIND, TEXTURE_S_BADFACE = 1, 2, 4
+TEXTURE_SHADING_NONE, TEXTURE_SHADING_FLAT, TEXTURE_SHADING_PHONG = 0, 1, 2
+TEXTURE_NEAREST, TEXTURE_BILINEAR = 0, 1
+_i64p = C.POINTER(C.c_int64)  # host array: the texel offsets
+TEXTURE_PROTOTYPES = {
+    "pvnet_texture_abi_version": (_int, []),
+    "pvnet_texture_workspace_bytes": (_size, [_int] * 6),   # q, P, T, b, h, w
+    # pvnet_render_color's arguments through normals, then uv, texels, tex_offset, tex_h, tex_w (host), filter, then its from shading on
+    "pvnet_render_textured": (_int, SHADE_PROTOTYPES["pvnet_render_color"][1][:20] + [_ptr, _ptr, _i64p, _i32p, _i32p, _int] +
+                              SHADE_PROTOTYPES["pvnet_render_color"][1][20:]),
+}
+
 
 class SideLibrary(NamedTuple):
     path: str
@@ -278,6 +297,7 @@ SIDE_LIBRARIES = {
     "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
     "depth": SideLibrary(DEPTH_LIB_PATH, DEPTH_ABI_VERSION, DEPTH_PROTOTYPES),
     "shade": SideLibrary(SHADE_LIB_PATH, SHADE_ABI_VERSION, SHADE_PROTOTYPES),
+    "texture": SideLibrary(TEXTURE_LIB_PATH, TEXTURE_ABI_VERSION, TEXTURE_PROTOTYPES),
 }
 
 _lib = None
@@ -343,6 +363,7 @@ load_classes_library = functools.partial(_load_side, "classes")
 load_raster_library = functools.partial(_load_side, "raster")
 load_depth_library = functools.partial(_load_side, "depth")
 load_shade_library = functools.partial(_load_side, "shade")
+load_texture_library = functools.partial(_load_side, "texture")
 
 
 def reload_tuning():

@@ -35,6 +35,8 @@ _AUGMENT_WARP = os.path.join(CSRC, "augment_warp.h")   # the one copy of the pla
 _RASTER_COMMON = os.path.join(CSRC, "raster_common.h")   # the one copy of the projection and the coverage predicate, likewise
 _MESH_STAGES = os.path.join(CSRC, "mesh_stages.h")       # ... whose bodies live here: raster_common.h includes it, shade.hip directly
 _DEPTH_PLANE = os.path.join(CSRC, "depth_plane.h")       # the one copy of the depth of a covered pixel: depth.hip and shade.hip
+_MESH_CORE = os.path.join(CSRC, "mesh_core.h")           # the bodies behind mesh_stages.h: texture.hip includes them by this name
+_DEPTH_CORE = os.path.join(CSRC, "depth_core.h")         # the bodies behind depth_plane.h, likewise
 SIDE_LIBRARIES = {
     "head": (["head_metrics.hip"], "pvnet_head.h", []),          # the head metrics of a validation step
     "train": (["head_grad.hip"], "pvnet_train.h", []),           # the backward of the head losses of a training step
@@ -47,15 +49,24 @@ SIDE_LIBRARIES = {
     "depth": (["depth.hip"], "pvnet_depth.h", [_RASTER_COMMON, _MESH_STAGES, _DEPTH_PLANE]),   # ... -> depth, occlusion-correct labels,
                                                                                                # visible pixel counts
     "shade": (["shade.hip"], "pvnet_shade.h", [_MESH_STAGES, _DEPTH_PLANE]),   # ... -> shaded vertex-colour images over a background
+    "texture": (["texture.hip"], "pvnet_texture.h", [_MESH_CORE, _DEPTH_CORE]),   # ... -> the same with UV-mapped textures
 }
 
 
 def _side(name):
-    """(sources, what they depend on, the library) of one of SIDE_LIBRARIES"""
+    """(sources, what they depend on, the library) of one of SIDE_LIBRARIES.  The dependencies are the row's, closed under
+    ``#include "..."`` of files in csrc/: a header that one of them includes rebuilds the library without being listed in its row."""
     tu, header, extra = SIDE_LIBRARIES[name]
     src = [os.path.join(CSRC, f) for f in tu]
     deps = src + [os.path.join(CSRC, f) for f in ("head_common.h", "vote_common.h", "pvnet_rng.h")] + \
         [os.path.join(ROOT, "include", f) for f in sorted({header, "pvnet_head.h", "pvnet_vote.h"})] + extra
+    for d in deps:   # (grows while it is walked)
+        if os.path.dirname(d) == CSRC and os.path.exists(d):
+            with open(d) as fh:
+                for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', fh.read(), re.M):
+                    path = os.path.join(CSRC, inc)
+                    if os.path.exists(path) and path not in deps:
+                        deps.append(path)
     return src, deps, os.path.join(HERE, f"libpvnet_{name}.so")
 
 

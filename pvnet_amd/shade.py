@@ -14,7 +14,7 @@ shading.  Here:
                                colours, triangular faces): what ``LineModModelDB.get_ply_mesh`` reads with the ``plyfile`` package.
 
 pvnet_amd/csrc/shade.hip, libpvnet_shade.so; C ABI and THE DEFINITION: include/pvnet_shade.h; a numpy restatement:
-tests/shade_restatement.py.  Textures are not built.  Poses are float64 ``[b,m,3,4]`` (``pnp_batch_device``'s output is read in place).
+tests/shade_restatement.py.  Textured meshes: pvnet_amd/texture.py, a library of its own.  Poses are float64 ``[b,m,3,4]`` (``pnp_batch_device``'s output is read in place).
 
 Everything is enqueued on the current stream without synchronising; with caller-owned outputs and ``workspace`` a call is capturable
 in a graph.  PyTorch is plumbing only.  There is NO CPU fallback: without the library, or with CPU tensors, these raise ``RuntimeError``.
@@ -190,6 +190,12 @@ def read_ply(path):
     """An ASCII or binary_little_endian PLY file -> ``{"vertices": [P,3] float64, "faces": [T,3] int32, "normals": [P,3] float64 or
     None, "colors": [P,3] uint8 or None}``.  Reads the vertex properties ``x y z``, ``nx ny nz`` and ``red green blue`` (others are
     skipped) and the face element's list property (``vertex_indices`` / ``vertex_index``), whose lists must all have three entries."""
+    return _read_ply(path)[0]
+
+
+def _read_ply(path):
+    """(what ``read_ply`` returns, ``cols``: (property names, dtype) -> those vertex properties as columns, or None when one is missing):
+    the parser behind ``read_ply`` and ``texture.read_textured_ply``"""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header")
@@ -252,4 +258,4 @@ def read_ply(path):
 
     faces = tables.get("face")
     return {"vertices": cols("xyz", np.float64), "faces": faces if faces is not None else np.zeros((0, 3), np.int32),
-            "normals": cols(("nx", "ny", "nz"), np.float64), "colors": cols(("red", "green", "blue"), np.uint8)}
+            "normals": cols(("nx", "ny", "nz"), np.float64), "colors": cols(("red", "green", "blue"), np.uint8)}, cols
