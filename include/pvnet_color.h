@@ -3,12 +3,24 @@
  *
  * Every training sample of the reference passes through transforms.ColorJitter(brightness, contrast, saturation, hue)
  * (lib/datasets/linemod_dataset.py:185-190, applied at :233-234) between the geometric augmentation and ToTensor + Normalize.  Its
- * arithmetic lives in torchvision 0.2.1 and Pillow, which are not part of the reference tree.  THE DEFINITION below is THIS PROJECT'S
- * OWN: it follows their structure -- a uint8 image after every step, truncating blends, an integer luma, a random order of the four
- * steps, contrast about the mean luma of the whole image -- but not Pillow's fixed-point arithmetic, from which it may differ by a
- * grey level (the hue step's HSV round trip and the blends' rounding in particular).  Nothing was recorded from Pillow; the header,
- * its numpy restatement (tests/color_restatement.py) and the kernels (pvnet_amd/csrc/color_jitter.hip) are held to each other bit
- * for bit.
+ * arithmetic lives in torchvision 0.2.1 and Pillow, which are not part of the reference tree: adjust_brightness, adjust_contrast and
+ * adjust_saturation are ImageEnhance.Brightness, .Contrast and .Color, adjust_hue is convert('HSV'), a wrapped uint8 add on H and
+ * convert('RGB').  THE DEFINITION below is THIS PROJECT'S OWN TEXT of that arithmetic, one IEEE operation per step, and it is held to
+ * Pillow byte for byte.  Checked against Pillow 12.2.0 (tests/test_color_cpu.py, through tests/pillow_jitter_oracle.py, which
+ * restates torchvision's four functions with Pillow calls alone):
+ *   - steps B, S and C (the mean luma m included) equal ImageEnhance's result in every byte of the images and factors tested;
+ *   - step H's forward conversion equals convert('HSV') on all 2^24 colours, and its back conversion equals convert('RGB') on
+ *     every (h, s, v) that the forward conversion produces, under every shift of h;
+ *   - the float32 product of the shift lands on the integer of torchvision's double product for every factor tested;
+ *   - the whole chain equals torchvision's for all 24 orders and every subset of absent steps.
+ * tests/golden/color_pillow.npz is the record: Pillow's bytes for 48 chains over an image of the colours on which a float32-only
+ * hue differs from Pillow's, which the kernels (pvnet_amd/csrc/color_jitter.hip) reproduce on the device.  The header, its numpy
+ * restatement (tests/color_restatement.py) and the kernels are held to each other bit for bit.
+ *
+ * The values of step H changed without a change of PVNET_COLOR_ABI_VERSION (no signature or layout changed; this text is the
+ * record).  Before, H's forward hue was computed in float32 throughout, which gives another h than Pillow on 72 036 of the 2^24
+ * colours (one step of h, up to 6 grey levels after the back conversion), and the back conversion's f was x - floor(x) of the
+ * float32 x = ((float)h 6f) / 255f, which gives another byte than Pillow on two (h, s, v).
  *
  * `blur` needs no kernel: the reference calls blur_image(rgb, k) at linemod_dataset.py:232 and discards what it returns
  * (augmentation.py:204-205 returns a new array), so `blur: true` changes no pixel.
@@ -37,15 +49,20 @@
  *   H  to HSV:  maxc, minc of (r,g,b), v = maxc.  minc == maxc: h = s = 0.  Otherwise cr = maxc - minc,
  *        s = trunc((255f (float)cr) / (float)maxc),
  *        rc = (float)(maxc - r) / (float)cr, gc and bc likewise,
- *        t = bc - gc if r == maxc, else (2f + rc) - bc if g == maxc, else (4f + gc) - rc,
- *        x = t / 6f + 1f,  hf = x - floor(x),  h = trunc(hf 255f).
+ *        t = bc - gc in float32 if r == maxc; else (2.0 + (double)rc) - (double)bc if g == maxc, else (4.0 + (double)gc) -
+ *        (double)rc: two float64 operations, the result rounded once to float32          (Pillow's C: double literals, float variables)
+ *        x = (double)t / 6.0 + 1.0 in float64 (a true division, no reciprocal, not contracted),
+ *        hf = x - floor(x) in float64, rounded once to float32,  h = trunc((double)hf 255.0).
  *      the shift:  h <- (h + (trunc(fh 255f) mod 256)) mod 256        (mod with a non-negative result)
  *      back to RGB:  s == 0: r = g = b = v.  Otherwise
- *        x = ((float)h 6f) / 255f,  i = floor(x),  f = x - i,  sg = (float)s / 255f,  fv = (float)v,
+ *        i = (6 h) / 255 by integer division (0 .. 6),  f = (float)(6 h - 255 i) / 255f  (for each of the 256 h the float32 that
+ *        Pillow's (float)((float)h 6.0 / 255.0 - i) is),  sg = (float)s / 255f,  fv = (float)v,
  *        p  = clip(rint(fv (1f - sg)), 0, 255),
  *        q  = clip(rint(fv (1f - sg f)), 0, 255),
  *        t' = clip(rint(fv (1f - sg (1f - f))), 0, 255),
  *      (r,g,b) = (v,t',p), (q,v,p), (p,v,t'), (p,q,v), (t',p,v), (v,p,q) for i mod 6 = 0 .. 5.
+ *      (Pillow forms p, q and t' with float64 products and round(); with this f the float32 products and rint give the same
+ *      bytes on all 2^24 (h, s, v).)
  *   Normalise:  ((float)c / 255f - mean_c) / std_c  in float32, rounded once to the output type: the last line of
  *   include/pvnet_augment.h.  Where a mask is given and maskmul of the image is not 0, the float32 value is multiplied by
  *   (float)mask before that rounding (the reference's use_mask_out, applied after its transforms: linemod_dataset.py:237-238).

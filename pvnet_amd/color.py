@@ -10,8 +10,8 @@ Every training sample of the reference passes through ``transforms.ColorJitter(b
   (``pvnet_augment_jitter``; the plan and the warp are the code ``augment_batch`` runs);
 * ``training_configs_from_reference`` -- the reference's JSON as it stands -> ``(AugmentConfig, ColorJitterConfig or None)``.
 
-pvnet_amd/csrc/color_jitter.hip, libpvnet_color.so; C ABI and THE DEFINITION: include/pvnet_color.h (this project's own definition: it
-follows torchvision 0.2.1 and Pillow in structure, not in their fixed-point arithmetic, from which it may differ by a grey level); a
+pvnet_amd/csrc/color_jitter.hip, libpvnet_color.so; C ABI and THE DEFINITION: include/pvnet_color.h (this project's own text of
+torchvision 0.2.1's and Pillow's arithmetic, held to Pillow byte for byte: tests/pillow_jitter_oracle.py, tests/golden/color_pillow.npz); a
 numpy restatement: tests/color_restatement.py.
 
 ``blur`` needs no kernel: the reference calls ``blur_image(rgb, k)`` at linemod_dataset.py:232 and discards what it returns

@@ -125,22 +125,25 @@ __device__ __forceinline__ void hue_step(int& r, int& g, int& b, int hshift) {
         const float fcr = (float)cr;
         s = (int)((255.0f * fcr) / (float)maxc);
         const float rc = (float)(maxc - r) / fcr, gc = (float)(maxc - g) / fcr, bc = (float)(maxc - b) / fcr;
-        float t;
-        if (r == maxc) t = bc - gc;
-        else if (g == maxc) t = (2.0f + rc) - bc;
-        else t = (4.0f + gc) - rc;
-        const float x = t / 6.0f + 1.0f;
-        const float hf = x - floorf(x);
-        h = (int)(hf * 255.0f);
+        // Pillow writes the hue with double literals and float variables: the sums of the g and b branches, the division by 6 and
+        // the fractional part are float64 operations (uncontracted, a true division), each result rounded once to float32
+        // One pair of float64 operations for the three branches: the operands are selected first, and the r branch adds 0.0.  Its
+        // float64 sum and difference are exact (two float32 quotients in 0 .. 1), so the one rounding gives the float32 bc - gc.
+        const bool rmax = r == maxc, gmax = g == maxc;
+        const float ta = rmax ? bc : (gmax ? rc : gc), tb = rmax ? gc : (gmax ? bc : rc);
+        const double base = rmax ? 0.0 : (gmax ? 2.0 : 4.0);
+        const float t = (float)((base + (double)ta) - (double)tb);
+        const double x = (double)t / 6.0 + 1.0;
+        const float hf = (float)(x - floor(x));
+        h = (int)((double)hf * 255.0);
     }
     h = (h + hshift) & 255;
     if (s == 0) {
         r = g = b = v;
         return;
     }
-    const float x = ((float)h * 6.0f) / 255.0f;
-    const float fi = floorf(x);
-    const float f = x - fi;
+    int i = (6 * h) / 255;   // 0 .. 6
+    const float f = (float)(6 * h - 255 * i) / 255.0f;
     const float sg = (float)s / 255.0f, fv = (float)v;
     const float a1 = 1.0f - sg;
     const int p = clip_rint(fv * a1);
@@ -148,7 +151,6 @@ __device__ __forceinline__ void hue_step(int& r, int& g, int& b, int hshift) {
     const int q = clip_rint(fv * a2);
     const float g1 = 1.0f - f, sg1 = sg * g1, a3 = 1.0f - sg1;
     const int t2 = clip_rint(fv * a3);
-    int i = (int)fi;   // 0 .. 6
     i = i >= 6 ? i - 6 : i;
     r = i == 0 || i == 5 ? v : (i == 1 ? q : (i == 4 ? t2 : p));
     g = i == 1 || i == 2 ? v : (i == 0 ? t2 : (i == 3 ? q : p));

@@ -1,6 +1,7 @@
-"""numpy restatement of THE DEFINITION of include/pvnet_color.h, written from the header alone: float32 and integers, one operation
-per step in the header's order.  The kernels of pvnet_amd/csrc/color_jitter.hip are held to it bit for bit (tests/test_color_device.py);
-its own properties are checked on the CPU (tests/test_color_cpu.py)."""
+"""numpy restatement of THE DEFINITION of include/pvnet_color.h, written from the header alone: float32, float64 where the header
+says so, and integers, one operation per step in the header's order.  The kernels of pvnet_amd/csrc/color_jitter.hip are held to it
+bit for bit (tests/test_color_device.py); it is held to Pillow byte for byte, and its own properties are checked, on the CPU
+(tests/test_color_cpu.py, tests/pillow_jitter_oracle.py)."""
 import itertools
 
 import numpy as np
@@ -66,7 +67,10 @@ def clip_rint(x):
     return np.clip(np.rint(x), F(0), F(255)).astype(np.int64)
 
 
-def hue_step(img, fh):
+def rgb_to_hsv(img, float32_only=False):
+    """img [..., 3] integers -> (h, s, v), integers 0 .. 255: the forward conversion of step H.  float32_only: the hue as this
+    project defined it before it was held to Pillow (every operation in float32), kept so that the tests can find the colours on
+    which the two differ."""
     img = img.astype(np.int64)
     r, g, b = img[..., 0], img[..., 1], img[..., 2]
     maxc, minc = img.max(-1), img.min(-1)
@@ -77,28 +81,62 @@ def hue_step(img, fh):
     fmax = np.where(grey, 1, maxc).astype(np.float32)
     s = ((F(255) * fcr) / fmax).astype(np.int64)
     rc, gc, bc = ((maxc - ch).astype(np.float32) / fcr for ch in (r, g, b))
-    t = np.where(r == maxc, bc - gc, np.where(g == maxc, (F(2) + rc) - bc, (F(4) + gc) - rc))
-    x = t / F(6) + F(1)
-    hf = x - np.floor(x)
-    h = (hf * F(255)).astype(np.int64)
-    assert x.dtype == np.float32 and hf.dtype == np.float32
-    h, s = np.where(grey, 0, h), np.where(grey, 0, s)
-    shift = int(F(fh) * F(255)) % 256                     # int() truncates; % gives a non-negative result
-    h = (h + shift) % 256
-    x = (h.astype(np.float32) * F(6)) / F(255)
-    fi = np.floor(x)
-    f = x - fi
+    assert rc.dtype == np.float32
+    if float32_only:
+        t = np.where(r == maxc, bc - gc, np.where(g == maxc, (F(2) + rc) - bc, (F(4) + gc) - rc))
+        x = t / F(6) + F(1)
+        hf = x - np.floor(x)
+        h = (hf * F(255)).astype(np.int64)
+        assert x.dtype == np.float32 and hf.dtype == np.float32
+    else:
+        D = np.float64
+        rd, gd, bd = rc.astype(D), gc.astype(D), bc.astype(D)
+        t = np.where(r == maxc, bc - gc, np.where(g == maxc, ((D(2) + rd) - bd).astype(np.float32), ((D(4) + gd) - rd).astype(np.float32)))
+        assert t.dtype == np.float32
+        x = t.astype(D) / D(6) + D(1)
+        hf = (x - np.floor(x)).astype(np.float32)         # float64, rounded once
+        h = (hf.astype(D) * D(255)).astype(np.int64)
+    return np.where(grey, 0, h), np.where(grey, 0, s), v
+
+
+def hue_shift(fh):
+    """the float32 factor -> 0 .. 255: one float32 product, truncated toward zero, with a non-negative remainder"""
+    return int(F(fh) * F(255)) % 256
+
+
+def hsv_to_rgb(h, s, v):
+    """integer arrays 0 .. 255 -> [..., 3]: the back conversion of step H"""
+    h, s, v = (np.asarray(a, np.int64) for a in (h, s, v))
+    i = (6 * h) // 255                                    # 0 .. 6
+    f = (6 * h - 255 * i).astype(np.float32) / F(255)
     sg, fv = s.astype(np.float32) / F(255), v.astype(np.float32)
     p = clip_rint(fv * (F(1) - sg))
     q = clip_rint(fv * (F(1) - sg * f))
     t2 = clip_rint(fv * (F(1) - sg * (F(1) - f)))
-    i = fi.astype(np.int64) % 6
+    i = i % 6
     table = [(v, t2, p), (q, v, p), (p, v, t2), (p, q, v), (t2, p, v), (v, p, q)]
-    out = np.empty_like(img)
+    out = np.empty(h.shape + (3,), np.int64)
     for c in range(3):
         out[..., c] = np.select([i == k for k in range(6)], [table[k][c] for k in range(6)])
     out[s == 0] = v[s == 0][:, None]
     return out
+
+
+def hue_step(img, fh):
+    h, s, v = rgb_to_hsv(img)
+    return hsv_to_rgb((h + hue_shift(fh)) % 256, s, v)
+
+
+def step(img, s, f):
+    """one step of the chain on an integer image [h,w,3] with its float32 factor -> (the image, m of step C or None)"""
+    if s == B:
+        return blend(0, img, f), None
+    if s == S:
+        return blend(luma(img)[..., None], img, f), None
+    if s == C:
+        m = mean_luma(img)
+        return blend(m, img, f), m
+    return hue_step(img, f), None
 
 
 def jitter_uint8(rgb, cfg, u):
@@ -107,16 +145,7 @@ def jitter_uint8(rgb, cfg, u):
     img = rgb.astype(np.int64)
     trace = []
     for s in steps:
-        m = None
-        if s == B:
-            img = blend(0, img, fb)
-        elif s == S:
-            img = blend(luma(img)[..., None], img, fs)
-        elif s == C:
-            m = mean_luma(img)
-            img = blend(m, img, fc)
-        else:
-            img = hue_step(img, fh)
+        img, m = step(img, s, {B: fb, C: fc, S: fs, H: fh}[s])
         trace.append((s, m))
     assert img.min() >= 0 and img.max() <= 255
     return img, trace

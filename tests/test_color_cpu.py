@@ -1,7 +1,9 @@
 """CPU-only checks of the colour jitter on the device (include/pvnet_color.h, libpvnet_color.so): the header's exports against the
 prototype table of pvnet_amd/_abi.py, the built library, every bad argument rejected with the documented code before any HIP call,
 the register rule for the new kernels, the configuration's defaults against the reference's JSON, the reference's configuration
-loading as it stands, and the properties of the numpy restatement (tests/color_restatement.py) that follow from the definition.
+loading as it stands, the properties of the numpy restatement (tests/color_restatement.py) that follow from the definition, and that
+restatement against Pillow itself (tests/pillow_jitter_oracle.py, where Pillow is importable) and against the bytes recorded from it
+(tests/golden/color_pillow.npz, always).
 What holds for every side library alike (header against table, the built library's symbols, the register tool's selection, the loud
 failure without it) is in tests/test_side_libraries_cpu.py."""
 import ctypes as C
@@ -56,8 +58,9 @@ def test_header_declares_the_exports_and_every_one_has_a_prototype():
               for f in line.strip().split(None, 1)[1].split(",")]
     assert fields == [n for n, _ in _abi.ColorConfigStruct._fields_]
     assert C.sizeof(_abi.ColorConfigStruct) == 4 * 8 + 6 * 4
-    # the header says whose definition it is, how it may differ from Pillow, and what blur is
-    assert "THIS PROJECT'S" in HDR and "Pillow" in HDR and "grey level" in HDR
+    # the header says whose text it is, that it is held to Pillow byte for byte (the version, the record), and what blur is
+    assert "THIS PROJECT'S" in HDR and "Pillow byte for byte" in HDR and "Pillow 12.2.0" in HDR and "tests/golden/color_pillow.npz" in HDR
+    assert "may differ" not in HDR and "Nothing was recorded" not in HDR
     assert "linemod_dataset.py:232" in HDR and "augmentation.py:204-205" in HDR
 
 
@@ -307,3 +310,182 @@ def test_restatement_orders_mean_clip_and_hue_wrap():
     assert out[0, 0, 0] == 200 and out[0, 0, 1] == 0 and out[0, 0, 2] > 150
     out, _ = RS.jitter_uint8(red, dict(ZERO, hue=0.5), np.array([0, 0, 0, 5.0 / 6.0, 0.0]))
     assert out[0, 0, 1] == 200 and out[0, 0, 2] == 0 and out[0, 0, 0] < 10
+
+
+# ---- the restatement against Pillow (tests/pillow_jitter_oracle.py) and against what was recorded from it --------------------------------
+
+from tests import pillow_jitter_oracle as PO  # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "color_pillow.npz")
+KEYS = ("brightness", "contrast", "saturation", "hue")
+
+
+def pil():
+    """' (Pillow x.y.z)' for the assertion messages; skips without Pillow"""
+    return f" (Pillow {pytest.importorskip('PIL').__version__})"
+
+
+def slabs():
+    """all 2^24 colours as 16 images [4096,256,3] uint8"""
+    for r0 in range(0, 256, 16):
+        r, g, b = np.meshgrid(np.arange(r0, r0 + 16), np.arange(256), np.arange(256), indexing="ij")
+        yield np.stack([r, g, b], -1).reshape(16 * 256, 256, 3).astype(np.uint8)
+
+
+@pytest.fixture(scope="module")
+def forward_pass():
+    """the forward conversion over all 2^24 colours, once: (mismatches with Pillow per plane, the distinct (s, v) pairs, the number
+    of colours on which the float32-only hue differs per maxc branch)"""
+    tag = pil()
+    bad, pairs, hard = np.zeros(3, np.int64), set(), np.zeros(3, np.int64)
+    for img in slabs():
+        h, s, v = RS.rgb_to_hsv(img)
+        for k, (got, want) in enumerate(zip((h, s, v), PO.rgb_to_hsv(img))):
+            bad[k] += int((got != want).sum())
+        pairs.update(np.unique(s * 256 + v).tolist())
+        d = RS.rgb_to_hsv(img, float32_only=True)[0] != h
+        m = img.max(-1)
+        branch = np.where(img[..., 0] == m, 0, np.where(img[..., 1] == m, 1, 2))
+        hard += np.bincount(branch[d], minlength=3)
+    return bad, np.array(sorted(pairs)), hard, tag
+
+
+def test_forward_hsv_equals_pillow_on_every_colour(forward_pass):
+    bad, pairs, hard, tag = forward_pass
+    print(f"forward conversion over 2^24 colours{tag}: mismatches in h, s, v {bad.tolist()}; {len(pairs)} distinct (s, v); the float32-only "
+          f"hue differs on {hard.tolist()} colours of the r, g, b branches")
+    assert bad.tolist() == [0, 0, 0], f"h, s, v mismatches {bad.tolist()}{tag}"
+    # the float32-only hue is another one: on no colour of the r branch (float32 there by definition), on many of the others
+    assert hard[0] > 0 and hard[1] > 0 and hard[2] > 0 and int(hard.sum()) == 72036, f"{hard.tolist()}{tag}"
+
+
+def test_back_conversion_equals_pillow_on_every_triple_that_occurs(forward_pass):
+    """every (s, v) that the forward pass produces x all 256 h: every (h, s, v) that occurs, under every shift"""
+    _, pairs, _, tag = forward_pass
+    s, v = pairs // 256, pairs % 256
+    shape = (len(pairs), 256)
+    h = np.broadcast_to(np.arange(256)[None, :], shape)
+    s, v = np.broadcast_to(s[:, None], shape), np.broadcast_to(v[:, None], shape)
+    got, want = RS.hsv_to_rgb(h, s, v), PO.hsv_to_rgb(h, s, v)
+    bad = np.argwhere(got != want)
+    print(f"back conversion over {len(pairs)} x 256 (h, s, v){tag}: {len(bad)} mismatching bytes")
+    assert len(bad) == 0, f"{len(bad)} bytes, first (s, v, h, channel) {(int(s[bad[0][0], 0]), int(v[bad[0][0], 0]), *bad[0][1:].tolist())}{tag}"
+    assert len(pairs) > 30000 and (199 * 256 + 206) in set(pairs.tolist())   # where x - floor(x) of a float32 x misses Pillow's byte
+
+
+def half_image():
+    """a 4 x 4 image of random colours whose luma sum puts (2 S_L + N) / (2 N) exactly on a half"""
+    for seed in range(1000):
+        img = np.random.default_rng(seed).integers(0, 256, (4, 4, 3), dtype=np.uint8)
+        if int(RS.luma(img).sum()) % 16 == 8:
+            return img
+    raise AssertionError("no such image")
+
+
+def test_steps_b_s_c_equal_pillow():
+    tag = pil()
+    half = half_image()
+    assert (2 * int(RS.luma(half).sum())) % (2 * 16) == 16 and RS.mean_luma(half) == int(RS.luma(half).sum()) // 16 + 1
+    images = {"48 x 64": image(20, 48, 64), "1 x 1": np.array([[[200, 17, 90]]], np.uint8), "half": half,
+              "two greys": np.array([[[10, 10, 10], [11, 11, 11]]], np.uint8)}
+    for name, rgb in images.items():
+        for factor in (0.0, 0.9, 1.1, 2.0, 1e6):
+            f = np.float32(factor)
+            for s, fn in ((RS.B, PO.adjust_brightness), (RS.S, PO.adjust_saturation), (RS.C, PO.adjust_contrast)):
+                got = RS.step(rgb.astype(np.int64), s, f)[0]
+                want = np.asarray(fn(PO.to_pil(rgb), float(f)))
+                assert np.array_equal(got, want), f"step {s}, factor {factor}, image {name}: {int((got != want).sum())} bytes differ{tag}"
+
+
+def all_chains():
+    """(cfg, uniforms) of all 24 orders x the 16 subsets of present steps, wide ranges, hue factors of both signs"""
+    wide = dict(brightness=0.6, contrast=0.7, saturation=0.8, hue=0.5)
+    rng = np.random.default_rng(21)
+    for k in range(24):
+        for subset in range(16):
+            cfg = {key: (wide[key] if subset >> j & 1 else 0) for j, key in enumerate(KEYS)}
+            u = rng.uniform(0.0, 1.0, 5)
+            u[3] = rng.uniform(0.02, 0.48) + 0.5 * ((k + subset) & 1)
+            u[4] = (k + 0.5) / 24
+            yield cfg, u
+
+
+def test_chain_equals_pillow_for_every_order_and_subset():
+    tag = pil()
+    rgb = np.load(GOLDEN)["image"]
+    signs = set()
+    for cfg, u in all_chains():
+        got = RS.jitter_uint8(rgb, cfg, u)[0]
+        want = PO.jitter_uint8(rgb, cfg, u)
+        assert np.array_equal(got, want), f"{cfg}, {u.tolist()}: {int((got != want).sum())} bytes differ{tag}"
+        signs.add((cfg["hue"] != 0, bool(RS.hue_factor(0.5, u[3]) < 0)))
+    assert signs == {(a, b) for a in (False, True) for b in (False, True)}
+
+
+def check_chain_against_fixture():
+    z = np.load(GOLDEN)
+    rgb, ranges, U, want = z["image"], z["ranges"], z["uniforms"], z["want"]
+    version = str(z["pil_version"])
+    assert rgb.shape == (32, 40, 3) and rgb.dtype == np.uint8 and want.shape == (48, 2, 32, 40, 3) and want.dtype == np.uint8
+    assert os.path.getsize(GOLDEN) < os.path.getsize(os.path.join(ROOT, "tests", "golden", "head_metrics.npz"))
+    # half of the image: colours on which the float32-only hue differs, of all three maxc branches
+    top = rgb[:16].reshape(-1, 3)
+    assert bool((RS.rgb_to_hsv(top)[0] != RS.rgb_to_hsv(top, float32_only=True)[0]).all())
+    m = top.max(1)
+    assert min(int((top[:, 0] == m).sum()), int(((top[:, 0] != m) & (top[:, 1] == m)).sum()), int(((top[:, 0] != m) & (top[:, 1] != m)).sum())) >= 200
+    orders = []
+    for c in range(48):
+        cfg = dict(zip(KEYS, ranges[c]))
+        for j in range(2):
+            got = RS.jitter_uint8(rgb, cfg, U[c, j])[0]
+            assert np.array_equal(got, want[c, j]), f"case {c}.{j}: {int((got != want[c, j]).sum())} bytes differ (recorded from Pillow {version})"
+        assert cfg["hue"] == 0 or RS.hue_factor(cfg["hue"], U[c, 0, 3]) < 0 < RS.hue_factor(cfg["hue"], U[c, 1, 3])
+        orders.append((RS.ORDERS.index(tuple(RS.chain({}, U[c, 0])[4])), int((ranges[c] == 0).sum())))
+    # each of the 24 orders twice: all four steps, and one absent, rotating through the four
+    assert orders == [(k, copy) for k in range(24) for copy in (0, 1)]
+    assert [int(np.argmin(ranges[2 * k + 1])) for k in range(24)] == [k % 4 for k in range(24)]
+    return version
+
+
+def test_chain_equals_the_bytes_recorded_from_pillow():
+    assert check_chain_against_fixture() == "12.2.0"
+
+
+def test_fixture_needs_no_pillow(monkeypatch):
+    """with PIL unimportable the comparison with the recorded bytes runs all the same"""
+    for name in [n for n in sys.modules if n == "PIL" or n.startswith("PIL.")]:
+        monkeypatch.delitem(sys.modules, name)
+    monkeypatch.setitem(sys.modules, "PIL", None)
+    with pytest.raises(ImportError):
+        import PIL  # noqa: F401
+    check_chain_against_fixture()
+
+
+def test_fixture_is_what_its_maker_writes():
+    tag = pil()
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_color_golden as maker
+    rng = np.random.default_rng(20240)
+    z = np.load(GOLDEN)
+    img, n_hard = maker.make_image(rng)
+    ranges, uniforms = maker.make_cases(rng)
+    assert np.array_equal(img, z["image"]) and np.array_equal(ranges, z["ranges"]) and np.array_equal(uniforms, z["uniforms"]), tag
+    assert n_hard == int(z["hard_colours"]) == 72036
+
+
+def test_hue_shift_equals_torchvisions_near_every_step():
+    """float32 factors within 4 ulp of n / 255, n = -127 .. 127: the definition's float32 product against the oracle's double one"""
+    tag = pil()
+    count = 0
+    for n in range(-127, 128):
+        c = np.float32(n / 255)
+        vals, lo, hi = [c], c, c
+        for _ in range(4):
+            lo, hi = np.nextafter(lo, np.float32(-1)), np.nextafter(hi, np.float32(1))
+            vals += [lo, hi]
+        for f in vals:
+            assert abs(float(f)) <= 0.5
+            got, want = RS.hue_shift(f), PO.hue_shift(f)
+            assert got == want == int(np.uint8(np.int64(float(f) * 255))), f"fh = {float(f)!r}: {got} against {want}{tag}"
+            count += 1
+    assert count == 255 * 9

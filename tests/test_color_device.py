@@ -2,7 +2,11 @@
 
 The bar is equality: the device against the numpy restatement of include/pvnet_color.h (tests/color_restatement.py), ``torch.equal``
 on the output tensor for float32, bfloat16 and float16 (the restatement's float32 rounded once); the fused path against
-``augment_batch`` (mask, key-points, status) and against ``jitter_batch`` run on the warped uint8 image that ``augment_batch`` made."""
+``augment_batch`` (mask, key-points, status) and against ``jitter_batch`` run on the warped uint8 image that ``augment_batch`` made.
+The restatement is held to Pillow on the CPU (tests/test_color_cpu.py); here the device is held to the bytes recorded from Pillow
+(tests/golden/color_pillow.npz, no Pillow needed) and to the restatement on every colour where a float32-only hue is not Pillow's."""
+import os
+
 import numpy as np
 import pytest
 
@@ -297,3 +301,106 @@ def test_output_feeds_the_head_loss(K, A):
     torch.cuda.synchronize()
     assert bool(torch.isfinite(image).all()) and float(loss_vertex.detach().sum()) > 0 and bool(torch.isfinite(vp.grad).all())
     assert bool(torch.isfinite(seg.grad).all()) and status.tolist()[0] == ARS.S_NO_FOREGROUND
+
+
+# ---- the device against the bytes recorded from Pillow, and on the colours where a float32-only hue is not Pillow's ----------------------
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "color_pillow.npz")
+KEYS = ("brightness", "contrast", "saturation", "hue")
+
+
+def golden_groups():
+    """the fixture's 48 cases x 2 draws, grouped by configuration: (cfg, rgb [n,32,40,3], uniforms [n,5], Pillow's bytes [n,32,40,3])"""
+    z = np.load(GOLDEN)
+    image, ranges, U, want = z["image"], z["ranges"], z["uniforms"], z["want"]
+    groups = {}
+    for c in range(48):
+        groups.setdefault(tuple(ranges[c].tolist()), []).append(c)
+    assert len(groups) == 5 and sum(len(v) for v in groups.values()) == 48
+    for key, cases in groups.items():
+        n = 2 * len(cases)
+        yield (dict(zip(KEYS, key)), np.ascontiguousarray(np.broadcast_to(image, (n,) + image.shape)), U[cases].reshape(n, 5),
+               want[cases].reshape((n,) + image.shape), str(z["pil_version"]))
+
+
+def normalized(want):
+    return torch.from_numpy(np.stack([RS.normalize(w.astype(np.int64)) for w in want]))
+
+
+def test_jitter_batch_gives_the_bytes_recorded_from_pillow(K):
+    for cfg, rgb, U, want, version in golden_groups():
+        ref = normalized(want)
+        t_rgb, t_U = torch.from_numpy(rgb).to(dev()), torch.from_numpy(U)
+        for dt in DTYPES:
+            got = K.jitter_batch(t_rgb, K.ColorJitterConfig(**cfg), t_U, out_dtype=dt)
+            torch.cuda.synchronize()
+            bad = (got.cpu() != ref.to(dt)).flatten(1).any(1).nonzero().flatten().tolist()
+            assert torch.equal(got.cpu(), ref.to(dt)), f"{cfg}, {dt}: images {bad} differ from what Pillow {version} gave"
+
+
+def test_fused_path_gives_the_bytes_recorded_from_pillow(K, A):
+    """``augment_jitter_batch`` under the identity geometric plan: nothing masked, rotated, cropped, resized or flipped"""
+    identity = A.AugmentConfig(mask=False, rotation=False, crop=False, flip=False, use_mask_out=False)
+    for cfg, rgb, U, want, version in golden_groups():
+        n, h, w = rgb.shape[:3]
+        ref = normalized(want)
+        mask = np.zeros((n, h, w), np.uint8)
+        mask[:, 8:20, 10:30] = 1
+        hc = np.tile(np.array([[5.0, 7.0, 1.0], [30.0, 20.0, 2.0]]), (n, 1, 1))
+        args = (torch.from_numpy(rgb).to(dev()), torch.from_numpy(mask).to(dev()), torch.from_numpy(hc).to(dev()), h, w, identity)
+        tU = torch.from_numpy(np.random.default_rng(31).uniform(0.0, 1.0, (n, 12)))
+        plain = A.augment_batch(*args, tU, 3)
+        assert torch.equal(plain[0], A.normalize_batch(args[0])) and torch.equal(plain[1].cpu(), torch.from_numpy(mask))   # the identity
+        for dt in DTYPES:
+            got = K.augment_jitter_batch(*args, K.ColorJitterConfig(**cfg), tU, torch.from_numpy(U), 3, out_dtype=dt)
+            torch.cuda.synchronize()
+            assert torch.equal(got[0].cpu(), ref.to(dt)), f"{cfg}, {dt}: differs from what Pillow {version} gave"
+            assert torch.equal(got[1], plain[1]) and torch.equal(got[2], plain[2]) and torch.equal(got[3], plain[3])
+
+
+@pytest.fixture(scope="module")
+def hard_image():
+    """[1,282,256,3] uint8: every colour on which the hue computed in float32 throughout and the definition's differ (72 036 of the
+    2^24, found here from the two numpy formulas), shuffled, the last row filled up with the first colours again"""
+    found = []
+    for r0 in range(0, 256, 16):
+        r, g, b = np.meshgrid(np.arange(r0, r0 + 16), np.arange(256), np.arange(256), indexing="ij")
+        img = np.stack([r, g, b], -1).reshape(-1, 3).astype(np.uint8)
+        found.append(img[RS.rgb_to_hsv(img)[0] != RS.rgb_to_hsv(img, float32_only=True)[0]])
+    hard = np.random.default_rng(40).permutation(np.concatenate(found))
+    assert len(hard) == 72036
+    w = 256
+    h = -(-len(hard) // w)
+    return np.concatenate([hard, hard[:h * w - len(hard)]]).reshape(1, h, w, 3)
+
+
+def branches(rgb):
+    """how many pixels take the r, g and b branch of the forward hue"""
+    c = rgb.reshape(-1, 3).astype(np.int64)
+    m = c.max(1)
+    return [int((c[:, 0] == m).sum()), int(((c[:, 0] != m) & (c[:, 1] == m)).sum()), int(((c[:, 0] != m) & (c[:, 1] != m)).sum())]
+
+
+HUE_ONLY = dict(ZERO, hue=0.5)
+HUE_U = np.array([[0.3, 0.3, 0.3, u3, 0.5] for u3 in (0.5, 0.6, 0.4)])   # fh = 0, 0.1, -0.1: shifts 0, +25, -25
+
+
+def check_hard(K, rgb):
+    assert [RS.hue_shift(RS.chain(HUE_ONLY, u)[3]) for u in HUE_U] == [0, 25, 256 - 25]
+    assert all(RS.chain(HUE_ONLY, u)[4] == [RS.H] for u in HUE_U) and min(branches(rgb)) > 0
+    batch = np.ascontiguousarray(np.broadcast_to(rgb, (3,) + rgb.shape[1:]))
+    check(K, batch, HUE_ONLY, HUE_U)
+    # these are the colours the float32-only hue gets wrong: with it every pixel's h is another, and the images differ
+    old = np.stack([RS.hsv_to_rgb((h + RS.hue_shift(RS.chain(HUE_ONLY, u)[3])) % 256, s, v)
+                    for u in HUE_U for h, s, v in [RS.rgb_to_hsv(rgb[0], float32_only=True)]])
+    new = np.stack([RS.jitter_uint8(rgb[0], HUE_ONLY, u)[0] for u in HUE_U])
+    assert all(bool((o != n).any()) for o, n in zip(old, new))
+
+
+def test_hard_colours_on_the_vector_path(K, hard_image):
+    assert hard_image.shape[2] % 8 == 0
+    check_hard(K, hard_image)
+
+
+def test_hard_colours_on_the_element_path(K, hard_image):
+    check_hard(K, np.ascontiguousarray(hard_image[:, :33, :47]))
