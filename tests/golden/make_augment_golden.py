@@ -15,17 +15,24 @@ put under them, and nothing of them is changed:
   counter-based one.
 
 The file holds data only: per case the inputs (``rgb [48,64,3]`` uint8, ``mask [48,64]`` uint8, ``hcoords [vn,3]`` float64,
-``uniforms [12]``, the target size, the seed, the configuration overrides as JSON) and the reference's float64 ``hcoords`` (before the
-loader casts them to float32); for the cases without rotation and without resize -- flip, crop, pad and mask-out are pure numpy in the
-reference -- also its uint8 image and its mask.
+``uniforms [12]``, the target size, the seed, the configuration overrides as JSON), the reference's float64 ``hcoords`` (before the
+loader casts them to float32), and its uint8 image and its mask.  Without rotation and without resize -- flip, crop, pad and mask-out
+are pure numpy in the reference -- these are the reference's own numbers.  With them they are what the reference's own code chains
+together (``rotate_instance``, ``crop_resize_instance_v2``, crop or pad, flip: its order, offsets and conventions) over the two stand-in
+samplers: interpolated twice and rounded to uint8 twice, where the product interpolates once.  The mask is a chain of integer maps
+and must be the product's exactly; the image is an oracle to within the two roundings wherever no tap of the second interpolation
+reaches a canvas pixel already blended with the zero border.  ``ramp_cases`` lists the cases whose picture is the ramp
+``(4x, 5y, 2x + 2y)``, which has a closed form; their ``rgb`` is not stored: it is ``tests/augment_cases.ramp(48, 64)``.
 """
 import importlib
+import io
 import json
 import linecache
 import math
 import os
 import sys
 import types
+import zipfile
 
 import numpy as np
 
@@ -80,6 +87,21 @@ def cases():
         if vn > 2:
             hc[2] *= 1.75   # a key-point whose homogeneous scale is not 1
         out[name] = (picture(rng), mask, hc, size, over, u)
+    # appended after every draw above, so the earlier cases stay what they were: ramp pictures, rotated, the mask-out gate closed
+    from tests.augment_cases import ramp as ramp_picture
+    ramp = ramp_picture(H, W)
+    mixed = dict(resize_hmin=12, resize_hmax=30, resize_wmin=12, resize_wmax=30)
+    more = {
+        "ramp_rotation_only": (blob(22, 34, 9.4), (32, 40), grow, dict(maskout=0.7, resize=0.9, flip=0.8, ang=0.08)),
+        "ramp_rotation_grow": (blob(25, 29, 9.1), (24, 32), grow, dict(maskout=0.6, resize=0.2, flip=0.7, ang=0.9)),
+        "ramp_rotation_shrink": (blob(23, 33, 10.2), (32, 40), shrink, dict(maskout=0.8, resize=0.4, flip=0.9, ang=0.2)),
+        "ramp_rotation_resize_flip": (blob(21, 30, 8.7), (24, 32), mixed, dict(maskout=0.9, resize=0.5, flip=0.3, ang=0.75)),
+        "ramp_rotation_resize_odd_target": (blob(26, 35, 9.8), (31, 37), mixed, dict(maskout=0.55, resize=0.1, flip=0.6, ang=0.97)),
+    }
+    for name, (mask, size, over, kw) in more.items():
+        u = row(**kw)
+        hc = np.concatenate([rng.uniform(-10.0, 70.0, (4, 2)), np.ones((4, 1))], 1)
+        out[name] = (ramp.copy(), mask, hc, size, over, u)
     return out
 
 
@@ -183,18 +205,26 @@ def main(reference_root):
             np.random.random, np.random.uniform, np.random.randint = saved
         assert out.dtype == np.float64 and img.shape == (height, width, 3) and m.shape == (height, width)
         names.append(name)
-        arrays[f"{name}.rgb"], arrays[f"{name}.mask"], arrays[f"{name}.hcoords"] = rgb, mask, hc
+        arrays[f"{name}.mask"], arrays[f"{name}.hcoords"] = mask, hc
+        if not name.startswith("ramp_"):   # the ramp is a formula (tests/augment_cases.ramp); interleaved it does not deflate
+            arrays[f"{name}.rgb"] = rgb
         arrays[f"{name}.uniforms"], arrays[f"{name}.size"], arrays[f"{name}.seed"] = u, np.array([height, width]), np.array(seed)
         arrays[f"{name}.cfg"] = np.array(json.dumps(over))
         arrays[f"{name}.ref_hcoords"] = out
         integer_only = not (5 in draws.used or 7 in draws.used)
-        if integer_only:
-            arrays[f"{name}.ref_image"] = np.ascontiguousarray(img).astype(np.uint8)
-            arrays[f"{name}.ref_mask"] = np.ascontiguousarray(m).astype(np.uint8)
-        print(f"{name:30s} vn={hc.shape[0]} -> {(height, width)} draws {sorted(draws.used)} foreground {int((m != 0).sum())}"
-              f"{' (image and mask recorded)' if integer_only else ''}")
+        assert img.dtype == np.uint8 and int(m.min()) >= 0 and int(m.max()) <= 255
+        arrays[f"{name}.ref_image"] = np.ascontiguousarray(img)
+        arrays[f"{name}.ref_mask"] = np.ascontiguousarray(m).astype(np.uint8)
+        print(f"{name:34s} vn={hc.shape[0]} -> {(height, width)} draws {sorted(draws.used)} foreground {int((m != 0).sum())}"
+              f"{' (pure numpy in the reference)' if integer_only else ' (the chain over the stand-in samplers)'}")
     arrays["cases"] = np.array(names)
-    np.savez_compressed(OUT, **arrays)
+    arrays["ramp_cases"] = np.array([n for n in names if n.startswith("ramp_")])
+    # np.savez_compressed's container without the zip64 fields it adds to every entry: most of the entries are a few bytes
+    with zipfile.ZipFile(OUT, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key, value in arrays.items():
+            data = io.BytesIO()
+            np.lib.format.write_array(data, np.asanyarray(value), allow_pickle=False)
+            z.writestr(zipfile.ZipInfo(key + ".npy", (1980, 1, 1, 0, 0, 0)), data.getvalue(), zipfile.ZIP_DEFLATED, 9)
     print("wrote", OUT, os.path.getsize(OUT), "bytes")
 
 

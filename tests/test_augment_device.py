@@ -1,7 +1,10 @@
 """GPU tests of the augmentation on the device (pvnet_amd/augment.py, pvnet_amd/csrc/augment.hip, libpvnet_augment.so).
 
 The bar is equality: the device against the numpy restatement of include/pvnet_augment.h (tests/augment_restatement.py), bit for bit,
-and its key-points against what the reference's own ``augmentation`` returned (tests/golden/augment.npz)."""
+and its key-points and masks against what the reference's own ``augmentation`` returned (tests/golden/augment.npz).  Two oracles
+that do not descend from the header hold the image of rotated and resized samples: the closed form of a ramp source under the
+inverse of the composed forward maps (tests/augment_cases.py, bar 0.5 + 1e-6), and the reference's own chain over stand-in
+samplers, recorded in the fixture (ramp pictures, at most 1 grey level 2 px inside the source)."""
 import json
 import os
 
@@ -11,6 +14,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from tests import augment_cases as AC  # noqa: E402
 from tests import augment_restatement as RS  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,11 +42,12 @@ def bits(t):
 
 
 def run(A, rgb, mask, hc, size, cfg, U, seed, out_dtype=torch.float32, mask_dtype=torch.uint8, pad_strides=False, mask_in=torch.uint8,
-        by_value=False):
-    """one device call against the restatement; returns both sides"""
+        by_value=False, want=None):
+    """one device call against the restatement (``want``: its output where a caller has it already); returns both sides"""
     dev = torch.device("cuda:0")
     config = A.AugmentConfig(**cfg)
-    want = RS.augment_batch(rgb, mask, hc, size[0], size[1], cfg, U, seed)
+    if want is None:
+        want = RS.augment_batch(rgb, mask, hc, size[0], size[1], cfg, U, seed)
     t_rgb, t_mask = torch.from_numpy(rgb).to(dev), torch.from_numpy(mask).to(dev).to(mask_in)
     if pad_strides:   # rows longer than the image, a gap between the images: any strides with the channel stride 1
         b, h, w = mask.shape
@@ -71,7 +76,7 @@ def run(A, rgb, mask, hc, size, cfg, U, seed, out_dtype=torch.float32, mask_dtyp
 
 
 def case(g, n):
-    return (g[n + ".rgb"][None], g[n + ".mask"][None], g[n + ".hcoords"][None], tuple(int(v) for v in g[n + ".size"]),
+    return (AC.golden_rgb(g, n)[None], g[n + ".mask"][None], g[n + ".hcoords"][None], tuple(int(v) for v in g[n + ".size"]),
             json.loads(str(g[n + ".cfg"])), g[n + ".uniforms"][None], int(g[n + ".seed"]))
 
 
@@ -95,16 +100,94 @@ def test_identity_plan_equals_the_torch_composition(A, golden):
 
 def test_device_equals_restatement_and_reference_keypoints(A, golden):
     """every recorded case: (48,64) -> (32,40) the vector path, -> (31,37) the element path, the padded sizes; the device's
-    key-points equal the REFERENCE's recorded float64 ones"""
+    key-points equal the REFERENCE's recorded float64 ones, and its mask the REFERENCE's recorded one, rotated and resized cases
+    included"""
     seen = set()
+    assert len(golden["cases"]) >= 16
     for n in (str(x) for x in golden["cases"]):
         rgb, mask, hc, size, cfg, U, seed = case(golden, n)
         got, want = run(A, rgb, mask, hc, size, cfg, U, seed)
         assert np.array_equal(got[2].cpu().numpy()[0], golden[n + ".ref_hcoords"]), n
-        if n + ".ref_mask" in golden:
-            assert np.array_equal(got[1].cpu().numpy()[0], golden[n + ".ref_mask"]), n
+        assert np.array_equal(got[1].cpu().numpy()[0], golden[n + ".ref_mask"]), n
         seen.add(size)
     assert {(32, 40), (31, 37), (56, 72), (48, 64)} <= seen
+
+
+def test_device_image_against_the_references_chain(A, golden):
+    """The device's image against the image the reference's own code chains together (rotate_instance, crop_resize_instance_v2, crop
+    or pad, flip) over the stand-in samplers.  Without rotation and resize: ``==``.  Ramp pictures, rotated and resized: at most 1
+    grey level wherever the source point is 2 px inside the source and the canvas point inside the canvas -- against the exact ramp
+    two passes are off by at most 0.5 + 0.5, one pass by at most 0.5, so the integers differ by less than 2.  The noisy pictures:
+    printed, not asserted (the deviation the header names)."""
+    dev = torch.device("cuda:0")
+    ramps = {str(x) for x in golden["ramp_cases"]}
+    checked = 0
+    for n in (str(x) for x in golden["cases"]):
+        rgb, mask, hc, size, cfg, U, seed = case(golden, n)
+        image, m, _, status = A.augment_batch(torch.from_numpy(rgb).to(dev), torch.from_numpy(mask).to(dev), torch.from_numpy(hc).to(dev),
+                                              size[0], size[1], A.AugmentConfig(**cfg), torch.from_numpy(U), seed)
+        torch.cuda.synchronize()
+        v = AC.recover_uint8(image.cpu().numpy())[0]
+        ref = golden[n + ".ref_image"]
+        plan = RS.augment_one(rgb[0], mask[0], hc[0], size[0], size[1], cfg, U[0], seed)[4]
+        assert np.array_equal(m.cpu().numpy()[0], golden[n + ".ref_mask"]), n
+        if not plan["rotated"] and not plan["resized"]:
+            assert np.array_equal(v, ref.astype(np.int64).transpose(2, 0, 1)), n
+            continue
+        worst, pixels, anywhere = AC.two_pass_difference(v, ref, plan, 48, 64)
+        print(f"{n}: device against the reference's two passes: at most {worst} on {pixels} pixels 2 px inside, {anywhere} anywhere")
+        if n in ramps:
+            assert worst <= 1 and pixels >= 200, (n, worst, pixels)
+            checked += 1
+    assert checked == 5
+
+
+def device_images(A, group, out_dtype=torch.float32):
+    """the device's output for one group of tests/augment_cases.py"""
+    dev = torch.device("cuda:0")
+    got = A.augment_batch(torch.from_numpy(group["rgb"]).to(dev), torch.from_numpy(group["mask"]).to(dev), torch.from_numpy(group["hc"]).to(dev),
+                          group["size"][0], group["size"][1], A.AugmentConfig(**group["cfg"]), torch.from_numpy(group["U"]), group["seed"],
+                          out_dtype=out_dtype)
+    torch.cuda.synchronize()
+    return got
+
+
+def test_device_image_equals_the_ramp_closed_form(A):
+    """The device's float32 image, directly (not through the restatement), against ``rint(I(sx, sy))`` of a ramp source: the source
+    point is the inverse of the composed forward maps R, S, C, F in float64 (tests/augment_cases.py), the bar 0.5 (the one rint) +
+    1e-6.  300 samples of status 0 over three resize ranges and four targets, 503 372 interior pixels; one group with the mask-out
+    gate open (pixels with a tap in the rectangle left out); a 37 x 53 source.  bfloat16 and float16 are the float32 result rounded
+    once, on the vector path (32,40) and the element path (31,37)."""
+    worst, counts = 0.0, []
+    groups = AC.ramp_set()
+    for g in groups + (AC.ramp_maskout_case(),) + AC.ramp_odd_source():
+        main = any(g is x for x in groups)
+        image, m, _, status = device_images(A, g)
+        assert image.dtype == torch.float32 and status.tolist() == [0] * len(g["rgb"])
+        w, c, left = AC.ramp_check(image.cpu().numpy(), g)
+        print(f"{g['name']}: worst {w:.8f} on {sum(c)} interior pixels, {sum(left)} left out")
+        assert w <= AC.RAMP_BAR, (g["name"], w)
+        assert min(c) >= (AC.RAMP_MIN_INTERIOR_PER_SAMPLE if main else 500) and (sum(left) >= 500) == bool(g["maskout"])
+        if main:
+            worst, counts = max(worst, w), counts + c
+        if g["size"] in ((32, 40), (31, 37)) and (g["name"].startswith("mixed") or g["name"].startswith("37x53")):
+            for dt in (torch.bfloat16, torch.float16):
+                half = device_images(A, g, dt)[0]
+                assert half.dtype == dt and torch.equal(bits(half), bits(image.to(dt))), (g["name"], dt)
+    print(f"ramp closed form, device: worst |v - I(sx, sy)| = {worst:.8f} on {sum(counts)} interior pixels of {len(counts)} samples")
+    assert len(counts) >= 250 and sum(counts) >= AC.RAMP_MIN_INTERIOR_TOTAL
+
+
+def test_seeded_sweep_equals_restatement(A):
+    """280 seeded samples in seven calls of 40, all twelve uniforms over [0, 1): empty, one-row, one-column, border and interior
+    blobs, two source sizes, five targets, three resize ranges, the three output types, use_mask_out on and off, the three mask
+    input types, padded strides.  What they cover is asserted on the CPU (tests/test_augment_cpu.py)."""
+    cover = AC.sweep_coverage(AC.sweep_calls())
+    assert cover["samples"] >= 192 and all(cover[f"status_{b}"] >= 1 for b in (1, 2, 4, 8))
+    for c in AC.sweep_calls():
+        run(A, c["rgb"], c["mask"], c["hc"], c["size"], c["cfg"], c["U"], c["seed"], out_dtype=getattr(torch, c["out_dtype"]),
+            mask_dtype=getattr(torch, c["mask_dtype"]), pad_strides=c["pad_strides"], mask_in=getattr(torch, c["mask_in"]),
+            by_value=bool(c["cfg"].get("use_mask_out")), want=c["want"])
 
 
 def test_element_path_padded_strides_int64_masks_and_half_types(A, golden):
@@ -208,7 +291,8 @@ def test_in_place_keypoints_and_misaligned_outputs(A, golden):
 
 
 def test_full_size_index_range(A):
-    """(480,640) -> (256,256) and -> (480,640) at b = 2: the sizes of a training batch, more than one block per row group"""
+    """(480,640) -> (256,256) and -> (480,640) at b = 4: the sizes of a training batch, more than one block per row group; the last
+    two samples have the angle at the two ends of its range (-30 and just below +30 degrees)"""
     rng = np.random.default_rng(11)
     H, W = 480, 640
     yy, xx = np.mgrid[0:H, 0:W]
@@ -218,9 +302,18 @@ def test_full_size_index_range(A):
     U = rng.uniform(0.05, 0.95, (2, 12))
     U[0, [0, 6, 10]] = 0.2, 0.3, 0.2
     U[1, [0, 6, 10]] = 0.7, 0.5, 0.9
+    # drawn after everything above, so the first two samples stay what they were
+    rgb = np.concatenate([rgb, rng.integers(0, 256, (2, H, W, 3), dtype=np.uint8)])
+    mask = np.concatenate([mask, np.stack([((yy - 120) ** 2 + (xx - 480) ** 2 < 60 ** 2), ((yy - 330) ** 2 + (xx - 150) ** 2 / 4 < 45 ** 2)]).astype(np.uint8)])
+    hc = np.concatenate([hc, np.concatenate([rng.uniform(0.0, 640.0, (2, 9, 2)), np.ones((2, 9, 1))], 2)])
+    U = np.concatenate([U, rng.uniform(0.05, 0.95, (2, 12))])
+    U[2, [0, 5, 6, 10]] = 0.8, 0.0, 0.4, 0.7
+    U[3, [0, 5, 6, 10]] = 0.3, 1.0 - 2.0 ** -53, 0.2, 0.1
+    assert RS.trig(U[2, 5], RS.DEFAULTS)[1] == -RS.trig(1.0, RS.DEFAULTS)[1] and abs(RS.trig(U[3, 5], RS.DEFAULTS)[1] - 0.5) < 1e-12
     for size in ((256, 256), (480, 640)):
         got, want = run(A, rgb, mask, hc, size, {}, U, 2024)
-        assert want[3].tolist() == [0, 0] and want[4][0]["resized"] and want[4][1]["resized"] and want[1].sum() > 0
+        assert want[3].tolist() == [0, 0, 0, 0] and all(p["resized"] and p["rotated"] for p in want[4]) and want[1].sum() > 0
+        assert all(want[1][i].sum() > 0 for i in range(4))
 
 
 def test_graph_capture_replays_and_two_calls_agree(A, golden):

@@ -13,6 +13,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from tests import augment_cases as AC  # noqa: E402
 from tests import augment_restatement as ARS  # noqa: E402
 from tests import color_restatement as RS  # noqa: E402
 
@@ -229,6 +230,40 @@ def test_fused_path_equals_augment_then_jitter(K, A):
     maskmul = torch.tensor([int(p["maskmul"]) for p in plans], dtype=torch.int32)
     assert torch.equal(got[1], base[1]) and torch.equal(got[2], base[2]) and torch.equal(got[3], base[3])
     assert torch.equal(got[0], K.jitter_batch(warped, K.ColorJitterConfig(**WIDE), JU, mask=base[1], maskmul=maskmul))
+
+
+def test_fused_path_under_the_warps_own_oracles(K, A):
+    """``augment_jitter_batch`` compiles the same warp (pvnet_amd/csrc/augment_warp.h) into another library.  With all four ranges
+    0 its image satisfies the ramp's closed form (tests/augment_cases.py: the inverse of the composed forward maps, bar 0.5 + 1e-6)
+    on one batch of the ramp set per store path, and its mask is the one the reference's own chain gave for the recorded ramp cases
+    (tests/golden/augment.npz), whose image it meets to 1 grey level 2 px inside the source."""
+    import json
+    zero = K.ColorJitterConfig(**ZERO)
+    for g in [x for x in AC.ramp_set() if x["name"] in ("mixed->(32, 40)", "mixed->(31, 37)")]:
+        n = len(g["rgb"])
+        got = K.augment_jitter_batch(torch.from_numpy(g["rgb"]).to(dev()), torch.from_numpy(g["mask"]).to(dev()), torch.from_numpy(g["hc"]).to(dev()),
+                                     *g["size"], A.AugmentConfig(**g["cfg"]), zero, torch.from_numpy(g["U"]), torch.from_numpy(uniforms(n, 15)),
+                                     g["seed"])
+        torch.cuda.synchronize()
+        assert got[3].tolist() == [0] * n and got[0].dtype == torch.float32
+        worst, counts, _ = AC.ramp_check(got[0].cpu().numpy(), g)
+        print(f"fused, {g['name']}: worst |v - I(sx, sy)| = {worst:.8f} on {sum(counts)} interior pixels")
+        assert worst <= AC.RAMP_BAR and min(counts) >= AC.RAMP_MIN_INTERIOR_PER_SAMPLE and sum(counts) >= 15000, (worst, counts)
+    golden = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "augment.npz"))
+    names = [str(x) for x in golden["ramp_cases"]]
+    assert len(names) == 5
+    for name in names:
+        rgb, mask, hc, U = AC.golden_rgb(golden, name), golden[name + ".mask"], golden[name + ".hcoords"], golden[name + ".uniforms"]
+        size, cfg, seed = tuple(int(v) for v in golden[name + ".size"]), json.loads(str(golden[name + ".cfg"])), int(golden[name + ".seed"])
+        got = K.augment_jitter_batch(torch.from_numpy(rgb[None]).to(dev()), torch.from_numpy(mask[None]).to(dev()),
+                                     torch.from_numpy(hc[None]).to(dev()), *size, A.AugmentConfig(**cfg), zero, torch.from_numpy(U[None]),
+                                     torch.from_numpy(uniforms(1, 16)), seed)
+        torch.cuda.synchronize()
+        assert np.array_equal(got[1].cpu().numpy()[0], golden[name + ".ref_mask"]) and golden[name + ".ref_mask"].sum() > 0, name
+        assert np.array_equal(got[2].cpu().numpy()[0], golden[name + ".ref_hcoords"]), name
+        plan = ARS.augment_one(rgb, mask, hc, *size, cfg, U, seed)[4]
+        worst, pixels, _ = AC.two_pass_difference(AC.recover_uint8(got[0].cpu().numpy())[0], golden[name + ".ref_image"], plan, 48, 64)
+        assert worst <= 1 and pixels >= 200, (name, worst, pixels)
 
 
 def test_fused_multiply_with_mask_values_above_255(K, A):
