@@ -12,7 +12,7 @@
  *
  * Instances: (mesh id, pose [3,4] float64, K, target image, label 1 .. 255), the instance table of pvnet_render (pvnet_raster.h).
  *
- * Coverage: stage P then stage R of pvnet_raster.h, unchanged (the kernels compile the same functions, pvnet_amd/csrc/raster_common.h):
+ * Coverage: stage P then stage R of pvnet_raster.h, unchanged (the kernels compile the same functions, pvnet_amd/csrc/mesh_core.h):
  * the vertices are projected in float64 in that header's operation order, u and v rounded to float32, and a pixel of the triangle's
  * inclusive box belongs to the triangle when the float32 same_side predicate holds for the three edges.  The depth image of one
  * instance alone (far = +inf) is therefore non-zero exactly where pvnet_render's mask is 1, whenever the instance's status is 0.

@@ -24,7 +24,7 @@
  * THE DEFINITION
  *
  * Instances, coverage, the depth of a covered pixel under one triangle, `far`, the skipped triangles and the status bits: pvnet_depth.h,
- * unchanged (the kernels compile the same functions: pvnet_amd/csrc/mesh_stages.h, pvnet_amd/csrc/depth_plane.h).
+ * unchanged (the kernels compile the same functions: pvnet_amd/csrc/mesh_core.h, pvnet_amd/csrc/depth_core.h).
  *
  * Composition.  A pixel takes the smallest kept depth over all triangles of all instances of its image; at equal float32 depth the
  * instance earlier in the list wins, and between two faces of one instance the lower face index (local to its mesh).  Depth, labels,

@@ -23,8 +23,8 @@
  *
  * Unchanged, by reference:
  *   pvnet_depth.h   instances and coverage; the depth of a covered pixel under one triangle; `far`; the skipped triangles and the status
- *                   bits (the kernels compile the same functions: pvnet_amd/csrc/mesh_core.h, pvnet_amd/csrc/depth_core.h, the bodies
- *                   behind the headers the other three libraries include);
+ *                   bits (the kernels compile the same functions: pvnet_amd/csrc/mesh_core.h, pvnet_amd/csrc/depth_core.h, and the
+ *                   one z-buffer of pvnet_amd/csrc/zbuffer_core.h);
  *   pvnet_shade.h   the composition order (depth, then instance, then face); C_k, z_k and the float32 screen vertex (x_k, y_k); the
  *                   screen barycentrics l_k with their clamps; the perspective weights w_k = l_k / z_k, s, and the interpolation A(a)
  *                   with its fallback a0; the eye point e; the three light terms (none / flat / Phong); the final

@@ -32,11 +32,10 @@ ARCH = "gfx950"
 # stays as it is.  One row per library, under the name pvnet_amd._abi.SIDE_LIBRARIES binds it by:
 # name -> (translation units, its header under include/, what they include beyond that header and the common ones)
 _AUGMENT_WARP = os.path.join(CSRC, "augment_warp.h")   # the one copy of the plan and the warp: the two libraries that compile it rebuild with it
-_RASTER_COMMON = os.path.join(CSRC, "raster_common.h")   # the one copy of the projection and the coverage predicate, likewise
-_MESH_STAGES = os.path.join(CSRC, "mesh_stages.h")       # ... whose bodies live here: raster_common.h includes it, shade.hip directly
-_DEPTH_PLANE = os.path.join(CSRC, "depth_plane.h")       # the one copy of the depth of a covered pixel: depth.hip and shade.hip
-_MESH_CORE = os.path.join(CSRC, "mesh_core.h")           # the bodies behind mesh_stages.h: texture.hip includes them by this name
-_DEPTH_CORE = os.path.join(CSRC, "depth_core.h")         # the bodies behind depth_plane.h, likewise
+_MESH_CORE = os.path.join(CSRC, "mesh_core.h")         # the one copy of the projection and the coverage predicate, likewise
+_ZBUFFER_CORE = os.path.join(CSRC, "zbuffer_core.h")   # the one copy of the z-buffer (it includes mesh_core.h and depth_core.h, the
+                                                       # depth of a covered pixel): depth.hip, shade.hip and texture.hip
+_PIXEL_COLOR = os.path.join(CSRC, "pixel_color.h")     # the one copy of the colour of a covered pixel: shade.hip and texture.hip
 SIDE_LIBRARIES = {
     "head": (["head_metrics.hip"], "pvnet_head.h", []),          # the head metrics of a validation step
     "train": (["head_grad.hip"], "pvnet_train.h", []),           # the backward of the head losses of a training step
@@ -45,11 +44,10 @@ SIDE_LIBRARIES = {
     "color": (["color_jitter.hip"], "pvnet_color.h",              # the colour jitter, alone or fused behind that warp
               [_AUGMENT_WARP, os.path.join(ROOT, "include", "pvnet_augment.h")]),
     "classes": (["class_split.hip"], "pvnet_classes.h", []),     # class labels -> the bit masks the voting layer runs on
-    "raster": (["raster.hip"], "pvnet_raster.h", [_RASTER_COMMON, _MESH_STAGES]),   # poses and meshes -> silhouettes and label images
-    "depth": (["depth.hip"], "pvnet_depth.h", [_RASTER_COMMON, _MESH_STAGES, _DEPTH_PLANE]),   # ... -> depth, occlusion-correct labels,
-                                                                                               # visible pixel counts
-    "shade": (["shade.hip"], "pvnet_shade.h", [_MESH_STAGES, _DEPTH_PLANE]),   # ... -> shaded vertex-colour images over a background
-    "texture": (["texture.hip"], "pvnet_texture.h", [_MESH_CORE, _DEPTH_CORE]),   # ... -> the same with UV-mapped textures
+    "raster": (["raster.hip"], "pvnet_raster.h", [_MESH_CORE]),     # poses and meshes -> silhouettes and label images
+    "depth": (["depth.hip"], "pvnet_depth.h", [_ZBUFFER_CORE]),     # ... -> depth, occlusion-correct labels, visible pixel counts
+    "shade": (["shade.hip"], "pvnet_shade.h", [_ZBUFFER_CORE, _PIXEL_COLOR]),       # ... -> shaded vertex-colour images over a background
+    "texture": (["texture.hip"], "pvnet_texture.h", [_ZBUFFER_CORE, _PIXEL_COLOR]),   # ... -> the same with UV-mapped textures
 }
 
 

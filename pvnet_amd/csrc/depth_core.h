@@ -1,7 +1,7 @@
 // depth_core.h -- the ONE copy of the depth of a covered pixel under one triangle (include/pvnet_depth.h, THE DEFINITION): the plane of
-// inverse depth in float64, clamped to the triangle's z range.  Compiled by depth.hip (libpvnet_depth.so) and shade.hip
-// (libpvnet_shade.so) through depth_plane.h and by texture.hip (libpvnet_texture.so) from here: the depth a colour or textured render
-// writes is the depth render's because all three evaluate these functions.
+// inverse depth in float64, clamped to the triangle's z range.  Compiled by depth.hip (libpvnet_depth.so), shade.hip
+// (libpvnet_shade.so) and texture.hip (libpvnet_texture.so) with the triangle walk of zbuffer_core.h: the depth a colour or textured
+// render writes is the depth render's because all three evaluate these functions.
 //
 // Nothing here may be contracted into a fused multiply-add; float64 denormals are kept (the compiler's default for gfx950).
 #ifndef PVNET_DEPTH_CORE_H_

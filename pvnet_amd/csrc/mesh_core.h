@@ -1,7 +1,7 @@
-// mesh_core.h -- the bodies of stage P (pose -> float32 screen vertex) and of stage R's coverage predicate (include/pvnet_raster.h,
-// THE DEFINITION).  raster.hip and depth.hip reach them through raster_common.h and mesh_stages.h, shade.hip through mesh_stages.h,
-// texture.hip (libpvnet_texture.so) includes this header itself: a colour or textured image is covered exactly where the silhouette is
-// set and the depth image non-zero because all four evaluate these functions.
+// mesh_core.h -- the ONE copy of stage P (pose -> float32 screen vertex) and of stage R's coverage predicate (include/pvnet_raster.h,
+// THE DEFINITION).  raster.hip (libpvnet_raster.so) includes it itself; depth.hip, shade.hip and texture.hip compile it with the
+// z-buffer of zbuffer_core.h: a colour or textured image is covered exactly where the silhouette is set and the depth image non-zero
+// because all four libraries evaluate these functions.
 //
 // Nothing here may be contracted into a fused multiply-add (tests/test_raster_cpu.py looks for fused float32 instructions in the
 // assembly); float32 denormals are kept (the compiler's default for gfx950).

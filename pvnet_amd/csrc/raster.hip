@@ -24,7 +24,7 @@
 #include "vote_common.h"
 
 #include "pvnet_raster.h"
-#include "raster_common.h"   // project, make_edge, same_side, inside: shared with depth.hip
+#include "mesh_core.h"   // project, make_edge, same_side, inside: shared with depth.hip, shade.hip and texture.hip
 
 #pragma STDC FP_CONTRACT OFF
 

@@ -21,6 +21,7 @@ in a graph.  PyTorch is plumbing only.  There is NO CPU fallback: without the li
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -128,14 +129,32 @@ def render_color(meshes, mesh_ids, labels, poses, K, h, w, ambient=0.5, shading=
     :return: ``(rgb [b,h,w,3] uint8, depth [b,h,w] float32, labels [b,h,w] uint8[, visible [b,m] int32][, status [b,m] int32])``;
              depth, labels, visible and status are ``depth.render_depth``'s
     """
-    if not isinstance(meshes, ColorMeshes):
-        raise RuntimeError("meshes must be a ColorMeshes")
+    return _render(_SHADE, meshes, mesh_ids, labels, poses, K, h, w, ambient=ambient, shading=shading, background=background, far=far,
+                   out_rgb=out_rgb, out_depth=out_depth, out_labels=out_labels, workspace=workspace, return_visible=return_visible,
+                   return_status=return_status, max_instances=max_instances)
+
+
+# what tells render_color from texture.render_textured: the table they take, the limit, the workspace formula, the library, its entry point
+_FrontEnd = collections.namedtuple("_FrontEnd", "kind limit workspace_bytes load entry")
+_SHADE = _FrontEnd(ColorMeshes, SHADE_MAX_INSTANCES, shade_workspace_bytes, load_shade_library, "pvnet_render_color")
+
+
+def _render(front, meshes, mesh_ids, labels, poses, K, h, w, *, ambient, shading, background, far, out_rgb, out_depth, out_labels,
+            workspace, return_visible, return_status, max_instances, choice=None, extra=None):
+    """The body of ``render_color`` and of ``texture.render_textured``.  ``choice``: ``(name, value, allowed)`` of one more argument
+    that must be a key of ``allowed``, checked after ``shading``; ``extra(dev)``: the arguments the library takes between the normals
+    and the shading, as a tuple."""
+    kind, limit = front.kind, front.limit
+    if not isinstance(meshes, kind):
+        raise RuntimeError(f"meshes must be a {kind.__name__}")
     max_instances = int(max_instances)
-    if not 1 <= max_instances <= SHADE_MAX_INSTANCES:
-        raise RuntimeError(f"max_instances must lie in 1 .. {SHADE_MAX_INSTANCES}")
+    if not 1 <= max_instances <= limit:
+        raise RuntimeError(f"max_instances must lie in 1 .. {limit}")
     mesh_ids, labels, poses, h, w, far = _checked(meshes, mesh_ids, labels, poses, h, w, far, max_instances)
     if shading not in SHADING:
         raise RuntimeError(f"shading must be one of {sorted(SHADING)}")
+    if choice is not None and choice[1] not in choice[2]:
+        raise RuntimeError(f"{choice[0]} must be one of {sorted(choice[2])}")
     ambient = float(ambient)
     if not (math.isfinite(ambient) and ambient >= 0):
         raise RuntimeError("ambient must be finite and >= 0")
@@ -153,7 +172,8 @@ def render_color(meshes, mesh_ids, labels, poses, K, h, w, ambient=0.5, shading=
     visible = torch.empty(b * m, dtype=torch.int32, device=dev) if return_visible else None
     status = torch.empty(b * m, dtype=torch.int32, device=dev) if return_status else None
     if b:
-        lib = load_shade_library()
+        entry = getattr(front.load(), front.entry)
+        between = extra(dev) if extra is not None else ()
         Kd, per = _camera(K, dev, (b, m))
         vertices, faces, _ = meshes.on(dev)
         colors, normals = meshes.shading_on(dev)
@@ -163,16 +183,16 @@ def render_color(meshes, mesh_ids, labels, poses, K, h, w, ambient=0.5, shading=
             for i0, i1 in _image_stretches(b, m, max_instances):
                 nb, n = i1 - i0, (i1 - i0) * m
                 s = i0 * m
-                ws = _workspace(workspace, shade_workspace_bytes(n, nb, h, w, meshes), dev, align=16, sized=True)
+                ws = _workspace(workspace, front.workspace_bytes(n, nb, h, w, meshes), dev, align=16, sized=True)
                 arr = lambda vals: (C.c_int32 * max(n, 1))(*vals)   # noqa: E731
-                _check(lib.pvnet_render_color(
-                    _ptr(vertices), _ptr(faces), meshes._c_voff, meshes._c_foff, meshes.count, meshes.total_vertices, meshes.total_faces, n,
-                    arr(mesh_ids * nb), _ptr(flat[s:]) if n else None, _ptr(Kd[s:] if per else Kd), 1 if per else 0,
-                    arr([i for i in range(nb) for _ in range(m)]), arr(labels * nb), nb, h, w, far, _ptr(colors),
-                    _ptr(normals) if shading == "phong" else None, SHADING[shading], ambient, c_bg,
-                    _ptr(bg_image[i0:]) if bg_image is not None else None, _ptr(rgb[i0:]), _ptr(depth[i0:]), _ptr(label[i0:]),
-                    _ptr(visible[s:]) if visible is not None and n else None, _ptr(status[s:]) if status is not None and n else None,
-                    _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_render_color")
+                head = (_ptr(vertices), _ptr(faces), meshes._c_voff, meshes._c_foff, meshes.count, meshes.total_vertices,
+                        meshes.total_faces, n, arr(mesh_ids * nb), _ptr(flat[s:]) if n else None, _ptr(Kd[s:] if per else Kd),
+                        1 if per else 0, arr([i for i in range(nb) for _ in range(m)]), arr(labels * nb), nb, h, w, far, _ptr(colors),
+                        _ptr(normals) if shading == "phong" else None)
+                tail = (SHADING[shading], ambient, c_bg, _ptr(bg_image[i0:]) if bg_image is not None else None, _ptr(rgb[i0:]),
+                        _ptr(depth[i0:]), _ptr(label[i0:]), _ptr(visible[s:]) if visible is not None and n else None,
+                        _ptr(status[s:]) if status is not None and n else None, _ptr(ws), _nbytes(ws), _stream(dev))
+                _check(entry(*head, *between, *tail), front.entry)
     res = (rgb, depth, label)
     if return_visible:
         res += (visible.view(b, m),)

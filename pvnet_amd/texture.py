@@ -26,12 +26,9 @@ import math
 import numpy as np
 import torch
 
-from ._abi import (TEXTURE_BILINEAR, TEXTURE_MAX_INSTANCES, TEXTURE_MAX_SIDE, TEXTURE_NEAREST, _check,  # noqa: F401
-                   load_texture_library)
-from ._marshal import nbytes as _nbytes, ptr as _ptr, stream as _stream, workspace as _workspace
-from .depth import _checked, _image_stretches, _out   # the front end of the z-buffer: the same checks, the same split
-from .render import _camera
-from .shade import SHADING, ColorMeshes, _read_ply
+from ._abi import TEXTURE_BILINEAR, TEXTURE_MAX_INSTANCES, TEXTURE_MAX_SIDE, TEXTURE_NEAREST, load_texture_library
+from ._marshal import ptr as _ptr
+from .shade import SHADING, ColorMeshes, _FrontEnd, _read_ply, _render   # noqa: F401 (SHADING: this module's name for it too)
 
 FILTER = {"nearest": TEXTURE_NEAREST, "bilinear": TEXTURE_BILINEAR}
 
@@ -138,62 +135,16 @@ def render_textured(meshes, mesh_ids, labels, poses, K, h, w, ambient=0.5, shadi
     Every other parameter, and the return value, as ``shade.render_color``:
     ``(rgb [b,h,w,3] uint8, depth [b,h,w] float32, labels [b,h,w] uint8[, visible [b,m] int32][, status [b,m] int32])``.
     """
-    if not isinstance(meshes, TexturedMeshes):
-        raise RuntimeError("meshes must be a TexturedMeshes")
-    max_instances = int(max_instances)
-    if not 1 <= max_instances <= TEXTURE_MAX_INSTANCES:
-        raise RuntimeError(f"max_instances must lie in 1 .. {TEXTURE_MAX_INSTANCES}")
-    mesh_ids, labels, poses, h, w, far = _checked(meshes, mesh_ids, labels, poses, h, w, far, max_instances)
-    if shading not in SHADING:
-        raise RuntimeError(f"shading must be one of {sorted(SHADING)}")
-    if filter not in FILTER:
-        raise RuntimeError(f"filter must be one of {sorted(FILTER)}")
-    ambient = float(ambient)
-    if not (math.isfinite(ambient) and ambient >= 0):
-        raise RuntimeError("ambient must be finite and >= 0")
-    dev, b, m = poses.device, int(poses.shape[0]), int(poses.shape[1])
-    bg_image, bg_color = None, (0, 0, 0)
-    if isinstance(background, torch.Tensor):
-        bg_image = _out(background, (b, h, w, 3), torch.uint8, dev, "background")
-    elif background is not None:
-        bg_color = tuple(int(x) for x in background)
-        if len(bg_color) != 3 or any(not 0 <= x <= 255 for x in bg_color):
-            raise RuntimeError("background must be a colour triple in 0 .. 255 or a uint8 CUDA tensor [b,h,w,3]")
-    rgb = _out(out_rgb, (b, h, w, 3), torch.uint8, dev, "out_rgb")
-    depth = _out(out_depth, (b, h, w), torch.float32, dev, "out_depth")
-    label = _out(out_labels, (b, h, w), torch.uint8, dev, "out_labels")
-    visible = torch.empty(b * m, dtype=torch.int32, device=dev) if return_visible else None
-    status = torch.empty(b * m, dtype=torch.int32, device=dev) if return_status else None
-    if b:
-        lib = load_texture_library()
-        Kd, per = _camera(K, dev, (b, m))
-        vertices, faces, _ = meshes.on(dev)
-        colors, normals = meshes.shading_on(dev)
+    def extra(dev):
         uv, texels = meshes.textures_on(dev)
-        flat = poses.view(-1, 3, 4)
-        c_bg = (C.c_uint8 * 3)(*bg_color)
-        with torch.cuda.device(dev):
-            for i0, i1 in _image_stretches(b, m, max_instances):
-                nb, n = i1 - i0, (i1 - i0) * m
-                s = i0 * m
-                ws = _workspace(workspace, texture_workspace_bytes(n, nb, h, w, meshes), dev, align=16, sized=True)
-                arr = lambda vals: (C.c_int32 * max(n, 1))(*vals)   # noqa: E731
-                _check(lib.pvnet_render_textured(
-                    _ptr(vertices), _ptr(faces), meshes._c_voff, meshes._c_foff, meshes.count, meshes.total_vertices, meshes.total_faces, n,
-                    arr(mesh_ids * nb), _ptr(flat[s:]) if n else None, _ptr(Kd[s:] if per else Kd), 1 if per else 0,
-                    arr([i for i in range(nb) for _ in range(m)]), arr(labels * nb), nb, h, w, far, _ptr(colors),
-                    _ptr(normals) if shading == "phong" else None, _ptr(uv), _ptr(texels), meshes._c_toff, meshes._c_th, meshes._c_tw,
-                    FILTER[filter], SHADING[shading], ambient, c_bg,
-                    _ptr(bg_image[i0:]) if bg_image is not None else None, _ptr(rgb[i0:]), _ptr(depth[i0:]), _ptr(label[i0:]),
-                    _ptr(visible[s:]) if visible is not None and n else None, _ptr(status[s:]) if status is not None and n else None,
-                    _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_render_textured")
-    res = (rgb, depth, label)
-    if return_visible:
-        res += (visible.view(b, m),)
-    if return_status:
-        res += (status.view(b, m),)
-    return res
+        return _ptr(uv), _ptr(texels), meshes._c_toff, meshes._c_th, meshes._c_tw, FILTER[filter]
 
+    return _render(_TEXTURE, meshes, mesh_ids, labels, poses, K, h, w, ambient=ambient, shading=shading, background=background, far=far,
+                   out_rgb=out_rgb, out_depth=out_depth, out_labels=out_labels, workspace=workspace, return_visible=return_visible,
+                   return_status=return_status, max_instances=max_instances, choice=("filter", filter, FILTER), extra=extra)
+
+
+_TEXTURE = _FrontEnd(TexturedMeshes, TEXTURE_MAX_INSTANCES, texture_workspace_bytes, load_texture_library, "pvnet_render_textured")
 
 _UV_SPELLINGS = (("texture_u", "texture_v"), ("u", "v"), ("s", "t"))
 

@@ -42,8 +42,11 @@ def lib():
 
 def test_registry_row():
     assert build.SIDE_LIBRARIES["depth"][:2] == (["depth.hip"], "pvnet_depth.h")
-    shared = os.path.join(build.CSRC, "raster_common.h")
-    assert {n for n in build.SIDE_LIBRARIES if shared in build._side(n)[1]} == {"raster", "depth"}
+    shared, zbuffer = os.path.join(build.CSRC, "mesh_core.h"), os.path.join(build.CSRC, "zbuffer_core.h")
+    assert build.SIDE_LIBRARIES["depth"][2] == [zbuffer] and build.SIDE_LIBRARIES["raster"][2] == [shared]
+    # the projection and the coverage predicate rebuild the silhouette library and the three that render through the z-buffer
+    assert {n for n in build.SIDE_LIBRARIES if shared in build._side(n)[1]} == {"raster", "depth", "shade", "texture"}
+    assert {n for n in build.SIDE_LIBRARIES if zbuffer in build._side(n)[1]} == {"depth", "shade", "texture"}
     assert _abi.SIDE_LIBRARIES["depth"] == (_abi.DEPTH_LIB_PATH, _abi.DEPTH_ABI_VERSION, _abi.DEPTH_PROTOTYPES)
     assert _abi.load_depth_library.args == ("depth",)
 

@@ -54,16 +54,18 @@ def lib():
 
 def test_registry_row():
     assert build.SIDE_LIBRARIES["shade"][:2] == (["shade.hip"], "pvnet_shade.h")
-    stages, plane = os.path.join(build.CSRC, "mesh_stages.h"), os.path.join(build.CSRC, "depth_plane.h")
-    assert build.SIDE_LIBRARIES["shade"][2] == [stages, plane]
-    assert os.path.join(build.CSRC, "raster_common.h") not in build._side("shade")[1]
+    zbuffer, color = os.path.join(build.CSRC, "zbuffer_core.h"), os.path.join(build.CSRC, "pixel_color.h")
+    stages, plane = os.path.join(build.CSRC, "mesh_core.h"), os.path.join(build.CSRC, "depth_core.h")
+    assert build.SIDE_LIBRARIES["shade"][2] == [zbuffer, color]
     # the headers rebuild exactly the libraries that compile them
-    assert {n for n in build.SIDE_LIBRARIES if stages in build._side(n)[1]} == {"raster", "depth", "shade"}
-    assert {n for n in build.SIDE_LIBRARIES if plane in build._side(n)[1]} == {"depth", "shade"}
+    assert {n for n in build.SIDE_LIBRARIES if stages in build._side(n)[1]} == {"raster", "depth", "shade", "texture"}
+    assert {n for n in build.SIDE_LIBRARIES if plane in build._side(n)[1]} == {"depth", "shade", "texture"}
+    assert {n for n in build.SIDE_LIBRARIES if zbuffer in build._side(n)[1]} == {"depth", "shade", "texture"}
+    assert {n for n in build.SIDE_LIBRARIES if color in build._side(n)[1]} == {"shade", "texture"}
     text = open(os.path.join(build.CSRC, "shade.hip")).read()
-    assert '#include "mesh_stages.h"' in text and '#include "depth_plane.h"' in text and '#include "raster_common.h"' not in text
-    assert '#include "mesh_stages.h"' in open(os.path.join(build.CSRC, "raster_common.h")).read()
-    assert '#include "depth_plane.h"' in open(os.path.join(build.CSRC, "depth.hip")).read()
+    assert '#include "pixel_color.h"' in text and '#include "zbuffer_core.h"' in open(color).read()
+    assert '#include "mesh_core.h"' in open(zbuffer).read() and '#include "depth_core.h"' in open(zbuffer).read()
+    assert '#include "zbuffer_core.h"' in open(os.path.join(build.CSRC, "depth.hip")).read()
     assert _abi.SIDE_LIBRARIES["shade"] == (_abi.SHADE_LIB_PATH, _abi.SHADE_ABI_VERSION, _abi.SHADE_PROTOTYPES)
     assert _abi.load_shade_library.args == ("shade",)
 

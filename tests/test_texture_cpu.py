@@ -9,6 +9,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -36,20 +37,22 @@ def lib():
 # ---- 1. the registry row and the ABI mirror ---------------------------------------------------------------------------------------------
 def test_registry_row():
     core, plane = os.path.join(build.CSRC, "mesh_core.h"), os.path.join(build.CSRC, "depth_core.h")
-    assert build.SIDE_LIBRARIES["texture"] == (["texture.hip"], "pvnet_texture.h", [core, plane])
+    zbuffer, color = os.path.join(build.CSRC, "zbuffer_core.h"), os.path.join(build.CSRC, "pixel_color.h")
+    assert build.SIDE_LIBRARIES["texture"] == (["texture.hip"], "pvnet_texture.h", [zbuffer, color])
     assert list(build.SIDE_LIBRARIES)[-1] == "texture" == list(_abi.SIDE_LIBRARIES)[-1]
     assert _abi.SIDE_LIBRARIES["texture"] == (_abi.TEXTURE_LIB_PATH, _abi.TEXTURE_ABI_VERSION, _abi.TEXTURE_PROTOTYPES)
     assert _abi.load_texture_library.args == ("texture",)
-    # the inner headers hold the bodies; the headers the other three libraries name only include them, under their old guards
-    for outer, inner, guard, body in (("mesh_stages.h", "mesh_core.h", "PVNET_MESH_STAGES_H_", "same_side"),
-                                      ("depth_plane.h", "depth_core.h", "PVNET_DEPTH_PLANE_H_", "pixel_depth")):
-        text = open(os.path.join(build.CSRC, outer)).read()
+    # each shared header holds its bodies under its own guard
+    for header, guard, body in (("mesh_core.h", "PVNET_MESH_CORE_H_", "same_side"), ("depth_core.h", "PVNET_DEPTH_CORE_H_", "pixel_depth"),
+                                ("zbuffer_core.h", "PVNET_ZBUFFER_CORE_H_", "tri_body"), ("pixel_color.h", "PVNET_PIXEL_COLOR_H_", "pixel_color")):
+        text = open(os.path.join(build.CSRC, header)).read()
         code = "\n".join(line.split("//")[0] for line in text.splitlines())
-        assert f"#ifndef {guard}" in code and f'#include "{inner}"' in code and "__device__" not in code and body not in code
-        assert body in open(os.path.join(build.CSRC, inner)).read()
-    # the inner headers rebuild the four libraries that compile them, and nothing else
+        assert f"#ifndef {guard}" in code and "__device__" in code and body in code, header
+    # each shared header rebuilds the libraries that compile it, and nothing else
     assert {n for n in build.SIDE_LIBRARIES if core in build._side(n)[1]} == {"raster", "depth", "shade", "texture"}
     assert {n for n in build.SIDE_LIBRARIES if plane in build._side(n)[1]} == {"depth", "shade", "texture"}
+    assert {n for n in build.SIDE_LIBRARIES if zbuffer in build._side(n)[1]} == {"depth", "shade", "texture"}
+    assert {n for n in build.SIDE_LIBRARIES if color in build._side(n)[1]} == {"shade", "texture"}
     assert "_abi.load_texture_library()" in open(os.path.join(ROOT, "__graft_entry__.py")).read()
     import pvnet_amd   # the front end is exported from the package
     for name in ("TexturedMeshes", "render_textured", "read_textured_ply", "texture_workspace_bytes"):
@@ -118,22 +121,46 @@ def test_build_dependencies_are_complete(name):
     assert reachable(deps) <= set(deps)   # closed: a listed header's own includes are listed too
 
 
+SHARED = {"raster": {"mesh_core.h"}, "depth": {"mesh_core.h", "depth_core.h", "zbuffer_core.h"},
+          "shade": {"mesh_core.h", "depth_core.h", "zbuffer_core.h", "pixel_color.h"},
+          "texture": {"mesh_core.h", "depth_core.h", "zbuffer_core.h", "pixel_color.h"}}   # the shared headers each renderer compiles
+
+
 def test_texture_reaches_the_inner_headers_only():
-    names = {os.path.basename(p) for p in reachable(build._side("texture")[0])}
-    assert {"mesh_core.h", "depth_core.h", "vote_common.h"} <= names
-    assert not names & {"mesh_stages.h", "depth_plane.h", "raster_common.h"}
-    deps = {os.path.basename(p) for p in build._side("texture")[1]}
-    assert not deps & {"mesh_stages.h", "depth_plane.h", "raster_common.h"}
-    for other, want in (("raster", {"raster_common.h", "mesh_stages.h", "mesh_core.h"}),
-                        ("depth", {"raster_common.h", "mesh_stages.h", "mesh_core.h", "depth_plane.h", "depth_core.h"}),
-                        ("shade", {"mesh_stages.h", "mesh_core.h", "depth_plane.h", "depth_core.h"})):
-        assert want <= {os.path.basename(p) for p in build._side(other)[1]}, other
-    # a library is stale when an inner header is newer than it
-    core = os.path.join(build.CSRC, "mesh_core.h")
-    for name in ("raster", "depth", "shade", "texture"):
+    every = set().union(*SHARED.values())
+    common = {"vote_common.h", "pvnet_rng.h"}   # what every library of the project compiles
+    assert every == {os.path.basename(p) for p in reachable([os.path.join(build.CSRC, "texture.hip")])} - common
+    for name, want in SHARED.items():   # what a library's sources reach, and what rebuilds it: these and no other shared header
+        names = {os.path.basename(p) for p in reachable(build._side(name)[0])}
+        assert names - common == want and "vote_common.h" in names, name
+        assert {os.path.basename(p) for p in build._side(name)[1]} & every == want, name
+    for gone in ("mesh_stages.h", "depth_plane.h", "raster_common.h"):   # no forwarding header is left
+        assert not os.path.exists(os.path.join(build.CSRC, gone)), gone
+    # a library is stale when a shared header is newer than it
+    for name, want in SHARED.items():
         _, deps, target = build._side(name)
-        assert core in deps and build.fresh(target, deps) == (os.path.exists(target) and
-                                                              all(os.path.getmtime(target) >= os.path.getmtime(d) for d in deps))
+        assert all(os.path.join(build.CSRC, header) in deps for header in want)
+        assert build.fresh(target, deps) == (os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(d) for d in deps))
+    with tempfile.NamedTemporaryFile() as target:
+        for header in sorted(every):
+            path = os.path.join(build.CSRC, header)
+            stamp = os.path.getmtime(path)
+            os.utime(target.name, (stamp - 10, stamp - 10))
+            assert not build.fresh(target.name, [path]), header
+            os.utime(target.name, (stamp, stamp))
+            assert build.fresh(target.name, [path]), header
+
+
+def test_the_z_buffer_and_the_pixel_colour_are_written_once():
+    """the sharing is real: among the translation units and headers of the three z-buffer libraries, the atomic minimum of the walk, the
+    call that makes a triangle's depth plane and the resolve kernels' pixel split each occur in exactly one file"""
+    files = set()
+    for name in ("depth", "shade", "texture"):
+        files |= {p for p in build._side(name)[1] if os.path.dirname(p) == build.CSRC}
+    assert {os.path.basename(p) for p in files} >= {"depth.hip", "shade.hip", "texture.hip", "zbuffer_core.h", "pixel_color.h"}
+    code = {p: "\n".join(line.split("//")[0] for line in open(p).read().splitlines()) for p in files}
+    for what, where in (("atomicMin(", "zbuffer_core.h"), ("= make_plane(", "zbuffer_core.h"), ("__umul64hi(", "pixel_color.h")):
+        assert [os.path.basename(p) for p, text in code.items() if what in text] == [where], what
 
 
 # ---- 3. the built library ----------------------------------------------------------------------------------------------------------------
