@@ -29,9 +29,11 @@ def available() -> bool:
 
 
 class Capture:
-    """What the driver handed to the extension: per image the idxs it drew (:547) and the pixels it kept (:542)."""
+    """What the driver handed to the extension: per image the idxs it drew (:547) and the pixels it kept (:542); and what it got back
+    in its last round: the hypotheses [hn,vn,2] float32 (:554) and the inlier counts ``inliers.sum(-1)`` [hn,vn] that :557-561 sums."""
     def __init__(self):
         self.idxs, self.coords, self.tn, self.rounds = [], [], [], []
+        self.hyp, self.counts = [], []
 
 
 @contextlib.contextmanager
@@ -39,6 +41,7 @@ def reference_driver(capture: Capture | None = None):
     import torch
     from oracle import cref
     stub = types.ModuleType(_NAMES[2])
+    last_hyp = [None]  # the tensor the stub returned last: the driver hands it back to be scored (:558), the refinement (:584) does not
 
     def generate_hypothesis(direct, coords, idxs):
         if capture is not None:
@@ -52,13 +55,21 @@ def reference_driver(capture: Capture | None = None):
                 capture.coords.append(c_np)
                 capture.tn.append(int(c_np.shape[0]))
                 capture.rounds.append(1)
-        return torch.from_numpy(cref.generate_hypothesis(direct.contiguous().numpy(), coords.contiguous().numpy(),
-                                                         idxs.contiguous().numpy()))
+                capture.hyp.append(None)
+                capture.counts.append(None)
+        hyp = torch.from_numpy(cref.generate_hypothesis(direct.contiguous().numpy(), coords.contiguous().numpy(),
+                                                        idxs.contiguous().numpy()))
+        if capture is not None:
+            capture.hyp[-1] = hyp.numpy().copy()
+            last_hyp[0] = hyp
+        return hyp
 
     def voting_for_hypothesis(direct, coords, hypo_pts, inliers, inlier_thresh):
         assert inliers.is_contiguous() and inliers.dtype == torch.uint8
         cref.voting_for_hypothesis(direct.contiguous().numpy(), coords.contiguous().numpy(),
                                    hypo_pts.contiguous().numpy(), inliers.numpy(), float(inlier_thresh))
+        if capture is not None and hypo_pts is last_hyp[0]:
+            capture.counts[-1] = inliers.numpy().sum(-1, dtype=np.int64)
 
     stub.generate_hypothesis = generate_hypothesis
     stub.voting_for_hypothesis = voting_for_hypothesis

@@ -14,6 +14,13 @@ G6  ref_driver_v3.npz -- outputs of the REFERENCE'S OWN ransac_voting_layer_v3 (
 G7  ref_driver_siblings.npz -- the same for the reference's sibling functions of the "next" rows of SURVEY section 8(f):
                       ransac_voting_layer_v5 (:763-858), estimate_voting_distribution_with_mean (:333-406),
                       ransac_motion_voting (:960-981) and the Python-level generate_hypothesis (:983-1034).
+G6L ref_driver_layout_{A..E}.npz -- the same executed driver at the shapes where the release library does something else than at G6's:
+                      A (b 8, vn 9, hn 1024, clean and noisy images alternating), B (b 6, vn 12, hn 800, one image of three pixels) and
+                      C (b 8, vn 8, hn 768, thinned by max_num) get a disc-culling layout; D is the BASELINE shape 2 x 480 x 640 at hn 1024,
+                      E the reference demo's own call (the cat mask, hn 512), both scored densely.  Stored per case: key-points, live
+                      images, tn, rounds, kept-pixel bits, the draws (uint16), the first-index winners and their counts, and a sha256 per
+                      image of the hypotheses' bytes and of the counts as int32 (the arrays themselves would double the files).
+G7L ref_driver_layout_sib_{v5,dist,gh}.npz -- the siblings of G7 on A's inputs at hn 1024.
 G8  reference_callers.json -- how the reference's OWN tools/demo.py and tools/train_linemod.py call the voting layer:
                       both scripts imported UNCHANGED through tools/refshim.py (their five voting-layer imports bind this
                       repository's HIP functions), every EvalWrapper's forward() run with recorders in place of the layer
@@ -162,6 +169,111 @@ def make_ref_siblings():
           "| cov[0,0]", cov[0, 0].round(4).tolist())
 
 
+# G6L: the executed driver at the layouts the release library treats differently.  Case letters, what each reaches: the docstring above.
+REF_DRIVER_LAYOUT_CASES = {
+    "A": dict(b=8, vn=9, first_index=1000, h=96, w=128, radius=14, noise="alternate", hn=1024, kw=dict(inlier_thresh=0.99),
+              edit="none", torch_seed=200),
+    "B": dict(b=6, vn=12, first_index=1020, h=72, w=96, radius=10, noise=True, hn=800, kw=dict(inlier_thresh=0.999),
+              edit="image2_three_pixels", torch_seed=201),
+    "C": dict(b=8, vn=8, first_index=1040, h=96, w=128, radius=14, noise=True, hn=768, kw=dict(inlier_thresh=0.99, max_num=300),
+              edit="none", torch_seed=202),
+    "D": dict(b=2, vn=9, first_index=1062, h=480, w=640, radius=40, noise=True, hn=1024, kw=dict(inlier_thresh=0.99),
+              edit="none", torch_seed=203),
+    "E": dict(b=1, vn=9, demo=True, noise_seed=1080, h=480, w=640, hn=512, kw=dict(inlier_thresh=0.99), edit="none", torch_seed=204),
+}
+LAYOUT_SIBLINGS = ("v5", "dist", "gh")   # G7L, on case A's inputs: one file each (the draws of one are ~200 KB)
+LAYOUT_SIBLING_SEEDS = dict(v5=210, dist=211, gh=212)
+LAYOUT_DIST = dict(round_hyp_num=256, min_hyp_num=1024)
+
+
+def layout_fixture_path(name):
+    return os.path.join(OUT, f"ref_driver_layout_{name}.npz")
+
+
+def ref_driver_layout_inputs(case):
+    """mask [b,h,w] int64, vertex view [b,h,w,vn,2], true key-points [b,vn,2] of one G6L case (shared with the tests)."""
+    from pvnet_amd import synth
+    if case.get("demo"):                                   # tools/demo.py: the cat mask, a noisy field towards points_2d
+        g = np.load(os.path.join(OUT, "demo_cat.npz"))
+        h, w = (int(x) for x in g["shape"])
+        fg = np.unpackbits(g["mask_bits"])[:h * w].reshape(h, w).astype(bool)
+        rng = np.random.default_rng(case["noise_seed"])
+        planar = synth.add_noise(synth.field_from_keypoints(fg, g["points_2d"], "normal", rng), fg, rng)
+        return fg.astype(np.int64)[None], synth.planar_to_vertex_view(planar[None]), g["points_2d"][None].astype(np.float64)
+    kw = dict(h=case["h"], w=case["w"], vn=case["vn"], radius=case["radius"], background="normal")
+    if case["noise"] == "alternate":                       # even images clean, odd images noisy
+        ms, ps, ks = zip(*(synth.make_image(case["first_index"] + i, noise=bool(i % 2), **kw) for i in range(case["b"])))
+        mask, planar, kpts = np.stack(ms), np.stack(ps), np.stack(ks)
+    else:
+        mask, planar, kpts = synth.make_batch(case["b"], first_index=case["first_index"], noise=case["noise"], **kw)
+    if case["edit"] == "image2_three_pixels":
+        mask[2] = 0
+        mask[2, 7, 10:13] = 1
+    return mask, synth.planar_to_vertex_view(planar), kpts
+
+
+def pack_idxs(idxs, tn):
+    return idxs.astype(np.uint16 if max(tn) <= 1 << 16 else np.int32)
+
+
+def sha256_rows(arrays, dtype):
+    import hashlib
+    return np.stack([np.frombuffer(hashlib.sha256(np.ascontiguousarray(a, dtype).tobytes()).digest(), np.uint8) for a in arrays])
+
+
+def first_index_winners(counts):
+    """[n][hn,vn] counts -> first-index winners [n,vn] int32 and their counts (torch.max(., 0) on CPU tensors, :562)"""
+    wi = np.stack([c.argmax(axis=0) for c in counts]).astype(np.int32)
+    wc = np.stack([c.max(axis=0) for c in counts]).astype(np.int32)
+    return wi, wc
+
+
+def layout_case_record(name):
+    """runs the reference driver on one G6L case -> the dict that is stored"""
+    from oracle import ref_driver
+    case = REF_DRIVER_LAYOUT_CASES[name]
+    mask, vertex, kpts = ref_driver_layout_inputs(case)
+    out, cap = ref_driver.run_v3(mask, vertex, case["hn"], torch_seed=case["torch_seed"], **case["kw"])
+    live = [bi for bi in range(mask.shape[0]) if int((mask[bi].astype(np.uint8) != 0).sum()) >= case["kw"].get("min_num", 5)]
+    assert len(live) == len(cap.idxs) == len(cap.hyp) == len(cap.counts)
+    wi, wc = first_index_winners(cap.counts)
+    rec = dict(out=out, live=np.array(live), tn=np.array(cap.tn), rounds=np.array(cap.rounds),
+               keep_bits=np.packbits(keep_from_capture(cap, live, mask.shape)), idxs=pack_idxs(np.stack(cap.idxs), cap.tn),
+               win_idx=wi, win_cnt=wc, hyp_sha=sha256_rows(cap.hyp, np.float32), cnt_sha=sha256_rows(cap.counts, np.int32))
+    print(f"ref driver layout case {name}: live {live} tn {cap.tn} rounds {cap.rounds} max|out-kpt| "
+          f"{np.abs(out[live] - kpts[live]).max():.3f} px")
+    return rec
+
+
+def layout_sibling_record(name):
+    from oracle import ref_driver
+    case = REF_DRIVER_LAYOUT_CASES["A"]
+    mask, vertex, kpts = ref_driver_layout_inputs(case)
+    b, hn, seed = mask.shape[0], case["hn"], LAYOUT_SIBLING_SEEDS[name]
+    if name == "v5":     # default max_num=100: every image thinned to ~100 pixels inside 256-pixel work items
+        (pts, conf), cap = ref_driver.run("ransac_voting_layer_v5", mask, vertex, hn, torch_seed=seed, inlier_thresh=0.99)
+        return dict(pts=pts, conf=conf, keep_bits=np.packbits(keep_from_capture(cap, range(b), mask.shape)),
+                    idxs=pack_idxs(np.stack(cap.idxs), cap.tn), tn=np.array(cap.tn))
+    if name == "dist":   # four rounds of 256 independent pairs = one draw of 1024
+        mean = kpts.astype(np.float32)
+        (_, cov), cap = ref_driver.run("estimate_voting_distribution_with_mean", mask, vertex, mean, torch_seed=seed,
+                                       inlier_thresh=0.99, **LAYOUT_DIST)
+        rounds = len(cap.idxs) // b
+        idxs = np.stack([np.concatenate(cap.idxs[bi * rounds:(bi + 1) * rounds], 0) for bi in range(b)])
+        return dict(mean=mean, cov=cov, idxs=pack_idxs(idxs, cap.tn), rounds=np.array(rounds))
+    (hyp, counts), cap = ref_driver.run("generate_hypothesis", mask, vertex, hn, torch_seed=seed, inlier_thresh=0.99)
+    return dict(idxs=pack_idxs(np.stack(cap.idxs), cap.tn), hyp_sha=sha256_rows(hyp, np.float32), cnt_sha=sha256_rows(counts, np.int32))
+
+
+def make_ref_driver_layouts():
+    for name in REF_DRIVER_LAYOUT_CASES:
+        np.savez_compressed(layout_fixture_path(name), **layout_case_record(name))
+    for name in LAYOUT_SIBLINGS:
+        np.savez_compressed(layout_fixture_path("sib_" + name), **layout_sibling_record(name))
+    print("ref driver layouts:", {n: os.path.getsize(layout_fixture_path(n)) for n in
+                                  list(REF_DRIVER_LAYOUT_CASES) + ["sib_" + s for s in LAYOUT_SIBLINGS]})
+
+
 def make_reference_callers():
     import json
     import subprocess
@@ -216,6 +328,7 @@ if __name__ == "__main__":
         make_demo()
         make_ref_driver()
         make_ref_siblings()
+        make_ref_driver_layouts()
         make_backbone()
     else:
         print("no /root/reference: demo and reference-driver fixtures not regenerated")
