@@ -11,12 +11,16 @@ from .voting import (estimate_voting_distribution_with_mean, generate_hypothesis
                      ransac_voting_layer_v5, voting_for_hypothesis)
 
 _TEXTURE = ("TexturedMeshes", "render_textured", "read_textured_ply", "texture_workspace_bytes")   # pvnet_amd.texture, on first use
+_TAIL = ("TailParams", "fused_tail", "FusedTailNet")   # pvnet_amd.tail, on first use
 
-__all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE]
+__all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE, *_TAIL]
 
 
 def __getattr__(name):
     if name in _TEXTURE:
         from . import texture
         return getattr(texture, name)
+    if name in _TAIL:
+        from . import tail
+        return getattr(tail, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -260,6 +260,20 @@ SHADE_PROTOTYPES = {
                            DEPTH_PROTOTYPES["pvnet_render_depth"][1][18:]),
 }
 
+# ---- libpvnet_tail.so (include/pvnet_tail.h): the network's tail in one launch -- upsample, concat, 3 x 3 and 1 x 1 convolution; it takes
+# E_* above --------------------------------------------------------------------------------------------------------------------------------
+TAIL_LIB_PATH = os.path.join(_HERE, "libpvnet_tail.so")
+TAIL_ABI_VERSION = 1
+TAIL_WIDTH, TAIL_MAX_COUT = 32, 32
+TAIL_T_F32, TAIL_T_F16, TAIL_T_BF16 = 0, 1, 2
+TAIL_BF16, TAIL_F32 = 0, 1     # precision
+TAIL_F_RAW = 1
+TAIL_PROTOTYPES = {
+    "pvnet_tail_abi_version": (_int, []),
+    # fm + type + strides, image + type + strides, w1, b1, w2, b2, b, hin, win, h, w, feat, raw, cout, precision, flags, out + type, stream
+    "pvnet_tail_forward": (_int, [_ptr, _int, _i64p, _ptr, _int, _i64p, _ptr, _ptr, _ptr, _ptr] + [_int] * 9 + [C.c_uint32, _ptr, _int, _ptr]),
+}
+
 # ---- libpvnet_texture.so (include/pvnet_texture.h): pvnet_render_color with UV-mapped textures; a mesh without one is shaded as there ----
 TEXTURE_LIB_PATH = os.path.join(_HERE, "libpvnet_texture.so")
 TEXTURE_ABI_VERSION = 1
@@ -297,6 +311,7 @@ SIDE_LIBRARIES = {
     "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
     "depth": SideLibrary(DEPTH_LIB_PATH, DEPTH_ABI_VERSION, DEPTH_PROTOTYPES),
     "shade": SideLibrary(SHADE_LIB_PATH, SHADE_ABI_VERSION, SHADE_PROTOTYPES),
+    "tail": SideLibrary(TAIL_LIB_PATH, TAIL_ABI_VERSION, TAIL_PROTOTYPES),
     "texture": SideLibrary(TEXTURE_LIB_PATH, TEXTURE_ABI_VERSION, TEXTURE_PROTOTYPES),
 }
 
@@ -363,6 +378,7 @@ load_classes_library = functools.partial(_load_side, "classes")
 load_raster_library = functools.partial(_load_side, "raster")
 load_depth_library = functools.partial(_load_side, "depth")
 load_shade_library = functools.partial(_load_side, "shade")
+load_tail_library = functools.partial(_load_side, "tail")
 load_texture_library = functools.partial(_load_side, "texture")
 
 
