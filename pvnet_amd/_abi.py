@@ -260,6 +260,20 @@ SHADE_PROTOTYPES = {
                            DEPTH_PROTOTYPES["pvnet_render_depth"][1][18:]),
 }
 
+# ---- libpvnet_decoder.so (include/pvnet_decoder.h): a decoder stage in one launch -- upsample, concat, 3 x 3 convolution, LeakyReLU; it
+# takes E_* above ----------------------------------------------------------------------------------------------------------------------------
+DECODER_LIB_PATH = os.path.join(_HERE, "libpvnet_decoder.so")
+DECODER_ABI_VERSION = 1
+DECODER_SKIP = 64              # channels of skip
+DECODER_T_F32, DECODER_T_F16, DECODER_T_BF16 = 0, 1, 2
+DECODER_F_PACKED = 1           # w is the bfloat16 fragment-order image of the weights
+DECODER_SHAPES = ((64, 64, 32), (128, 64, 64))   # (cl, cs, co): conv2s and conv4s of Resnet18_8s
+DECODER_PROTOTYPES = {
+    "pvnet_decoder_abi_version": (_int, []),
+    # lo + type + strides, skip + type + strides, w, bias, b, hin, win, h, w_, cl, cs, co, flags, out + type, stream
+    "pvnet_decoder_stage": (_int, [_ptr, _int, _i64p, _ptr, _int, _i64p, _ptr, _ptr] + [_int] * 8 + [C.c_uint32, _ptr, _int, _ptr]),
+}
+
 # ---- libpvnet_tail.so (include/pvnet_tail.h): the network's tail in one launch -- upsample, concat, 3 x 3 and 1 x 1 convolution; it takes
 # E_* above --------------------------------------------------------------------------------------------------------------------------------
 TAIL_LIB_PATH = os.path.join(_HERE, "libpvnet_tail.so")
@@ -311,6 +325,7 @@ SIDE_LIBRARIES = {
     "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
     "depth": SideLibrary(DEPTH_LIB_PATH, DEPTH_ABI_VERSION, DEPTH_PROTOTYPES),
     "shade": SideLibrary(SHADE_LIB_PATH, SHADE_ABI_VERSION, SHADE_PROTOTYPES),
+    "decoder": SideLibrary(DECODER_LIB_PATH, DECODER_ABI_VERSION, DECODER_PROTOTYPES),
     "tail": SideLibrary(TAIL_LIB_PATH, TAIL_ABI_VERSION, TAIL_PROTOTYPES),
     "texture": SideLibrary(TEXTURE_LIB_PATH, TEXTURE_ABI_VERSION, TEXTURE_PROTOTYPES),
 }
@@ -378,6 +393,7 @@ load_classes_library = functools.partial(_load_side, "classes")
 load_raster_library = functools.partial(_load_side, "raster")
 load_depth_library = functools.partial(_load_side, "depth")
 load_shade_library = functools.partial(_load_side, "shade")
+load_decoder_library = functools.partial(_load_side, "decoder")
 load_tail_library = functools.partial(_load_side, "tail")
 load_texture_library = functools.partial(_load_side, "texture")
 
