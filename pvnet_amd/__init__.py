@@ -13,8 +13,9 @@ from .voting import (estimate_voting_distribution_with_mean, generate_hypothesis
 _TEXTURE = ("TexturedMeshes", "render_textured", "read_textured_ply", "texture_workspace_bytes")   # pvnet_amd.texture, on first use
 _TAIL = ("TailParams", "fused_tail", "FusedTailNet")   # pvnet_amd.tail, on first use
 _DECODER = ("StageParams", "fused_stage", "FusedDecoderNet")   # pvnet_amd.decoder, on first use
+_STEM = ("StemParams", "fused_stem", "FusedStemNet")   # pvnet_amd.stem, on first use
 
-__all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE, *_TAIL, *_DECODER]
+__all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE, *_TAIL, *_DECODER, *_STEM]
 
 
 def __getattr__(name):
@@ -27,4 +28,7 @@ def __getattr__(name):
     if name in _DECODER:
         from . import decoder
         return getattr(decoder, name)
+    if name in _STEM:
+        from . import stem
+        return getattr(stem, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

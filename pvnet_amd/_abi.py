@@ -288,6 +288,18 @@ TAIL_PROTOTYPES = {
     "pvnet_tail_forward": (_int, [_ptr, _int, _i64p, _ptr, _int, _i64p, _ptr, _ptr, _ptr, _ptr] + [_int] * 9 + [C.c_uint32, _ptr, _int, _ptr]),
 }
 
+# ---- libpvnet_stem.so (include/pvnet_stem.h): the network's stem in one launch -- 7 x 7 stride-2 convolution, ReLU, 3 x 3 stride-2
+# max-pool; it takes E_* above ----------------------------------------------------------------------------------------------------------------
+STEM_LIB_PATH = os.path.join(_HERE, "libpvnet_stem.so")
+STEM_ABI_VERSION = 1
+STEM_CIN, STEM_COUT = 3, 64
+STEM_T_F32, STEM_T_F16, STEM_T_BF16 = 0, 1, 2
+STEM_PROTOTYPES = {
+    "pvnet_stem_abi_version": (_int, []),
+    # image + type + strides, w, bias, b, h, w_, x2s, pooled, out type, stream
+    "pvnet_stem_forward": (_int, [_ptr, _int, _i64p, _ptr, _ptr, _int, _int, _int, _ptr, _ptr, _int, _ptr]),
+}
+
 # ---- libpvnet_texture.so (include/pvnet_texture.h): pvnet_render_color with UV-mapped textures; a mesh without one is shaded as there ----
 TEXTURE_LIB_PATH = os.path.join(_HERE, "libpvnet_texture.so")
 TEXTURE_ABI_VERSION = 1
@@ -325,6 +337,7 @@ SIDE_LIBRARIES = {
     "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
     "depth": SideLibrary(DEPTH_LIB_PATH, DEPTH_ABI_VERSION, DEPTH_PROTOTYPES),
     "shade": SideLibrary(SHADE_LIB_PATH, SHADE_ABI_VERSION, SHADE_PROTOTYPES),
+    "stem": SideLibrary(STEM_LIB_PATH, STEM_ABI_VERSION, STEM_PROTOTYPES),
     "decoder": SideLibrary(DECODER_LIB_PATH, DECODER_ABI_VERSION, DECODER_PROTOTYPES),
     "tail": SideLibrary(TAIL_LIB_PATH, TAIL_ABI_VERSION, TAIL_PROTOTYPES),
     "texture": SideLibrary(TEXTURE_LIB_PATH, TEXTURE_ABI_VERSION, TEXTURE_PROTOTYPES),
@@ -393,6 +406,7 @@ load_classes_library = functools.partial(_load_side, "classes")
 load_raster_library = functools.partial(_load_side, "raster")
 load_depth_library = functools.partial(_load_side, "depth")
 load_shade_library = functools.partial(_load_side, "shade")
+load_stem_library = functools.partial(_load_side, "stem")
 load_decoder_library = functools.partial(_load_side, "decoder")
 load_tail_library = functools.partial(_load_side, "tail")
 load_texture_library = functools.partial(_load_side, "texture")
