@@ -14,8 +14,10 @@ _TEXTURE = ("TexturedMeshes", "render_textured", "read_textured_ply", "texture_w
 _TAIL = ("TailParams", "fused_tail", "FusedTailNet")   # pvnet_amd.tail, on first use
 _DECODER = ("StageParams", "fused_stage", "FusedDecoderNet")   # pvnet_amd.decoder, on first use
 _STEM = ("StemParams", "fused_stem", "FusedStemNet")   # pvnet_amd.stem, on first use
+_TRUNK = ("ConvParams", "fused_conv3x3", "FusedBasicBlock", "FusedTrunkNet")   # pvnet_amd.trunk, on first use
 
-__all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE, *_TAIL, *_DECODER, *_STEM]
+__all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE, *_TAIL, *_DECODER, *_STEM,
+           *_TRUNK]
 
 
 def __getattr__(name):
@@ -31,4 +33,7 @@ def __getattr__(name):
     if name in _STEM:
         from . import stem
         return getattr(stem, name)
+    if name in _TRUNK:
+        from . import trunk
+        return getattr(trunk, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -319,6 +319,22 @@ TEXTURE_PROTOTYPES = {
                               SHADE_PROTOTYPES["pvnet_render_color"][1][20:]),
 }
 
+# ---- libpvnet_trunk.so (include/pvnet_trunk.h): a 3 x 3 convolution of the residual trunk in one launch -- one or two inputs, BatchNorm
+# folded in, residual and activation on its own accumulators; it takes E_* above -----------------------------------------------------------
+TRUNK_LIB_PATH = os.path.join(_HERE, "libpvnet_trunk.so")
+TRUNK_ABI_VERSION = 1
+TRUNK_MAX_WIDTH = 512          # c1 + c2 and co, at most; each a multiple of 32
+TRUNK_CO_GROUP = 128           # output channels of a workgroup
+TRUNK_T_F32, TRUNK_T_F16, TRUNK_T_BF16 = 0, 1, 2
+TRUNK_ACT_NONE, TRUNK_ACT_RELU, TRUNK_ACT_LEAKY = 0, 1, 2
+TRUNK_GEOMETRIES = ((1, 1), (2, 1), (1, 2), (1, 4))   # (stride, dilation)
+TRUNK_PROTOTYPES = {
+    "pvnet_trunk_abi_version": (_int, []),
+    # src1 + type + strides, src2 + type + strides, res + type + strides, w, bias, b, h, w_, c1, c2, co, stride, dilation, act,
+    # out + type, stream
+    "pvnet_conv3x3_fused": (_int, [_ptr, _int, _i64p] * 3 + [_ptr, _ptr] + [_int] * 9 + [_ptr, _int, _ptr]),
+}
+
 
 class SideLibrary(NamedTuple):
     path: str
@@ -337,6 +353,7 @@ SIDE_LIBRARIES = {
     "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
     "depth": SideLibrary(DEPTH_LIB_PATH, DEPTH_ABI_VERSION, DEPTH_PROTOTYPES),
     "shade": SideLibrary(SHADE_LIB_PATH, SHADE_ABI_VERSION, SHADE_PROTOTYPES),
+    "trunk": SideLibrary(TRUNK_LIB_PATH, TRUNK_ABI_VERSION, TRUNK_PROTOTYPES),
     "stem": SideLibrary(STEM_LIB_PATH, STEM_ABI_VERSION, STEM_PROTOTYPES),
     "decoder": SideLibrary(DECODER_LIB_PATH, DECODER_ABI_VERSION, DECODER_PROTOTYPES),
     "tail": SideLibrary(TAIL_LIB_PATH, TAIL_ABI_VERSION, TAIL_PROTOTYPES),
@@ -410,6 +427,7 @@ load_stem_library = functools.partial(_load_side, "stem")
 load_decoder_library = functools.partial(_load_side, "decoder")
 load_tail_library = functools.partial(_load_side, "tail")
 load_texture_library = functools.partial(_load_side, "texture")
+load_trunk_library = functools.partial(_load_side, "trunk")
 
 
 def reload_tuning():

@@ -47,6 +47,7 @@ SIDE_LIBRARIES = {
     "raster": (["raster.hip"], "pvnet_raster.h", [_MESH_CORE]),     # poses and meshes -> silhouettes and label images
     "depth": (["depth.hip"], "pvnet_depth.h", [_ZBUFFER_CORE]),     # ... -> depth, occlusion-correct labels, visible pixel counts
     "shade": (["shade.hip"], "pvnet_shade.h", [_ZBUFFER_CORE, _PIXEL_COLOR]),       # ... -> shaded vertex-colour images over a background
+    "trunk": (["trunk.hip"], "pvnet_trunk.h", []),               # a 3x3 conv of the residual trunk: BatchNorm, residual, activation fused
     "stem": (["stem.hip"], "pvnet_stem.h", []),                  # the network's stem in one launch: 7x7/2 conv, ReLU, 3x3/2 max-pool
     "decoder": (["decoder.hip"], "pvnet_decoder.h", []),         # a decoder stage in one launch: upsample, concat, 3x3 conv, LeakyReLU
     "tail": (["tail.hip"], "pvnet_tail.h", []),                  # the network's tail in one launch: upsample, concat, 3x3 and 1x1 conv

@@ -1,0 +1,281 @@
+"""The residual trunk's 3 x 3 convolutions on the device, one launch each (include/pvnet_trunk.h, libpvnet_trunk.so): the convolution
+over one or two concatenated inputs with the eval() BatchNorm folded in, and the residual addition and the activation applied to its
+own accumulators -- ``conv1`` + ``bn1`` + ``relu`` and ``conv2`` + ``bn2`` + add + ``relu`` of the reference's ``BasicBlock.forward``
+(lib/networks/resnet.py:54-70), and ``fc`` and ``cat`` + ``conv8s`` of its ``Resnet18_8s`` (lib/networks/model_repository.py:17-33, 67).
+Inference only: no autograd, ``eval()`` BatchNorm; training keeps the PyTorch trunk.
+
+    params = ConvParams.from_modules(conv, bn, act)           # folds the BatchNorm in float64 and packs the weights, once
+    y = fused_conv3x3(x, params, residual=r)                  # [b,co,ho,wo]; src2= concatenates a second input behind the first
+    y = FusedBasicBlock(block)(x)                             # two launches; a 1 x 1 downsample is one F.conv2d with its BatchNorm folded
+    seg_pred, ver_pred = FusedTrunkNet(net, layers=LAYERS)(image)   # fused stem, the named pieces fused, fused stages and tail
+
+There is one tier: operands rounded to bfloat16, float32 accumulation on the matrix pipe.  PyTorch is plumbing only.  There is NO CPU
+fallback: without the library, or with CPU tensors, these raise ``RuntimeError``.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from ._abi import (TRUNK_ACT_LEAKY, TRUNK_ACT_NONE, TRUNK_ACT_RELU, TRUNK_GEOMETRIES, TRUNK_MAX_WIDTH, TRUNK_T_BF16, TRUNK_T_F16,
+                   TRUNK_T_F32, _check, load_trunk_library)
+from ._marshal import ptr as _ptr, stream as _stream, strides as _strides
+from .decoder import DEFAULT_STAGES
+from .stem import DEFAULT_STEM, FusedStemNet, fused_stem
+from .tail import SLOPE
+
+_TYPE_CODES = {torch.float32: TRUNK_T_F32, torch.float16: TRUNK_T_F16, torch.bfloat16: TRUNK_T_BF16}
+ACTS = {"none": TRUNK_ACT_NONE, "relu": TRUNK_ACT_RELU, "leaky": TRUNK_ACT_LEAKY}
+LAYERS = ("layer1", "layer2", "layer3", "layer4", "fc", "conv8s")   # the reference's attribute names, in the order the network runs them
+# the pieces FusedTrunkNet fuses unless told otherwise: those that tools/trunk_probe.py measured faster than the eager piece by more than
+# the spread of the eager piece's rounds (profiles/trunk_probe.txt); every other piece stays reachable by naming it
+DEFAULT_LAYERS = ("layer3", "fc", "conv8s")
+
+
+def out_sizes(h, w, stride):
+    """(ho, wo) of an h x w input: the header's integer divisions"""
+    return (h - 1) // stride + 1, (w - 1) // stride + 1
+
+
+def pack_weights(w):
+    """``w [co,cin,3,3]`` float32 -> the bfloat16 image the library takes, ``[cin/32, 9, 2, co/32, 64, 8]``: element
+    (chunk, tap, half, m, lane, j) is ``bf16(w[32 m + (lane & 31)][32 chunk + 16 half + 8 (lane >> 5) + j][tap / 3][tap % 3])``, the
+    rounding torch's round-to-nearest-even"""
+    co, cin = int(w.shape[0]), int(w.shape[1])
+    v = w.to(torch.bfloat16).reshape(co // 32, 32, cin // 32, 2, 2, 8, 9)   # m, r, chunk, half, hh, j, tap
+    return v.permute(2, 6, 3, 0, 4, 1, 5).contiguous().reshape(cin // 32, 9, 2, co // 32, 64, 8)
+
+
+def _fold(conv, bn):
+    """the eval() BatchNorm folded into a bias-free convolution in float64: ``s = gamma / sqrt(var + eps)``, ``w = W * s``, ``bias =
+    beta - mean * s``, each rounded once to float32"""
+    with torch.no_grad():
+        var, mean = bn.running_var.double(), bn.running_mean.double()
+        gamma = bn.weight.double() if bn.weight is not None else torch.ones_like(var)
+        beta = bn.bias.double() if bn.bias is not None else torch.zeros_like(var)
+        s = gamma / torch.sqrt(var + bn.eps)
+        return (conv.weight.double() * s[:, None, None, None]).float().cpu(), (beta - mean * s).float().cpu()
+
+
+def _check_bn(who, conv, bn):
+    if not (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)):
+        raise ValueError(f"{who}: expected Conv2d, BatchNorm2d")
+    if bn.training or bn.running_mean is None or bn.running_var is None:
+        raise ValueError(f"{who}: the BatchNorm must be in eval() mode with running statistics (inference only)")
+    if conv.bias is not None:
+        raise ValueError(f"{who}: the reference's convolutions have no bias")
+    if bn.num_features != conv.out_channels:
+        raise ValueError(f"{who}: the BatchNorm's width is not the convolution's")
+
+
+class ConvParams:
+    """A convolution's weights as the library takes them: ``w [co,cin,3,3]`` and ``bias [co]`` (the 3 x 3 convolution with the
+    BatchNorm folded in), float32 and contiguous, ``packed``, the same weights rounded to bfloat16 in the kernel's fragment order, and
+    its ``stride``, ``dilation`` (one of (1,1), (2,1), (1,2), (1,4); the padding is the dilation) and ``act`` ("none", "relu" or
+    "leaky").  ``on(device)`` gives (and keeps) the device's copies of ``bias`` and ``packed``."""
+
+    def __init__(self, w, bias, stride=1, dilation=1, act="none"):
+        w, bias = (torch.as_tensor(t).detach().to(torch.float32).contiguous() for t in (w, bias))
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or tuple(bias.shape) != (int(w.shape[0]),):
+            raise ValueError(f"ConvParams: w must be [co,cin,3,3] and bias [co] (got {tuple(w.shape)}, {tuple(bias.shape)})")
+        co, cin = int(w.shape[0]), int(w.shape[1])
+        if co % 32 or cin % 32 or not 0 < co <= TRUNK_MAX_WIDTH or not 0 < cin <= TRUNK_MAX_WIDTH:
+            raise ValueError(f"ConvParams: widths must be multiples of 32 up to {TRUNK_MAX_WIDTH} (got {cin} -> {co}): the ResNet-18 "
+                             "trunk's shapes only")
+        if (int(stride), int(dilation)) not in TRUNK_GEOMETRIES:
+            raise ValueError(f"ConvParams: (stride, dilation) must be one of {TRUNK_GEOMETRIES} (got {(stride, dilation)})")
+        if act not in ACTS:
+            raise ValueError(f"ConvParams: act must be one of {tuple(ACTS)} (got {act!r})")
+        self.w, self.bias = w, bias
+        self.cin, self.co, self.stride, self.dilation, self.act = cin, co, int(stride), int(dilation), act
+        self.packed = pack_weights(w)
+        self._on = {}
+
+    def on(self, device):
+        device = torch.device(device)
+        if device not in self._on:
+            self._on[device] = tuple(t.to(device) for t in (self.bias, self.packed))
+        return self._on[device]
+
+    @classmethod
+    def from_modules(cls, conv, bn, act=None):
+        """Folds the ``eval()`` BatchNorm into the convolution in float64, exactly as ``StageParams.from_modules`` does.  Refuses what
+        the fused convolution does not compute: a BatchNorm in training mode or without running statistics, a convolution with a bias,
+        a kernel other than 3 x 3, a padding that is not the dilation, groups, an activation (``act``: None, a module or one of
+        "none", "relu", "leaky") other than ReLU and LeakyReLU(0.1), widths, strides and dilations outside the library's."""
+        _check_bn("ConvParams", conv, bn)
+        if isinstance(act, nn.ReLU):
+            act = "relu"
+        elif isinstance(act, nn.LeakyReLU):
+            if float(act.negative_slope) != SLOPE:
+                raise ValueError(f"ConvParams: the LeakyReLU slope must be {SLOPE} (got {act})")
+            act = "leaky"
+        elif act is None:
+            act = "none"
+        elif act not in ACTS:
+            raise ValueError(f"ConvParams: the activation must be ReLU, LeakyReLU({SLOPE}) or none (got {act})")
+        if tuple(conv.kernel_size) != (3, 3) or conv.groups != 1 or conv.padding_mode != "zeros":
+            raise ValueError("ConvParams: expected Conv2d(cin, cout, 3, stride, d, d, groups=1, bias=False) with zero padding")
+        if conv.stride[0] != conv.stride[1] or conv.dilation[0] != conv.dilation[1] or tuple(conv.padding) != tuple(conv.dilation):
+            raise ValueError(f"ConvParams: the padding must be the dilation, both square (got stride {conv.stride}, padding "
+                             f"{conv.padding}, dilation {conv.dilation})")
+        return cls(*_fold(conv, bn), stride=conv.stride[0], dilation=conv.dilation[0], act=act)
+
+
+def fused_conv3x3(src1, params, *, src2=None, residual=None, out=None, out_dtype=None):
+    """A 3 x 3 convolution of the trunk for a batch, on the current stream, without synchronising: one launch, no workspace.
+
+    :param src1:      [b,c1,h,w] float32 / float16 / bfloat16 CUDA tensor, any strides
+    :param params:    ``ConvParams``; its stride, dilation and activation are the launch's
+    :param src2:      None or [b,c2,h,w] of the same three types (its own), any strides: the convolution reads ``cat([src1, src2], 1)``;
+                      c1 + c2 is the parameters' ``cin``, each a multiple of 32
+    :param residual:  None or [b,co,ho,wo] of the same three types, any strides: added in float32 before the activation
+    :param out:       None or the tensor to write into and return: contiguous ``[b,co,ho,wo]``
+    :param out_dtype: the type of a new ``out``: float32 / float16 / bfloat16; default ``src1``'s
+    """
+    if not isinstance(params, ConvParams):
+        raise RuntimeError("params must be a ConvParams")
+    for name, t in (("src1", src1), ("src2", src2), ("residual", residual)):
+        if t is None and name != "src1":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.dtype in _TYPE_CODES):
+            raise RuntimeError(f"{name} must be a 4-D float32, float16 or bfloat16 CUDA tensor")
+    dev = src1.device
+    b, c1, h, w = (int(v) for v in src1.shape)
+    c2 = 0 if src2 is None else int(src2.shape[1])
+    if b < 1 or h < 1 or w < 1:
+        raise RuntimeError("src1 must not be empty")
+    if c1 % 32 or c2 % 32 or c1 < 1 or (src2 is not None and c2 < 1) or c1 + c2 != params.cin:
+        raise RuntimeError(f"src1 and src2 must have multiples of 32 channels that add up to {params.cin} (got {c1} + {c2})")
+    if src2 is not None and (src2.device != dev or tuple(src2.shape) != (b, c2, h, w)):
+        raise RuntimeError(f"src2 must be {(b, c2, h, w)} on {dev} (got {tuple(src2.shape)} on {src2.device})")
+    ho, wo = out_sizes(h, w, params.stride)
+    shape = (b, params.co, ho, wo)
+    if residual is not None and (residual.device != dev or tuple(residual.shape) != shape):
+        raise RuntimeError(f"residual must be {shape} on {dev} (got {tuple(residual.shape)} on {residual.device})")
+    if out is None:
+        dtype = out_dtype if out_dtype is not None else src1.dtype
+        if dtype not in _TYPE_CODES:
+            raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    else:
+        want = out_dtype if out_dtype is not None else out.dtype if isinstance(out, torch.Tensor) else None
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == want and out.dtype in _TYPE_CODES and
+                tuple(out.shape) == shape and out.is_contiguous()):
+            raise RuntimeError(f"out must be a contiguous {want} CUDA tensor of shape {shape} on {dev}")
+    bias, wpk = params.on(dev)
+    lib = load_trunk_library()
+
+    def triple(t):
+        return (None, 0, None) if t is None else (_ptr(t), _TYPE_CODES[t.dtype], _strides(t, 4))
+
+    with torch.cuda.device(dev):
+        _check(lib.pvnet_conv3x3_fused(*triple(src1), *triple(src2), *triple(residual), _ptr(wpk), _ptr(bias), b, h, w, c1, c2,
+                                       params.co, params.stride, params.dilation, ACTS[params.act], _ptr(out), _TYPE_CODES[out.dtype],
+                                       _stream(dev)), "pvnet_conv3x3_fused")
+    return out
+
+
+def _block_modules(block):
+    """(conv1, bn1, conv2, bn2, downsample) of the reference's ``BasicBlock`` or of the stand-in's ``B`` (tools/e2e_amd.py)"""
+    for names in (("conv1", "bn1", "conv2", "bn2", "downsample"), ("c1", "b1", "c2", "b2", "down")):
+        if all(hasattr(block, n) for n in names) and not hasattr(block, "conv3"):   # (conv3: the Bottleneck, which is not supported)
+            return tuple(getattr(block, n) for n in names)
+    raise ValueError("FusedBasicBlock: neither the reference's BasicBlock (conv1, bn1, conv2, bn2, downsample) nor the stand-in's "
+                     "(c1, b1, c2, b2, down)")
+
+
+class FusedBasicBlock(nn.Module):
+    """A ``BasicBlock`` for inference in two launches: conv1 + bn1 + ReLU, then conv2 + bn2 + residual + ReLU.  The residual is the
+    input, or, for a block with a 1 x 1 ``downsample`` (Conv2d, BatchNorm2d), one ``F.conv2d`` under PyTorch with the downsample's
+    BatchNorm folded into its weight and bias (in float64, as ``ConvParams`` folds) -- one call where eager makes two."""
+
+    def __init__(self, block):
+        super().__init__()
+        conv1, bn1, conv2, bn2, down = _block_modules(block)
+        self.conv1 = ConvParams.from_modules(conv1, bn1, "relu")
+        self.conv2 = ConvParams.from_modules(conv2, bn2, "relu")
+        if (self.conv2.stride, self.conv2.cin) != (1, self.conv1.co):
+            raise ValueError("FusedBasicBlock: conv2 must have stride 1 and conv1's width")
+        self.down = None
+        if down is not None:
+            if not (isinstance(down, nn.Sequential) and len(down) == 2):
+                raise ValueError("FusedBasicBlock: the downsample must be a Sequential of Conv2d, BatchNorm2d")
+            _check_bn("FusedBasicBlock: downsample", down[0], down[1])
+            plain = (tuple(down[0].kernel_size), tuple(down[0].padding), tuple(down[0].dilation), down[0].groups)
+            if plain != ((1, 1), (0, 0), (1, 1), 1) or tuple(down[0].stride) != (self.conv1.stride,) * 2:
+                raise ValueError("FusedBasicBlock: the downsample must be Conv2d(cin, cout, 1, stride) with conv1's stride")
+            self.down = _fold(down[0], down[1])
+        elif self.conv1.stride != 1 or self.conv1.cin != self.conv2.co:
+            raise ValueError("FusedBasicBlock: a block that changes its shape needs a downsample")
+        self._down_on = {}
+
+    def residual(self, x):
+        """what conv2's launch adds: ``x``, or the folded downsample of it (in ``x``'s type)"""
+        if self.down is None:
+            return x
+        key = (x.device, x.dtype)
+        if key not in self._down_on:
+            self._down_on[key] = tuple(t.to(device=x.device, dtype=x.dtype) for t in self.down)
+        w, bias = self._down_on[key]
+        return F.conv2d(x, w, bias, stride=self.conv1.stride)
+
+    @torch.no_grad()
+    def forward(self, x):
+        y = fused_conv3x3(x, self.conv1)
+        return fused_conv3x3(y, self.conv2, residual=self.residual(x))
+
+
+def _seq_params(seq, who):
+    if not isinstance(seq, nn.Sequential) or len(seq) != 3:
+        raise ValueError(f"FusedTrunkNet: the network has no `{who}` Sequential of conv, bn, act")
+    return ConvParams.from_modules(seq[0], seq[1], seq[2])
+
+
+class FusedTrunkNet(FusedStemNet):
+    """``FusedStemNet`` with the pieces of the trunk named in ``layers`` -- drawn from ``LAYERS`` -- run through ``fused_conv3x3``:
+    ``layer1 .. layer4`` (the stand-in's ``l1 .. l4``) as ``FusedBasicBlock``s, ``fc`` as one launch, ``conv8s`` as one launch that
+    reads ``xfc`` and ``x8s`` as its two inputs, so its ``torch.cat`` is not made.  A piece not named runs its own modules;
+    ``layers=()`` is ``FusedStemNet``, bit for bit.  Returns the reference's ``(seg_pred, ver_pred)``, as views of one tensor.
+
+    ``precision`` is ``FusedStemNet``'s: ``None`` follows autocast -- the named pieces are fused where the features the stem handed
+    over are float16 or bfloat16, as they are under ``torch.autocast``; with float32 features they run the wrapped modules, because
+    the library has one tier --, ``"bf16"`` forces the fused pieces, ``"f32"`` the modules."""
+
+    def __init__(self, net, layers=DEFAULT_LAYERS, stem=DEFAULT_STEM, stages=DEFAULT_STAGES, precision=None):
+        super().__init__(net, stem=stem, stages=stages, precision=precision)
+        layers = tuple(layers)
+        if not set(layers) <= set(LAYERS) or len(set(layers)) != len(layers):
+            raise ValueError(f"layers must be drawn from {LAYERS} (got {layers})")
+        self.layers = layers
+        self.blocks = nn.ModuleDict({name: nn.ModuleList(FusedBasicBlock(blk) for blk in seq)
+                                     for name, seq in zip(LAYERS[:4], self._layers) if name in layers})
+        self.fc_params = _seq_params(self._fc, "fc") if "fc" in layers else None
+        self.conv8s_params = _seq_params(net.conv8s, "conv8s") if "conv8s" in layers else None
+        if layers:   # with none named, FusedStemNet's own trunk stays: the same calls, so the same bits
+            self._trunk = self._trunk_fused
+
+    def _layer(self, k, x, fuse):
+        name = LAYERS[k]
+        if not (fuse and name in self.layers):
+            return self._layers[k](x)
+        for blk in self.blocks[name]:
+            x = blk(x)
+        return x
+
+    def _trunk_fused(self, x):
+        dtype = self._stem_dtype(x)
+        if dtype is None:
+            x2s = self._stem_modules(x)
+            p = self._pool(x2s)
+        else:
+            x2s, p = fused_stem(x, self.stem_params, out_dtype=dtype)
+        fuse = self.precision == "bf16" or (self.precision is None and p.dtype != torch.float32)
+        x4s = self._layer(0, p, fuse)
+        x8s = self._layer(1, x4s, fuse)
+        x32s = self._layer(3, self._layer(2, x8s, fuse), fuse)
+        xfc = fused_conv3x3(x32s, self.fc_params) if fuse and "fc" in self.layers else self._fc(x32s)
+        if fuse and "conv8s" in self.layers:
+            return fused_conv3x3(xfc, self.conv8s_params, src2=x8s), x4s, x2s
+        return self.net.conv8s(torch.cat([xfc, x8s], 1)), x4s, x2s
