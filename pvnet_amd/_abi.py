@@ -326,6 +326,8 @@ TRUNK_ABI_VERSION = 1
 TRUNK_MAX_WIDTH = 512          # c1 + c2 and co, at most; each a multiple of 32
 TRUNK_CO_GROUP = 128           # output channels of a workgroup
 TRUNK_T_F32, TRUNK_T_F16, TRUNK_T_BF16 = 0, 1, 2
+assert ((TAIL_T_F32, TAIL_T_F16, TAIL_T_BF16) == (DECODER_T_F32, DECODER_T_F16, DECODER_T_BF16) == (STEM_T_F32, STEM_T_F16, STEM_T_BF16)
+        == (TRUNK_T_F32, TRUNK_T_F16, TRUNK_T_BF16)), "the four network libraries share one map of type codes (pvnet_amd/_net.py)"
 TRUNK_ACT_NONE, TRUNK_ACT_RELU, TRUNK_ACT_LEAKY = 0, 1, 2
 TRUNK_GEOMETRIES = ((1, 1), (2, 1), (1, 2), (1, 4))   # (stride, dilation)
 TRUNK_PROTOTYPES = {

@@ -19,9 +19,7 @@
 //               blocks and a B fragment all row blocks: 1.5 (CO = 32) or 1 (CO = 64) fragment reads per MFMA.
 // then, per tile, 3. store: pixels are on the lanes, so a store instruction writes 32 consecutive pixels of a channel plane; any
 // alignment of `out`.
-#include "vote_common.h"
-
-#include <type_traits>
+#include "net_common.h"
 
 #include "pvnet_decoder.h"
 
@@ -36,9 +34,11 @@ using pvd::f32x16;
 using pvd::VT_BF16;
 using pvd::VT_F16;
 using pvd::VT_F32;
+using pvnc::CPI;
+using pvnc::REC;
+using pvnc::rec_slot;
 
-static_assert(PVNET_DECODER_T_F32 == VT_F32 && PVNET_DECODER_T_F16 == VT_F16 && PVNET_DECODER_T_BF16 == VT_BF16,
-              "the type codes of pvnet_decoder.h are ld_elem_rt's");
+PVNET_NET_TYPE_CODES(DECODER);
 
 constexpr int CS = PVNET_DECODER_SKIP;    // channels of skip
 constexpr int CHUNK = 32;                 // channels of In staged at a time: two k-steps per tap
@@ -46,8 +46,6 @@ constexpr int TILE_W = 64, ROWS = 4;      // output pixels of a tile: a wave per
 constexpr int NQ = TILE_W / 32;
 constexpr int THREADS = 64 * ROWS;
 constexpr int HALO_W = TILE_W + 2, HALO_H = ROWS + 2, HALO_PIX = HALO_W * HALO_H;
-constexpr int REC = 80;                   // bytes of a pixel's record: 32 bfloat16 channels, padded from 64 to 80
-constexpr int CPI = 8;                    // channels of a staging item: 32 loads in flight per lane (upsampled), one 16-byte LDS store
 constexpr int GROUPS = CHUNK / CPI;       // staging items per pixel and chunk
 constexpr int KSTEPS = 18;                // per chunk: 9 taps x 2 halves of 16 channels
 constexpr int MAX_GRID_32 = 1024, MAX_GRID_64 = 768;   // workgroups of a launch: four (CO = 32) or three (CO = 64) per compute unit
@@ -65,21 +63,6 @@ struct StageArgs {
     float ry, rx;   // (float)(hin - 1) / (float)(h - 1), (float)(win - 1) / (float)(w_ - 1); 0 for h == 1 / w_ == 1
 };
 
-// a lane's sixteen accumulator registers -> its pixel of the 32 planes they are rows of (register g of lane half hh is row
-// (g & 3) + 8 (g >> 2) + 4 hh); `at` is the pixel's element in the block's plane 0.  One running pointer, as in tail.hip.
-template <int VT>
-__device__ __forceinline__ void store_rows(void* out, size_t at, size_t plane, const f32x16& v, int hh) {
-    typedef typename std::conditional<VT == VT_F32, float, typename std::conditional<VT == VT_F16, _Float16, __bf16>::type>::type T;
-    T* o = reinterpret_cast<T*>(out) + at + (size_t)(4 * hh) * plane;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        *o = (T)v[g];   // one rounding to the output type
-        o += (g & 3) == 3 ? 5 * plane : plane;
-    }
-}
-
-__device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : v * 0.1f; }
-
 // channels c0 .. c0 + 31 of In, upsampled from `lo`, of the tile at (ty0, tx0) of image bi with its halo -> LDS.  An item is (group of
 // CPI channels, pixel), pixels fastest: a wave's loads of a plane run along a row.
 template <int FT>
@@ -92,11 +75,8 @@ __device__ __forceinline__ void stage_lo(const StageArgs& P, int bi, int ty0, in
 #pragma unroll
         for (int c = 0; c < CPI; ++c) q[c] = (__bf16)0.f;
         if (Y >= 0 && Y < P.h && X >= 0 && X < P.w_) {
-            const float sy = (float)Y * P.ry, sx = (float)X * P.rx;
-            const int y0 = min((int)sy, P.hin - 1), x0 = min((int)sx, P.win - 1);   // (the minimum never binds: sy <= hin - 1)
-            const int y1 = y0 + (y0 < P.hin - 1), x1 = x0 + (x0 < P.win - 1);
-            const float ly = sy - (float)y0, lx = sx - (float)x0;
-            const float my = 1.f - ly, mx = 1.f - lx;
+            const pvnc::Taps t(Y, X, P.ry, P.rx, P.hin, P.win);
+            const int y0 = t.y0, y1 = t.y1, x0 = t.x0, x1 = t.x1;
             const int64_t base = (int64_t)bi * P.ls[0] + (int64_t)(c0 + cg * CPI) * P.ls[1];
             const int64_t o00 = base + (int64_t)y0 * P.ls[2] + (int64_t)x0 * P.ls[3], o01 = base + (int64_t)y0 * P.ls[2] + (int64_t)x1 * P.ls[3];
             const int64_t o10 = base + (int64_t)y1 * P.ls[2] + (int64_t)x0 * P.ls[3], o11 = base + (int64_t)y1 * P.ls[2] + (int64_t)x1 * P.ls[3];
@@ -105,11 +85,10 @@ __device__ __forceinline__ void stage_lo(const StageArgs& P, int bi, int ty0, in
                 const int64_t oc = (int64_t)c * P.ls[1];
                 const float v00 = pvd::ld_elem<FT>(P.lo, o00 + oc), v01 = pvd::ld_elem<FT>(P.lo, o01 + oc);
                 const float v10 = pvd::ld_elem<FT>(P.lo, o10 + oc), v11 = pvd::ld_elem<FT>(P.lo, o11 + oc);
-                const float top = mx * v00 + lx * v01, bot = mx * v10 + lx * v11;
-                q[c] = (__bf16)(my * top + ly * bot);
+                q[c] = (__bf16)t.blend(v00, v01, v10, v11);
             }
         }
-        *reinterpret_cast<bf16x8*>(tile + p * REC + cg * (2 * CPI)) = q;
+        *reinterpret_cast<bf16x8*>(tile + rec_slot(p, cg)) = q;
     }
 }
 
@@ -128,7 +107,7 @@ __device__ __forceinline__ void stage_skip(const StageArgs& P, int bi, int ty0, 
 #pragma unroll
             for (int c = 0; c < CPI; ++c) q[c] = (__bf16)pvd::ld_elem<FT>(P.skip, o + (int64_t)c * P.ss[1]);
         }
-        *reinterpret_cast<bf16x8*>(tile + p * REC + cg * (2 * CPI)) = q;
+        *reinterpret_cast<bf16x8*>(tile + rec_slot(p, cg)) = q;
     }
 }
 
@@ -147,19 +126,11 @@ __device__ __forceinline__ void stage_chunk(const StageArgs& P, int bi, int ty0,
     }
 }
 
-__device__ __forceinline__ void tile_of(const StageArgs& P, int tile, int& bi, int& ty0, int& tx0) {
-    const int tx = tile % P.tiles_x, rest = tile / P.tiles_x;
-    const int ty = rest % P.tiles_y;
-    bi = rest / P.tiles_y;
-    ty0 = ty * ROWS;
-    tx0 = tx * TILE_W;
-}
-
 // the A fragment of (chunk, k-step ks = 2 tap + half, row block m): lane (r, hh) holds output channel 32 m + r, k = 8 hh + j, which is
 // channel 32 chunk + 16 half + k of In at that tap
 template <int CIN, int CO, bool PACKED>
 __device__ __forceinline__ bf16x8 weights_fragment(const float* w, int chunk, int ks, int m, int lane) {
-    if (PACKED) return reinterpret_cast<const bf16x8*>(w)[((chunk * KSTEPS + ks) * (CO / 32) + m) * 64 + lane];
+    if (PACKED) return reinterpret_cast<const bf16x8*>(w)[pvnc::frag_at(chunk * KSTEPS + ks, CO / 32, m, lane)];
     const float* wr = w + ((size_t)(32 * m + (lane & 31)) * CIN + CHUNK * chunk + 16 * (ks & 1) + 8 * (lane >> 5)) * 9 + (ks >> 1);
     bf16x8 a;
 #pragma unroll
@@ -197,7 +168,7 @@ __global__ __launch_bounds__(THREADS) void decoder_stage_kernel(StageArgs P) {
 
     for (int t_ = blockIdx.x; t_ < P.ntiles; t_ += gridDim.x) {
         int bi, ty0, tx0;
-        tile_of(P, t_, bi, ty0, tx0);
+        pvnc::tile_of<TILE_W, ROWS>(P, t_, bi, ty0, tx0);
         const int Y = ty0 + wave;
         f32x16 acc[NQ][MB];
 #pragma unroll
@@ -233,18 +204,16 @@ __global__ __launch_bounds__(THREADS) void decoder_stage_kernel(StageArgs P) {
                 for (int m = 0; m < MB; ++m) {
                     f32x16 v = acc[q][m];
 #pragma unroll
-                    for (int g = 0; g < 16; ++g) v[g] = leaky(v[g]);
+                    for (int g = 0; g < 16; ++g) v[g] = pvnc::leaky(v[g]);
                     const size_t o = ((size_t)bi * CO + 32 * m) * plane + (size_t)Y * P.w_ + X;
-                    if (P.out_type == VT_BF16) store_rows<VT_BF16>(P.out, o, plane, v, hh);
-                    else if (P.out_type == VT_F16) store_rows<VT_F16>(P.out, o, plane, v, hh);
-                    else store_rows<VT_F32>(P.out, o, plane, v, hh);
+                    if (P.out_type == VT_BF16) pvnc::store_rows<VT_BF16>(P.out, o, plane, v, hh);
+                    else if (P.out_type == VT_F16) pvnc::store_rows<VT_F16>(P.out, o, plane, v, hh);
+                    else pvnc::store_rows<VT_F32>(P.out, o, plane, v, hh);
                 }
             }
         }
     }
 }
-
-inline bool type_ok(int t) { return t == PVNET_DECODER_T_F32 || t == PVNET_DECODER_T_F16 || t == PVNET_DECODER_T_BF16; }
 
 template <int CL, int CO>
 void launch(const StageArgs& P, bool packed, dim3 grid, hipStream_t s) {
@@ -266,19 +235,14 @@ int pvnet_decoder_stage(const void* lo, int lo_type, const int64_t lo_strides[4]
                         int cs, int co, uint32_t flags, void* out, int out_type, void* stream) {
     if (!lo || !lo_strides || !skip || !skip_strides || !w || !bias || !out) return PVNET_E_BADARG;
     if (b < 1 || hin < 1 || win < 1 || h < 1 || w_ < 1 || cl < 1 || cs < 1 || co < 1) return PVNET_E_BADARG;
-    if (!type_ok(lo_type) || !type_ok(skip_type) || !type_ok(out_type)) return PVNET_E_BADARG;
+    if (!pvnc::type_ok(lo_type) || !pvnc::type_ok(skip_type) || !pvnc::type_ok(out_type)) return PVNET_E_BADARG;
     if ((flags & ~PVNET_DECODER_F_PACKED) != 0) return PVNET_E_BADARG;
     if ((flags & PVNET_DECODER_F_PACKED) && (reinterpret_cast<uintptr_t>(w) & 15) != 0) return PVNET_E_BADARG;   // 16-byte fragment loads
     if ((long long)h != 2ll * hin || (long long)w_ != 2ll * win) return PVNET_E_BADARG;
     const bool conv2s = cl == 64 && cs == CS && co == 32, conv4s = cl == 128 && cs == CS && co == 64;
     if (!conv2s && !conv4s) return PVNET_E_UNSUPPORTED;
-    if (b > 65535 || h > 32768 || w_ > 32768) return PVNET_E_UNSUPPORTED;
     StageArgs P;
-    P.tiles_x = (w_ + TILE_W - 1) / TILE_W;
-    P.tiles_y = (h + ROWS - 1) / ROWS;
-    const long long ntiles = (long long)b * P.tiles_x * P.tiles_y;
-    if (ntiles > 0x7FFFFFFFll) return PVNET_E_UNSUPPORTED;
-    P.ntiles = (int)ntiles;
+    if (!pvnc::sizes_ok(b, h, w_) || pvnc::plan_tiles<TILE_W, ROWS>(P, b, h, w_) < 0) return PVNET_E_UNSUPPORTED;
     P.lo = lo;
     P.skip = skip;
     P.w = w;
@@ -295,16 +259,14 @@ int pvnet_decoder_stage(const void* lo, int lo_type, const int64_t lo_strides[4]
     P.win = win;
     P.h = h;
     P.w_ = w_;
-    P.ry = h > 1 ? (float)(hin - 1) / (float)(h - 1) : 0.f;
-    P.rx = w_ > 1 ? (float)(win - 1) / (float)(w_ - 1) : 0.f;
-    const int max_grid = conv2s ? MAX_GRID_32 : MAX_GRID_64;
-    const dim3 grid(P.ntiles < max_grid ? P.ntiles : max_grid);
+    P.ry = pvnc::up_ratio(hin, h);
+    P.rx = pvnc::up_ratio(win, w_);
+    const dim3 grid = pvnc::clamped_grid(P.ntiles, conv2s ? MAX_GRID_32 : MAX_GRID_64);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool packed = (flags & PVNET_DECODER_F_PACKED) != 0;
     if (conv2s) launch<64, 32>(P, packed, grid, s);
     else launch<128, 64>(P, packed, grid, s);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return pvnc::launch_status();
 }
 
 }  // extern "C"

@@ -19,9 +19,7 @@
 //               accumulators, a lane a pixel, took 2-byte stores: 512 store instructions per tile against 32);
 //   4. pool:    the 3 x 3 maxima of pbuf's 32 channels -> pooled, as unsigned maxima of the values' bits (no value is below +0, so
 //               the +0 of a position outside Ho x Wo never counts, and a NaN's bits are above every number's).
-#include "vote_common.h"
-
-#include <type_traits>
+#include "net_common.h"
 
 #include "pvnet_stem.h"
 
@@ -34,8 +32,7 @@ using pvd::VT_BF16;
 using pvd::VT_F16;
 using pvd::VT_F32;
 
-static_assert(PVNET_STEM_T_F32 == VT_F32 && PVNET_STEM_T_F16 == VT_F16 && PVNET_STEM_T_BF16 == VT_BF16,
-              "the type codes of pvnet_stem.h are ld_elem_rt's");
+PVNET_NET_TYPE_CODES(STEM);
 
 constexpr int CI = PVNET_STEM_CIN, CO = PVNET_STEM_COUT;
 constexpr int TILE_W = 64, ROWS = 4;                  // x2s pixels of a tile; both even: a pool window never reaches below or right of it
@@ -60,11 +57,6 @@ struct StemArgs {
     int image_type;
     int h, w_, ho, wo, hp, wp;
     int tiles_x, tiles_y, ntiles;
-};
-
-template <int VT>
-struct elem {
-    typedef typename std::conditional<VT == VT_F32, float, typename std::conditional<VT == VT_F16, _Float16, __bf16>::type>::type type;
 };
 
 // element (k group gi, tap 0) of a patch whose top-left element is the window's
@@ -127,18 +119,10 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_s_barrier();
 }
 
-__device__ __forceinline__ void tile_of(const StemArgs& P, int tile, int& bi, int& ty0, int& tx0) {
-    const int tx = tile % P.tiles_x, rest = tile / P.tiles_x;
-    const int ty = rest % P.tiles_y;
-    bi = rest / P.tiles_y;
-    ty0 = ty * ROWS;
-    tx0 = tx * TILE_W;
-}
-
 template <int OT>
 __global__ __launch_bounds__(THREADS) void stem_kernel(StemArgs P) {
     PVNET_SPARE_VGPRS(247);   // (239 in use: the compiler spends what two waves per SIMD leave it; the LDS allows two workgroups per compute unit: two waves per SIMD, 256 registers each)
-    typedef typename elem<OT>::type T;
+    typedef typename pvnc::elem<OT>::type T;
     __shared__ __attribute__((aligned(16))) __bf16 wfrag[2 * KSTEPS * 64 * 8];   // [m][k-step][lane][j]: the A fragments
     __shared__ __attribute__((aligned(16))) __bf16 patch[CI * PH * PWP];
     // the stored values' BITS, [channel of the half][local row][PB0 + local column]; +0 outside Ho x Wo.  Every value is +0 or above, or
@@ -179,18 +163,18 @@ __global__ __launch_bounds__(THREADS) void stem_kernel(StemArgs P) {
     float v0[STAGE_ITERS], v1[STAGE_ITERS];   // a tile's image values on their way into the patch
     if ((int)blockIdx.x < P.ntiles) {
         int bi, ty0, tx0;
-        tile_of(P, blockIdx.x, bi, ty0, tx0);
+        pvnc::tile_of<TILE_W, ROWS>(P, blockIdx.x, bi, ty0, tx0);
         tile_load(P, bi, ty0, tx0, v0, v1);
     }
     for (int t_ = blockIdx.x; t_ < P.ntiles; t_ += gridDim.x) {
         int bi, ty0, tx0;
-        tile_of(P, t_, bi, ty0, tx0);
+        pvnc::tile_of<TILE_W, ROWS>(P, t_, bi, ty0, tx0);
         const int cy0 = ty0 - 1, cx0 = tx0 - 1;
         patch_write(P, cy0, cx0, v0, v1, patch);
         lds_barrier();   // (the first tile: the weights and the bias too)
         if (t_ + (int)gridDim.x < P.ntiles) {   // the next tile's loads, in flight while this one is computed
             int nb, ny0, nx0;
-            tile_of(P, t_ + gridDim.x, nb, ny0, nx0);
+            pvnc::tile_of<TILE_W, ROWS>(P, t_ + gridDim.x, nb, ny0, nx0);
             tile_load(P, nb, ny0, nx0, v0, v1);
         }
 #pragma unroll 1
@@ -271,8 +255,6 @@ __global__ __launch_bounds__(THREADS) void stem_kernel(StemArgs P) {
     }
 }
 
-inline bool type_ok(int t) { return t == PVNET_STEM_T_F32 || t == PVNET_STEM_T_F16 || t == PVNET_STEM_T_BF16; }
-
 }  // namespace
 }  // namespace pvstem
 
@@ -286,8 +268,8 @@ int pvnet_stem_forward(const void* image, int image_type, const int64_t image_st
                        int w_, void* x2s, void* pooled, int out_type, void* stream) {
     if (!image || !image_strides || !w || !bias || !x2s) return PVNET_E_BADARG;
     if (b < 1 || h < 1 || w_ < 1) return PVNET_E_BADARG;
-    if (!type_ok(image_type) || !type_ok(out_type)) return PVNET_E_BADARG;
-    if (b > 65535 || h > 32768 || w_ > 32768) return PVNET_E_UNSUPPORTED;
+    if (!pvnc::type_ok(image_type) || !pvnc::type_ok(out_type)) return PVNET_E_BADARG;
+    if (!pvnc::sizes_ok(b, h, w_)) return PVNET_E_UNSUPPORTED;
     StemArgs P;
     P.h = h;
     P.w_ = w_;
@@ -295,11 +277,7 @@ int pvnet_stem_forward(const void* image, int image_type, const int64_t image_st
     P.wo = (w_ - 1) / 2 + 1;
     P.hp = (P.ho - 1) / 2 + 1;
     P.wp = (P.wo - 1) / 2 + 1;
-    P.tiles_x = (P.wo + TILE_W - 1) / TILE_W;
-    P.tiles_y = (P.ho + ROWS - 1) / ROWS;
-    const long long ntiles = (long long)b * P.tiles_x * P.tiles_y;
-    if (ntiles > 0x7FFFFFFFll) return PVNET_E_UNSUPPORTED;
-    P.ntiles = (int)ntiles;
+    if (pvnc::plan_tiles<TILE_W, ROWS>(P, b, P.ho, P.wo) < 0) return PVNET_E_UNSUPPORTED;
     P.image = image;
     P.w = w;
     P.bias = bias;
@@ -307,13 +285,12 @@ int pvnet_stem_forward(const void* image, int image_type, const int64_t image_st
     P.pooled = pooled;
     for (int i = 0; i < 4; ++i) P.is[i] = image_strides[i];
     P.image_type = image_type;
-    const dim3 grid(P.ntiles < MAX_GRID ? P.ntiles : MAX_GRID);
+    const dim3 grid = pvnc::clamped_grid(P.ntiles, MAX_GRID);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (out_type == PVNET_STEM_T_BF16) hipLaunchKernelGGL((stem_kernel<VT_BF16>), grid, dim3(THREADS), 0, s, P);
     else if (out_type == PVNET_STEM_T_F16) hipLaunchKernelGGL((stem_kernel<VT_F16>), grid, dim3(THREADS), 0, s, P);
     else hipLaunchKernelGGL((stem_kernel<VT_F32>), grid, dim3(THREADS), 0, s, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return pvnc::launch_status();
 }
 
 }  // extern "C"

@@ -21,9 +21,7 @@
 //   3. store:   pixels are on the lanes, so a store instruction writes 32 consecutive pixels of two channel planes (BF16 tier) or 64
 //               of one (F32 tier); any alignment of `out`.  (No 16-byte store path: a lane holds ONE pixel of a plane, and bringing
 //               eight to a lane would cost the lane movement the accumulator-as-operand layout avoids.)
-#include "vote_common.h"
-
-#include <type_traits>
+#include "net_common.h"
 
 #include "pvnet_tail.h"
 
@@ -38,8 +36,11 @@ using pvd::f32x16;
 using pvd::VT_BF16;
 using pvd::VT_F16;
 using pvd::VT_F32;
+using pvnc::CPI;
+using pvnc::leaky;
+using pvnc::rec_slot;
 
-static_assert(PVNET_TAIL_T_F32 == VT_F32 && PVNET_TAIL_T_F16 == VT_F16 && PVNET_TAIL_T_BF16 == VT_BF16, "the type codes of pvnet_tail.h are ld_elem_rt's");
+PVNET_NET_TYPE_CODES(TAIL);
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -50,9 +51,8 @@ constexpr int W1_ROW = CIN * 9;           // w1 elements per raw channel
 constexpr int TILE_W = 64, ROWS = 4;      // output pixels of a tile: a wave per row, two MFMA column blocks of 32
 constexpr int THREADS = 64 * ROWS;
 constexpr int HALO_W = TILE_W + 2, HALO_H = ROWS + 2, HALO_PIX = HALO_W * HALO_H;
-constexpr int REC_BF = 80;                // bytes of a pixel's record, BF16 tier: 32 + 3 channels + a zero, bfloat16, padded to 80
+constexpr int REC_BF = pvnc::REC;         // bytes of a pixel's record, BF16 tier: 32 + 3 channels + a zero, bfloat16
 constexpr int REC_F = 144;                // F32 tier: 32 + 3 channels + 1 zero, float32
-constexpr int CPI = 8;                    // channels of a staging item: 32 loads in flight per lane, one 16-byte (bfloat16) LDS store
 constexpr int FGROUPS = WIDTH / CPI, GROUPS = FGROUPS + 1;   // staging items per pixel: CPI feature channels each, then the image's three
 constexpr int MAX_GRID = 768;             // workgroups of a launch: three per compute unit
 
@@ -77,22 +77,6 @@ __device__ __forceinline__ void store_out(int vt, void* out, size_t idx, float v
     else reinterpret_cast<float*>(out)[idx] = v;
 }
 
-// a lane's sixteen accumulator registers -> its pixel of the planes they are rows of (register g of lane half hh is row
-// (g & 3) + 8 (g >> 2) + 4 hh), rows behind `rows` left out; `at` is the pixel's element in plane 0.  One running pointer: a table of
-// sixteen 64-bit plane offsets per lane is what the compiler otherwise keeps in registers across the whole kernel.
-template <int VT>
-__device__ __forceinline__ void store_rows(void* out, size_t at, size_t plane, const f32x16& v, int hh, int rows) {
-    typedef typename std::conditional<VT == VT_F32, float, typename std::conditional<VT == VT_F16, _Float16, __bf16>::type>::type T;
-    T* o = reinterpret_cast<T*>(out) + at + (size_t)(4 * hh) * plane;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        if ((g & 3) + 8 * (g >> 2) + 4 * hh < rows) *o = (T)v[g];   // one rounding to the output type
-        o += (g & 3) == 3 ? 5 * plane : plane;
-    }
-}
-
-__device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : v * 0.1f; }
-
 // In of the tile at (ty0, tx0) of image bi with its halo -> LDS.  An item is (group of CPI channels, pixel), pixels fastest: a wave's
 // loads of a plane run along a row.
 template <bool BF, int FT>
@@ -106,11 +90,8 @@ __device__ __forceinline__ void stage_tile_typed(const TailArgs& P, int bi, int 
         for (int c = 0; c < CPI; ++c) v[c] = 0.f;
         if (Y >= 0 && Y < P.h && X >= 0 && X < P.w) {
             if (cg < FGROUPS) {
-                const float sy = (float)Y * P.ry, sx = (float)X * P.rx;
-                const int y0 = min((int)sy, P.hin - 1), x0 = min((int)sx, P.win - 1);   // (the minimum never binds: sy <= hin - 1)
-                const int y1 = y0 + (y0 < P.hin - 1), x1 = x0 + (x0 < P.win - 1);
-                const float ly = sy - (float)y0, lx = sx - (float)x0;
-                const float my = 1.f - ly, mx = 1.f - lx;
+                const pvnc::Taps t(Y, X, P.ry, P.rx, P.hin, P.win);
+                const int y0 = t.y0, y1 = t.y1, x0 = t.x0, x1 = t.x1;
                 const int64_t base = (int64_t)bi * P.fs[0] + (int64_t)(cg * CPI) * P.fs[1];
                 const int64_t o00 = base + (int64_t)y0 * P.fs[2] + (int64_t)x0 * P.fs[3], o01 = base + (int64_t)y0 * P.fs[2] + (int64_t)x1 * P.fs[3];
                 const int64_t o10 = base + (int64_t)y1 * P.fs[2] + (int64_t)x0 * P.fs[3], o11 = base + (int64_t)y1 * P.fs[2] + (int64_t)x1 * P.fs[3];
@@ -119,8 +100,7 @@ __device__ __forceinline__ void stage_tile_typed(const TailArgs& P, int bi, int 
                     const int64_t oc = (int64_t)c * P.fs[1];
                     const float v00 = pvd::ld_elem<FT>(P.fm, o00 + oc), v01 = pvd::ld_elem<FT>(P.fm, o01 + oc);
                     const float v10 = pvd::ld_elem<FT>(P.fm, o10 + oc), v11 = pvd::ld_elem<FT>(P.fm, o11 + oc);
-                    const float top = mx * v00 + lx * v01, bot = mx * v10 + lx * v11;
-                    v[c] = my * top + ly * bot;
+                    v[c] = t.blend(v00, v01, v10, v11);
                 }
             } else {
                 const int64_t o = (int64_t)bi * P.is[0] + (int64_t)Y * P.is[2] + (int64_t)X * P.is[3];
@@ -132,7 +112,7 @@ __device__ __forceinline__ void stage_tile_typed(const TailArgs& P, int bi, int 
             bf16x8 q;
 #pragma unroll
             for (int c = 0; c < CPI; ++c) q[c] = (__bf16)v[c];
-            *reinterpret_cast<bf16x8*>(tile + p * REC_BF + cg * (2 * CPI)) = q;
+            *reinterpret_cast<bf16x8*>(tile + rec_slot(p, cg)) = q;
         } else {
             f32x4* dst = reinterpret_cast<f32x4*>(tile + p * REC_F + cg * (4 * CPI));
             dst[0] = f32x4{v[0], v[1], v[2], v[3]};
@@ -146,14 +126,6 @@ __device__ __forceinline__ void stage_tile(const TailArgs& P, int bi, int ty0, i
     if (P.fm_type == VT_BF16) stage_tile_typed<BF, VT_BF16>(P, bi, ty0, tx0, tile);
     else if (P.fm_type == VT_F16) stage_tile_typed<BF, VT_F16>(P, bi, ty0, tx0, tile);
     else stage_tile_typed<BF, VT_F32>(P, bi, ty0, tx0, tile);
-}
-
-__device__ __forceinline__ void tile_of(const TailArgs& P, int tile, int& bi, int& ty0, int& tx0) {
-    const int tx = tile % P.tiles_x, rest = tile / P.tiles_x;
-    const int ty = rest % P.tiles_y;
-    bi = rest / P.tiles_y;
-    ty0 = ty * ROWS;
-    tx0 = tx * TILE_W;
 }
 
 // byte offset, from the record of a block's top-left tap, of term k of the image's two k-steps: k = 3 tap + channel for k < 27, then
@@ -204,7 +176,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(80))) void 
 
     for (int t_ = blockIdx.x; t_ < P.ntiles; t_ += gridDim.x) {
         int bi, ty0, tx0;
-        tile_of(P, t_, bi, ty0, tx0);
+        pvnc::tile_of<TILE_W, ROWS>(P, t_, bi, ty0, tx0);
         stage_tile<true>(P, bi, ty0, tx0, tile);
         __syncthreads();
         const int Y = ty0 + wave;
@@ -243,7 +215,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(80))) void 
 #pragma unroll
                 for (int g = 0; g < 16; ++g) acc[g] = leaky(acc[g]);
                 if (P.raw) {
-                    if (X < P.w) store_rows<VT_F32>(P.out, (size_t)bi * WIDTH * plane + (size_t)Y * P.w + X, plane, acc, hh, WIDTH);
+                    if (X < P.w) pvnc::store_rows<VT_F32>(P.out, (size_t)bi * WIDTH * plane + (size_t)Y * P.w + X, plane, acc, hh, WIDTH);
                     continue;
                 }
                 bf16x8 B0, B1;
@@ -263,9 +235,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(80))) void 
                 y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2[1], B1, y, 0, 0, 0);
                 if (X < P.w) {
                     const size_t o = (size_t)bi * P.cout * plane + (size_t)Y * P.w + X;
-                    if (P.out_type == VT_BF16) store_rows<VT_BF16>(P.out, o, plane, y, hh, P.cout);
-                    else if (P.out_type == VT_F16) store_rows<VT_F16>(P.out, o, plane, y, hh, P.cout);
-                    else store_rows<VT_F32>(P.out, o, plane, y, hh, P.cout);
+                    if (P.out_type == VT_BF16) pvnc::store_rows<VT_BF16>(P.out, o, plane, y, hh, P.cout);
+                    else if (P.out_type == VT_F16) pvnc::store_rows<VT_F16>(P.out, o, plane, y, hh, P.cout);
+                    else pvnc::store_rows<VT_F32>(P.out, o, plane, y, hh, P.cout);
                 }
             }
         }
@@ -285,7 +257,7 @@ __global__ __launch_bounds__(THREADS) void tail_f32_kernel(TailArgs P) {
 
     for (int t_ = blockIdx.x; t_ < P.ntiles; t_ += gridDim.x) {
         int bi, ty0, tx0;
-        tile_of(P, t_, bi, ty0, tx0);
+        pvnc::tile_of<TILE_W, ROWS>(P, t_, bi, ty0, tx0);
         stage_tile<false>(P, bi, ty0, tx0, tile);
         __syncthreads();
         const int Y = ty0 + row, X = tx0 + col;
@@ -339,8 +311,6 @@ __global__ __launch_bounds__(THREADS) void tail_f32_kernel(TailArgs P) {
     }
 }
 
-inline bool type_ok(int t) { return t == PVNET_TAIL_T_F32 || t == PVNET_TAIL_T_F16 || t == PVNET_TAIL_T_BF16; }
-
 }  // namespace
 }  // namespace pvt
 
@@ -357,19 +327,14 @@ int pvnet_tail_forward(const void* fm, int fm_type, const int64_t fm_strides[4],
     if (!fm || !fm_strides || !image || !image_strides || !w1 || !b1 || !w2 || !b2 || !out) return PVNET_E_BADARG;
     if (b < 1 || hin < 1 || win < 1 || h < 1 || w < 1 || feat < 1 || raw < 1) return PVNET_E_BADARG;
     if (cout < 1 || cout > PVNET_TAIL_MAX_COUT) return PVNET_E_BADARG;
-    if (!type_ok(fm_type) || !type_ok(image_type) || !type_ok(out_type)) return PVNET_E_BADARG;
+    if (!pvnc::type_ok(fm_type) || !pvnc::type_ok(image_type) || !pvnc::type_ok(out_type)) return PVNET_E_BADARG;
     if (precision != PVNET_TAIL_BF16 && precision != PVNET_TAIL_F32) return PVNET_E_BADARG;
     if ((flags & ~PVNET_TAIL_F_RAW) != 0) return PVNET_E_BADARG;
     if ((flags & PVNET_TAIL_F_RAW) && out_type != PVNET_TAIL_T_F32) return PVNET_E_BADARG;
     if ((long long)h != 2ll * hin || (long long)w != 2ll * win) return PVNET_E_BADARG;
     if (feat != PVNET_TAIL_WIDTH || raw != PVNET_TAIL_WIDTH) return PVNET_E_UNSUPPORTED;
-    if (b > 65535 || h > 32768 || w > 32768) return PVNET_E_UNSUPPORTED;
     TailArgs P;
-    P.tiles_x = (w + TILE_W - 1) / TILE_W;
-    P.tiles_y = (h + ROWS - 1) / ROWS;
-    const long long ntiles = (long long)b * P.tiles_x * P.tiles_y;
-    if (ntiles > 0x7FFFFFFFll) return PVNET_E_UNSUPPORTED;
-    P.ntiles = (int)ntiles;
+    if (!pvnc::sizes_ok(b, h, w) || pvnc::plan_tiles<TILE_W, ROWS>(P, b, h, w) < 0) return PVNET_E_UNSUPPORTED;
     P.fm = fm;
     P.image = image;
     P.w1 = w1;
@@ -390,14 +355,13 @@ int pvnet_tail_forward(const void* fm, int fm_type, const int64_t fm_strides[4],
     P.w = w;
     P.cout = cout;
     P.raw = (flags & PVNET_TAIL_F_RAW) ? 1 : 0;
-    P.ry = h > 1 ? (float)(hin - 1) / (float)(h - 1) : 0.f;
-    P.rx = w > 1 ? (float)(win - 1) / (float)(w - 1) : 0.f;
-    const dim3 grid(P.ntiles < MAX_GRID ? P.ntiles : MAX_GRID), block(THREADS);
+    P.ry = pvnc::up_ratio(hin, h);
+    P.rx = pvnc::up_ratio(win, w);
+    const dim3 grid = pvnc::clamped_grid(P.ntiles, MAX_GRID), block(THREADS);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (precision == PVNET_TAIL_BF16) hipLaunchKernelGGL(tail_bf16_kernel, grid, block, 0, s, P);
     else hipLaunchKernelGGL(tail_f32_kernel, grid, block, 0, s, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return pvnc::launch_status();
 }
 
 }  // extern "C"

@@ -23,9 +23,7 @@
 // strides are non-negative and whose image spans less than 2^31 bytes, a 64-bit address per load for the rest (a negative stride through
 // the C ABI, an image over 2 GB).  The second is there for the header's "any element strides", computes the same bits, keeps fewer
 // loads in flight and has not been timed.
-#include "vote_common.h"
-
-#include <type_traits>
+#include "net_common.h"
 
 #include "pvnet_trunk.h"
 
@@ -40,17 +38,16 @@ using pvd::f32x16;
 using pvd::VT_BF16;
 using pvd::VT_F16;
 using pvd::VT_F32;
+using pvnc::CPI;
+using pvnc::REC;
 
-static_assert(PVNET_TRUNK_T_F32 == VT_F32 && PVNET_TRUNK_T_F16 == VT_F16 && PVNET_TRUNK_T_BF16 == VT_BF16,
-              "the type codes of pvnet_trunk.h are ld_elem_rt's");
+PVNET_NET_TYPE_CODES(TRUNK);
 
 constexpr int CHUNK = 32;                 // channels of In staged at a time: two k-steps per tap
 constexpr int TILE_W = 32, ROWS = 8;      // output pixels of a tile: one MFMA column block wide, an accumulator block per row
 constexpr int WAVES = 4, THREADS = 64 * WAVES;
 constexpr int COG = PVNET_TRUNK_CO_GROUP; // output channels of a work item: 32 per wave
 static_assert(COG == 32 * WAVES, "a wave owns one row block of 32 output channels");
-constexpr int REC = 80;                   // bytes of a pixel's record: 32 bfloat16 channels, padded from 64 to 80
-constexpr int CPI = 8;                    // channels of a staging item: one 16-byte LDS store
 constexpr int GROUPS = CHUNK / CPI;       // staging items per pixel and chunk
 constexpr int BATCH_NEAR = 5, BATCH_FAR = 2;   // staging items of a lane whose loads are in flight together (see stage_src)
 constexpr int MAX_GRID = 2048;            // workgroups of a launch
@@ -107,7 +104,7 @@ __device__ __forceinline__ void stage_src(const void* src, const int64_t (&st)[4
             const int py = p / HALO_W, px = p - py * HALO_W;
             const int Y = iy0 + py, X = ix0 + px;
             const bool inside = Y >= 0 && Y < h && X >= 0 && X < w_;
-            at[k] = it < N ? (p * REC + cg * (2 * CPI)) | (inside ? 0 : 1 << 30) : -1;
+            at[k] = it < N ? pvnc::rec_slot(p, cg) | (inside ? 0 : 1 << 30) : -1;
             const int Yc = min(max(Y, 0), h - 1), Xc = min(max(X, 0), w_ - 1);
             if constexpr (NEAR) {
                 const uint32_t o = (uint32_t)(cg * CPI) * n1 + (uint32_t)Yc * n2 + (uint32_t)Xc * n3;
@@ -149,21 +146,8 @@ __device__ __forceinline__ void stage_chunk(const ConvArgs& P, int bi, int iy0, 
 
 __device__ __forceinline__ float activate(float v, int act) {
     if (act == PVNET_TRUNK_ACT_RELU) return v <= 0.f ? 0.f : v;   // a NaN compares false and stays; -0 becomes +0
-    if (act == PVNET_TRUNK_ACT_LEAKY) return v > 0.f ? v : v * 0.1f;
+    if (act == PVNET_TRUNK_ACT_LEAKY) return pvnc::leaky(v);
     return v;
-}
-
-// a lane's sixteen finished values -> its pixel of the 32 planes they are rows of (register g of lane half hh is row
-// (g & 3) + 8 (g >> 2) + 4 hh); `at` is the pixel's element in the block's plane 0.  One running pointer, as in decoder.hip.
-template <int VT>
-__device__ __forceinline__ void store_rows(void* out, size_t at, size_t plane, const f32x16& v, int hh) {
-    typedef typename std::conditional<VT == VT_F32, float, typename std::conditional<VT == VT_F16, _Float16, __bf16>::type>::type T;
-    T* o = reinterpret_cast<T*>(out) + at + (size_t)(4 * hh) * plane;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        *o = (T)v[g];   // one rounding to the output type
-        o += (g & 3) == 3 ? 5 * plane : plane;
-    }
 }
 
 template <int S, int D>
@@ -178,9 +162,8 @@ __global__ __launch_bounds__(THREADS, S == 2 ? 1 : 2) void conv3x3_kernel(ConvAr
 
     for (int item = blockIdx.x; item < P.nitems; item += gridDim.x) {
         const int group = item / P.ntiles, t_ = item - group * P.ntiles;
-        const int tx = t_ % P.tiles_x, rest = t_ / P.tiles_x;
-        const int ty = rest % P.tiles_y, bi = rest / P.tiles_y;
-        const int ty0 = ty * ROWS, tx0 = tx * TILE_W;
+        int bi, ty0, tx0;
+        pvnc::tile_of<TILE_W, ROWS>(P, t_, bi, ty0, tx0);
         const int m = group * WAVES + wave;   // this wave's row block of output channels
         const bool active = m < P.mb;         // wave-uniform; the barriers are outside
         f32x16 acc[ROWS];
@@ -193,8 +176,8 @@ __global__ __launch_bounds__(THREADS, S == 2 ? 1 : 2) void conv3x3_kernel(ConvAr
         // The weights go a ROW OF TAPS at a time (six k-steps, ks = 2 tap + half; row `row` = 3 chunk + ky of the item's 3 nchunk): the
         // next row's six fragments are loaded behind this row's 48 MFMAs, the first row of the next chunk before that chunk is staged.
         // Not unrolled further: eighteen fragments beside the 128 accumulator registers would spill.
-        const size_t kstride = (size_t)P.mb * 64;
-        const bf16x8* wf = P.w + (size_t)(active ? m : 0) * 64 + lane;   // (a wave without channels loads row block 0's and uses nothing)
+        const size_t kstride = pvnc::frag_at((size_t)1, P.mb, 0, 0);   // a k-step of the weights' image
+        const bf16x8* wf = P.w + pvnc::frag_at((size_t)0, P.mb, active ? m : 0, lane);   // (a wave without channels loads row block 0's and uses nothing)
         const int last_row = 3 * P.nchunk - 1;
         bf16x8 A[6];
 #pragma unroll
@@ -240,9 +223,9 @@ __global__ __launch_bounds__(THREADS, S == 2 ? 1 : 2) void conv3x3_kernel(ConvAr
 #pragma unroll
                 for (int g = 0; g < 16; ++g) v[g] = activate(v[g], P.act);
                 const size_t o = ((size_t)bi * (32 * P.mb) + 32 * m) * plane + (size_t)Y * P.wo + X;
-                if (P.out_type == VT_BF16) store_rows<VT_BF16>(P.out, o, plane, v, hh);
-                else if (P.out_type == VT_F16) store_rows<VT_F16>(P.out, o, plane, v, hh);
-                else store_rows<VT_F32>(P.out, o, plane, v, hh);
+                if (P.out_type == VT_BF16) pvnc::store_rows<VT_BF16>(P.out, o, plane, v, hh);
+                else if (P.out_type == VT_F16) pvnc::store_rows<VT_F16>(P.out, o, plane, v, hh);
+                else pvnc::store_rows<VT_F32>(P.out, o, plane, v, hh);
             }
         }
     }
@@ -255,8 +238,6 @@ inline int near_ok(const int64_t st[4], int type, int c, int h, int w) {
                              (type == PVNET_TRUNK_T_F32 ? 4 : 2);
     return span < 2147483648.0L;
 }
-
-inline bool type_ok(int t) { return t == PVNET_TRUNK_T_F32 || t == PVNET_TRUNK_T_F16 || t == PVNET_TRUNK_T_BF16; }
 
 }  // namespace
 }  // namespace pvtrunk
@@ -274,6 +255,7 @@ int pvnet_conv3x3_fused(const void* src1, int src1_type, const int64_t src1_stri
     if (!src1 || !src1_strides || !w || !bias || !out) return PVNET_E_BADARG;
     if ((src2 != nullptr) != (c2 != 0) || (src2 && !src2_strides) || (res && !res_strides)) return PVNET_E_BADARG;
     if (b < 1 || h < 1 || w_ < 1 || c1 < 1 || c2 < 0 || co < 1 || stride < 1 || dilation < 1) return PVNET_E_BADARG;
+    using pvnc::type_ok;
     if (!type_ok(src1_type) || (src2 && !type_ok(src2_type)) || (res && !type_ok(res_type)) || !type_ok(out_type)) return PVNET_E_BADARG;
     if (act != PVNET_TRUNK_ACT_NONE && act != PVNET_TRUNK_ACT_RELU && act != PVNET_TRUNK_ACT_LEAKY) return PVNET_E_BADARG;
     if ((reinterpret_cast<uintptr_t>(w) & 15) != 0) return PVNET_E_BADARG;   // 16-byte fragment loads
@@ -282,15 +264,12 @@ int pvnet_conv3x3_fused(const void* src1, int src1_type, const int64_t src1_stri
     const int geometry = stride == 1 && dilation == 1 ? 0 : stride == 2 && dilation == 1 ? 1 : stride == 1 && dilation == 2 ? 2 :
                          stride == 1 && dilation == 4 ? 3 : -1;
     if (geometry < 0) return PVNET_E_UNSUPPORTED;
-    if (b > 65535 || h > 32768 || w_ > 32768) return PVNET_E_UNSUPPORTED;
+    if (!pvnc::sizes_ok(b, h, w_)) return PVNET_E_UNSUPPORTED;
     ConvArgs P;
     P.ho = (h - 1) / stride + 1;
     P.wo = (w_ - 1) / stride + 1;
-    P.tiles_x = (P.wo + TILE_W - 1) / TILE_W;
-    P.tiles_y = (P.ho + ROWS - 1) / ROWS;
-    const long long ntiles = (long long)b * P.tiles_x * P.tiles_y, nitems = ntiles * ((co + COG - 1) / COG);
-    if (nitems > 0x7FFFFFFFll) return PVNET_E_UNSUPPORTED;
-    P.ntiles = (int)ntiles;
+    const long long nitems = pvnc::plan_tiles<TILE_W, ROWS>(P, b, P.ho, P.wo, (co + COG - 1) / COG);
+    if (nitems < 0) return PVNET_E_UNSUPPORTED;
     P.nitems = (int)nitems;
     P.src[0] = src1;
     P.src[1] = src2;
@@ -315,14 +294,13 @@ int pvnet_conv3x3_fused(const void* src1, int src1_type, const int64_t src1_stri
     P.mb = co / 32;
     P.h = h;
     P.w_ = w_;
-    const dim3 grid(P.nitems < MAX_GRID ? P.nitems : MAX_GRID);
+    const dim3 grid = pvnc::clamped_grid(P.nitems, MAX_GRID);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (geometry == 0) hipLaunchKernelGGL((conv3x3_kernel<1, 1>), grid, dim3(THREADS), 0, s, P);
     else if (geometry == 1) hipLaunchKernelGGL((conv3x3_kernel<2, 1>), grid, dim3(THREADS), 0, s, P);
     else if (geometry == 2) hipLaunchKernelGGL((conv3x3_kernel<1, 2>), grid, dim3(THREADS), 0, s, P);
     else hipLaunchKernelGGL((conv3x3_kernel<1, 4>), grid, dim3(THREADS), 0, s, P);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return pvnc::launch_status();
 }
 
 }  // extern "C"

@@ -18,14 +18,13 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ._abi import (TRUNK_ACT_LEAKY, TRUNK_ACT_NONE, TRUNK_ACT_RELU, TRUNK_GEOMETRIES, TRUNK_MAX_WIDTH, TRUNK_T_BF16, TRUNK_T_F16,
-                   TRUNK_T_F32, _check, load_trunk_library)
+from ._abi import TRUNK_ACT_LEAKY, TRUNK_ACT_NONE, TRUNK_ACT_RELU, TRUNK_GEOMETRIES, TRUNK_MAX_WIDTH, _check, load_trunk_library
 from ._marshal import ptr as _ptr, stream as _stream, strides as _strides
+from ._net import (SLOPE, TYPE_CODES, NetworkParts, Params, check_conv_bn, check_input, conv_bn_act, fold_batchnorm, is_leaky,
+                   is_plain_conv, new_or_checked_out, pack_weights)
 from .decoder import DEFAULT_STAGES
-from .stem import DEFAULT_STEM, FusedStemNet, fused_stem
-from .tail import SLOPE
+from .stem import DEFAULT_STEM, FusedStemNet
 
-_TYPE_CODES = {torch.float32: TRUNK_T_F32, torch.float16: TRUNK_T_F16, torch.bfloat16: TRUNK_T_BF16}
 ACTS = {"none": TRUNK_ACT_NONE, "relu": TRUNK_ACT_RELU, "leaky": TRUNK_ACT_LEAKY}
 LAYERS = ("layer1", "layer2", "layer3", "layer4", "fc", "conv8s")   # the reference's attribute names, in the order the network runs them
 # the pieces FusedTrunkNet fuses unless told otherwise: those that tools/trunk_probe.py measured faster than the eager piece by more than
@@ -38,45 +37,16 @@ def out_sizes(h, w, stride):
     return (h - 1) // stride + 1, (w - 1) // stride + 1
 
 
-def pack_weights(w):
-    """``w [co,cin,3,3]`` float32 -> the bfloat16 image the library takes, ``[cin/32, 9, 2, co/32, 64, 8]``: element
-    (chunk, tap, half, m, lane, j) is ``bf16(w[32 m + (lane & 31)][32 chunk + 16 half + 8 (lane >> 5) + j][tap / 3][tap % 3])``, the
-    rounding torch's round-to-nearest-even"""
-    co, cin = int(w.shape[0]), int(w.shape[1])
-    v = w.to(torch.bfloat16).reshape(co // 32, 32, cin // 32, 2, 2, 8, 9)   # m, r, chunk, half, hh, j, tap
-    return v.permute(2, 6, 3, 0, 4, 1, 5).contiguous().reshape(cin // 32, 9, 2, co // 32, 64, 8)
-
-
-def _fold(conv, bn):
-    """the eval() BatchNorm folded into a bias-free convolution in float64: ``s = gamma / sqrt(var + eps)``, ``w = W * s``, ``bias =
-    beta - mean * s``, each rounded once to float32"""
-    with torch.no_grad():
-        var, mean = bn.running_var.double(), bn.running_mean.double()
-        gamma = bn.weight.double() if bn.weight is not None else torch.ones_like(var)
-        beta = bn.bias.double() if bn.bias is not None else torch.zeros_like(var)
-        s = gamma / torch.sqrt(var + bn.eps)
-        return (conv.weight.double() * s[:, None, None, None]).float().cpu(), (beta - mean * s).float().cpu()
-
-
-def _check_bn(who, conv, bn):
-    if not (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)):
-        raise ValueError(f"{who}: expected Conv2d, BatchNorm2d")
-    if bn.training or bn.running_mean is None or bn.running_var is None:
-        raise ValueError(f"{who}: the BatchNorm must be in eval() mode with running statistics (inference only)")
-    if conv.bias is not None:
-        raise ValueError(f"{who}: the reference's convolutions have no bias")
-    if bn.num_features != conv.out_channels:
-        raise ValueError(f"{who}: the BatchNorm's width is not the convolution's")
-
-
-class ConvParams:
+class ConvParams(Params):
     """A convolution's weights as the library takes them: ``w [co,cin,3,3]`` and ``bias [co]`` (the 3 x 3 convolution with the
     BatchNorm folded in), float32 and contiguous, ``packed``, the same weights rounded to bfloat16 in the kernel's fragment order, and
     its ``stride``, ``dilation`` (one of (1,1), (2,1), (1,2), (1,4); the padding is the dilation) and ``act`` ("none", "relu" or
     "leaky").  ``on(device)`` gives (and keeps) the device's copies of ``bias`` and ``packed``."""
 
+    DEVICE = ("bias", "packed")
+
     def __init__(self, w, bias, stride=1, dilation=1, act="none"):
-        w, bias = (torch.as_tensor(t).detach().to(torch.float32).contiguous() for t in (w, bias))
+        w, bias = self.float32(w, bias)
         if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or tuple(bias.shape) != (int(w.shape[0]),):
             raise ValueError(f"ConvParams: w must be [co,cin,3,3] and bias [co] (got {tuple(w.shape)}, {tuple(bias.shape)})")
         co, cin = int(w.shape[0]), int(w.shape[1])
@@ -90,25 +60,18 @@ class ConvParams:
         self.w, self.bias = w, bias
         self.cin, self.co, self.stride, self.dilation, self.act = cin, co, int(stride), int(dilation), act
         self.packed = pack_weights(w)
-        self._on = {}
-
-    def on(self, device):
-        device = torch.device(device)
-        if device not in self._on:
-            self._on[device] = tuple(t.to(device) for t in (self.bias, self.packed))
-        return self._on[device]
 
     @classmethod
     def from_modules(cls, conv, bn, act=None):
-        """Folds the ``eval()`` BatchNorm into the convolution in float64, exactly as ``StageParams.from_modules`` does.  Refuses what
+        """Folds the ``eval()`` BatchNorm into the convolution in float64, with ``_net.fold_batchnorm``.  Refuses what
         the fused convolution does not compute: a BatchNorm in training mode or without running statistics, a convolution with a bias,
         a kernel other than 3 x 3, a padding that is not the dilation, groups, an activation (``act``: None, a module or one of
         "none", "relu", "leaky") other than ReLU and LeakyReLU(0.1), widths, strides and dilations outside the library's."""
-        _check_bn("ConvParams", conv, bn)
+        check_conv_bn("ConvParams", conv, bn)
         if isinstance(act, nn.ReLU):
             act = "relu"
         elif isinstance(act, nn.LeakyReLU):
-            if float(act.negative_slope) != SLOPE:
+            if not is_leaky(act):
                 raise ValueError(f"ConvParams: the LeakyReLU slope must be {SLOPE} (got {act})")
             act = "leaky"
         elif act is None:
@@ -120,7 +83,7 @@ class ConvParams:
         if conv.stride[0] != conv.stride[1] or conv.dilation[0] != conv.dilation[1] or tuple(conv.padding) != tuple(conv.dilation):
             raise ValueError(f"ConvParams: the padding must be the dilation, both square (got stride {conv.stride}, padding "
                              f"{conv.padding}, dilation {conv.dilation})")
-        return cls(*_fold(conv, bn), stride=conv.stride[0], dilation=conv.dilation[0], act=act)
+        return cls(*fold_batchnorm(conv, bn), stride=conv.stride[0], dilation=conv.dilation[0], act=act)
 
 
 def fused_conv3x3(src1, params, *, src2=None, residual=None, out=None, out_dtype=None):
@@ -137,10 +100,8 @@ def fused_conv3x3(src1, params, *, src2=None, residual=None, out=None, out_dtype
     if not isinstance(params, ConvParams):
         raise RuntimeError("params must be a ConvParams")
     for name, t in (("src1", src1), ("src2", src2), ("residual", residual)):
-        if t is None and name != "src1":
-            continue
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.dtype in _TYPE_CODES):
-            raise RuntimeError(f"{name} must be a 4-D float32, float16 or bfloat16 CUDA tensor")
+        if t is not None or name == "src1":
+            check_input(name, t)
     dev = src1.device
     b, c1, h, w = (int(v) for v in src1.shape)
     c2 = 0 if src2 is None else int(src2.shape[1])
@@ -154,36 +115,18 @@ def fused_conv3x3(src1, params, *, src2=None, residual=None, out=None, out_dtype
     shape = (b, params.co, ho, wo)
     if residual is not None and (residual.device != dev or tuple(residual.shape) != shape):
         raise RuntimeError(f"residual must be {shape} on {dev} (got {tuple(residual.shape)} on {residual.device})")
-    if out is None:
-        dtype = out_dtype if out_dtype is not None else src1.dtype
-        if dtype not in _TYPE_CODES:
-            raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
-        out = torch.empty(shape, dtype=dtype, device=dev)
-    else:
-        want = out_dtype if out_dtype is not None else out.dtype if isinstance(out, torch.Tensor) else None
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == want and out.dtype in _TYPE_CODES and
-                tuple(out.shape) == shape and out.is_contiguous()):
-            raise RuntimeError(f"out must be a contiguous {want} CUDA tensor of shape {shape} on {dev}")
+    out = new_or_checked_out(out, out_dtype, src1.dtype, shape, dev)
     bias, wpk = params.on(dev)
     lib = load_trunk_library()
 
     def triple(t):
-        return (None, 0, None) if t is None else (_ptr(t), _TYPE_CODES[t.dtype], _strides(t, 4))
+        return (None, 0, None) if t is None else (_ptr(t), TYPE_CODES[t.dtype], _strides(t, 4))
 
     with torch.cuda.device(dev):
         _check(lib.pvnet_conv3x3_fused(*triple(src1), *triple(src2), *triple(residual), _ptr(wpk), _ptr(bias), b, h, w, c1, c2,
-                                       params.co, params.stride, params.dilation, ACTS[params.act], _ptr(out), _TYPE_CODES[out.dtype],
+                                       params.co, params.stride, params.dilation, ACTS[params.act], _ptr(out), TYPE_CODES[out.dtype],
                                        _stream(dev)), "pvnet_conv3x3_fused")
     return out
-
-
-def _block_modules(block):
-    """(conv1, bn1, conv2, bn2, downsample) of the reference's ``BasicBlock`` or of the stand-in's ``B`` (tools/e2e_amd.py)"""
-    for names in (("conv1", "bn1", "conv2", "bn2", "downsample"), ("c1", "b1", "c2", "b2", "down")):
-        if all(hasattr(block, n) for n in names) and not hasattr(block, "conv3"):   # (conv3: the Bottleneck, which is not supported)
-            return tuple(getattr(block, n) for n in names)
-    raise ValueError("FusedBasicBlock: neither the reference's BasicBlock (conv1, bn1, conv2, bn2, downsample) nor the stand-in's "
-                     "(c1, b1, c2, b2, down)")
 
 
 class FusedBasicBlock(nn.Module):
@@ -193,7 +136,7 @@ class FusedBasicBlock(nn.Module):
 
     def __init__(self, block):
         super().__init__()
-        conv1, bn1, conv2, bn2, down = _block_modules(block)
+        conv1, bn1, conv2, bn2, down = NetworkParts.basic_block(block)
         self.conv1 = ConvParams.from_modules(conv1, bn1, "relu")
         self.conv2 = ConvParams.from_modules(conv2, bn2, "relu")
         if (self.conv2.stride, self.conv2.cin) != (1, self.conv1.co):
@@ -202,11 +145,10 @@ class FusedBasicBlock(nn.Module):
         if down is not None:
             if not (isinstance(down, nn.Sequential) and len(down) == 2):
                 raise ValueError("FusedBasicBlock: the downsample must be a Sequential of Conv2d, BatchNorm2d")
-            _check_bn("FusedBasicBlock: downsample", down[0], down[1])
-            plain = (tuple(down[0].kernel_size), tuple(down[0].padding), tuple(down[0].dilation), down[0].groups)
-            if plain != ((1, 1), (0, 0), (1, 1), 1) or tuple(down[0].stride) != (self.conv1.stride,) * 2:
+            check_conv_bn("FusedBasicBlock: downsample", down[0], down[1])
+            if not is_plain_conv(down[0], 1, self.conv1.stride, 0, 1):
                 raise ValueError("FusedBasicBlock: the downsample must be Conv2d(cin, cout, 1, stride) with conv1's stride")
-            self.down = _fold(down[0], down[1])
+            self.down = fold_batchnorm(down[0], down[1])
         elif self.conv1.stride != 1 or self.conv1.cin != self.conv2.co:
             raise ValueError("FusedBasicBlock: a block that changes its shape needs a downsample")
         self._down_on = {}
@@ -227,12 +169,6 @@ class FusedBasicBlock(nn.Module):
         return fused_conv3x3(y, self.conv2, residual=self.residual(x))
 
 
-def _seq_params(seq, who):
-    if not isinstance(seq, nn.Sequential) or len(seq) != 3:
-        raise ValueError(f"FusedTrunkNet: the network has no `{who}` Sequential of conv, bn, act")
-    return ConvParams.from_modules(seq[0], seq[1], seq[2])
-
-
 class FusedTrunkNet(FusedStemNet):
     """``FusedStemNet`` with the pieces of the trunk named in ``layers`` -- drawn from ``LAYERS`` -- run through ``fused_conv3x3``:
     ``layer1 .. layer4`` (the stand-in's ``l1 .. l4``) as ``FusedBasicBlock``s, ``fc`` as one launch, ``conv8s`` as one launch that
@@ -250,32 +186,27 @@ class FusedTrunkNet(FusedStemNet):
             raise ValueError(f"layers must be drawn from {LAYERS} (got {layers})")
         self.layers = layers
         self.blocks = nn.ModuleDict({name: nn.ModuleList(FusedBasicBlock(blk) for blk in seq)
-                                     for name, seq in zip(LAYERS[:4], self._layers) if name in layers})
-        self.fc_params = _seq_params(self._fc, "fc") if "fc" in layers else None
-        self.conv8s_params = _seq_params(net.conv8s, "conv8s") if "conv8s" in layers else None
+                                     for name, seq in zip(LAYERS[:4], self.parts.layers) if name in layers})
+        self.fc_params, self.conv8s_params = (ConvParams.from_modules(*conv_bn_act(self.parts, name, "FusedTrunkNet")) if name in layers
+                                              else None for name in ("fc", "conv8s"))
         if layers:   # with none named, FusedStemNet's own trunk stays: the same calls, so the same bits
             self._trunk = self._trunk_fused
 
     def _layer(self, k, x, fuse):
         name = LAYERS[k]
         if not (fuse and name in self.layers):
-            return self._layers[k](x)
+            return self.parts.layers[k](x)
         for blk in self.blocks[name]:
             x = blk(x)
         return x
 
     def _trunk_fused(self, x):
-        dtype = self._stem_dtype(x)
-        if dtype is None:
-            x2s = self._stem_modules(x)
-            p = self._pool(x2s)
-        else:
-            x2s, p = fused_stem(x, self.stem_params, out_dtype=dtype)
+        x2s, p = self._stem(x)
         fuse = self.precision == "bf16" or (self.precision is None and p.dtype != torch.float32)
         x4s = self._layer(0, p, fuse)
         x8s = self._layer(1, x4s, fuse)
         x32s = self._layer(3, self._layer(2, x8s, fuse), fuse)
-        xfc = fused_conv3x3(x32s, self.fc_params) if fuse and "fc" in self.layers else self._fc(x32s)
+        xfc = fused_conv3x3(x32s, self.fc_params) if fuse and "fc" in self.layers else self.parts.fc(x32s)
         if fuse and "conv8s" in self.layers:
             return fused_conv3x3(xfc, self.conv8s_params, src2=x8s), x4s, x2s
-        return self.net.conv8s(torch.cat([xfc, x8s], 1)), x4s, x2s
+        return self.parts.eager_conv8s(xfc, x8s), x4s, x2s

@@ -74,6 +74,24 @@ def time_ms(fn, sets, reps):
     return e0.elapsed_time(e1) / (reps * len(sets))
 
 
+def network_error(say, dev, label, make, other_label, make_other):
+    """the fused network probes' last lines: the seeded stand-in under ``make(net)`` and ``make_other(net)`` against the eager float32
+    network, under autocast(bfloat16)"""
+    from tests import tail_cases as TC
+    net, x = TC.standin()
+    net, x = net.to(dev), x.to(dev)
+    with torch.no_grad():
+        ref = torch.cat(net(x), 1).double()
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            eager = torch.cat(net(x), 1).double()
+            fused = torch.cat(make(net)(x), 1).double()
+            other = torch.cat(make_other(net)(x), 1).double()
+    e, d = float((eager - ref).abs().max()), float((fused - ref).abs().max())
+    say()
+    say("== the seeded stand-in of tests/tail_cases.py, 1 x 3 x 32 x 48, autocast(bfloat16): largest difference to the eager float32 network")
+    say(f"  eager e = {e:.4e};  {label} {d:.4e} = {d / e:.2f} e (the test's bar is 2 e);  {other_label} {float((other - ref).abs().max()):.4e}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "head_metrics_probe.txt"))

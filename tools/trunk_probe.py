@@ -28,27 +28,10 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from pvnet_amd import decoder as D  # noqa: E402
 from pvnet_amd import stem as S  # noqa: E402
 from pvnet_amd import trunk as T  # noqa: E402
-from head_metrics_probe import H, W, time_ms  # noqa: E402
+from head_metrics_probe import H, W, network_error, time_ms  # noqa: E402
 import e2e_amd  # noqa: E402
 
 PEAK = 2.5e15   # bfloat16 matrix peak, dense, FLOP/s
-
-
-def network_error(say, dev):
-    from tests import tail_cases as TC
-    net, x = TC.standin()
-    net, x = net.to(dev), x.to(dev)
-    with torch.no_grad():
-        ref = torch.cat(net(x), 1).double()
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            eager = torch.cat(net(x), 1).double()
-            fused = torch.cat(T.FusedTrunkNet(net, layers=T.LAYERS, stem=True, stages=D.STAGES)(x), 1).double()
-            stem = torch.cat(S.FusedStemNet(net, stem=True, stages=D.STAGES)(x), 1).double()
-    e = float((eager - ref).abs().max())
-    say()
-    say("== the seeded stand-in of tests/tail_cases.py, 1 x 3 x 32 x 48, autocast(bfloat16): largest difference to the eager float32 network")
-    say(f"  eager e = {e:.4e};  FusedTrunkNet (all six pieces, stem and both stages) {float((fused - ref).abs().max()):.4e} = "
-        f"{float((fused - ref).abs().max()) / e:.2f} e (the test's bar is 2 e);  FusedStemNet {float((stem - ref).abs().max()):.4e}")
 
 
 def conv_work(p, b, h, w):
@@ -178,7 +161,9 @@ def main():
         v = tn[n]
         m = sorted(v)[len(v) // 2]
         say(f"  {n:90s} {m:8.2f} ms  ({min(v):.2f} .. {max(v):.2f})  {(m / base - 1) * 100:+6.1f} % of eager")
-    network_error(say, dev)
+    network_error(say, dev, "FusedTrunkNet (all six pieces, stem and both stages)",
+                  lambda net: T.FusedTrunkNet(net, layers=T.LAYERS, stem=True, stages=D.STAGES),
+                  "FusedStemNet", lambda net: S.FusedStemNet(net, stem=True, stages=D.STAGES))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
