@@ -133,7 +133,7 @@ int pvnet_render_depth(const double* vertices, const int32_t* faces, const int32
                        int P, int T, int q, const int32_t* mesh_id, const double* poses, const double* K, int k_per_instance,
                        const int32_t* image_id, const int32_t* label, int b, int h, int w, float far, float* depth_out,
                        uint8_t* label_out, int32_t* visible_out, int32_t* status_out, void* ws, size_t ws_bytes, void* stream) {
-    const Scene S = {vertices, faces, vertex_offset, face_offset, M, P, T, q, mesh_id, poses, K, k_per_instance, image_id, label, b, h, w, far};
+    const Scene S = {{vertices, faces, vertex_offset, face_offset, M, P, T, q, mesh_id, poses, K, k_per_instance, image_id, label, b, h, w}, far};
     int rc, max_f;
     Table tab;
     Workspace W;

@@ -5,7 +5,7 @@
 //
 // An object mesh has tens of thousands of triangles of a few pixels each, so the work is TRIANGLE-parallel into bit planes (one
 // [h, ceil(w/32)] uint32 plane per instance), not pixel-parallel over a triangle list:
-//   setup_kernel        (pvnet_render only) one workgroup: the instance table, which arrives in the launch's arguments, becomes
+//   setup_kernel        (pvnet_render only) one workgroup: the instance table (mesh_core.h), which arrives in the launch's arguments, becomes
 //                       records in the workspace (mesh ranges, the prefix of the faces for tri_out); status and counters zeroed
 //   clear_check_kernel  clears the planes with 16-byte stores; other workgroups of the same launch evaluate camera z of every vertex
 //                       of every instance (PVNET_RASTER_S_BEHIND)
@@ -38,13 +38,8 @@ struct Inst {   // one instance, as the kernels read it
 };
 static_assert(sizeof(Inst) == 32, "workspace layout");
 
-// the instance table as it travels in setup_kernel's arguments: mesh (6 bits) | label (8) << 6 | image (18) << 14
-struct Table {
-    uint32_t inst[PVNET_RASTER_MAX_INSTANCES];
-    int32_t voff[PVNET_RASTER_MAX_MESHES + 1], foff[PVNET_RASTER_MAX_MESHES + 1];
-};
-static_assert(sizeof(Table) <= 3800, "kernel arguments: 4 KB with the rest");
-static_assert(PVNET_RASTER_MAX_MESHES <= 64 && PVNET_RASTER_MAX_IMAGES < (1 << 18), "the packing of Table::inst");
+static_assert(PVNET_RASTER_MAX_INSTANCES == MAX_INSTANCES && PVNET_RASTER_MAX_MESHES == MAX_MESHES && PVNET_RASTER_MAX_IMAGES == MAX_IMAGES &&
+                  PVNET_RASTER_MAX_SIDE == MAX_IMAGE_SIDE, "mesh_core.h's Table and checks are written in this public header's limits");
 
 constexpr size_t WS_HEAD = 16;   // counters: [0] triangles that took the cooperative path
 
@@ -323,12 +318,6 @@ __global__ __launch_bounds__(TPB) void expand_kernel(ExpandParams P) {
     }
 }
 
-bool sizes_ok(int h, int w, int* rc) {
-    if (h < 2 || w < 2) { *rc = PVNET_E_BADARG; return false; }
-    if (h > PVNET_RASTER_MAX_SIDE || w > PVNET_RASTER_MAX_SIDE) { *rc = PVNET_E_UNSUPPORTED; return false; }
-    return true;
-}
-
 size_t plane_bytes(int q, int h, int w) {
     const size_t words = (size_t)q * (size_t)h * (size_t)((w + 31) / 32);
     return (words * 4 + 15) / 16 * 16;
@@ -371,7 +360,7 @@ int pvnet_raster_triangles(const float* tri, int n, int tn, int h, int w, uint8_
                            size_t ws_bytes, void* stream) {
     int rc = 0;
     if (n < 0 || tn < 0) return PVNET_E_BADARG;
-    if (!sizes_ok(h, w, &rc)) return rc;
+    if ((rc = check_sizes(h, w))) return rc;
     if (n > PVNET_RASTER_MAX_IMAGES) return PVNET_E_UNSUPPORTED;
     if (n == 0) return 0;
     if (!mask_out || !ws || (tn > 0 && !tri)) return PVNET_E_BADARG;
@@ -410,27 +399,14 @@ int pvnet_render(const double* vertices, const int32_t* faces, const int32_t* ve
                  int T, int q, const int32_t* mesh_id, const double* poses, const double* K, int k_per_instance,
                  const int32_t* image_id, const int32_t* label, const int32_t* order, int b, int h, int w, uint8_t* out,
                  float* tri_out, int32_t* status_out, void* ws, size_t ws_bytes, void* stream) {
-    int rc = 0;
-    if (M < 1 || P < 0 || T < 0 || q < 0 || b < 0) return PVNET_E_BADARG;
-    if (!sizes_ok(h, w, &rc)) return rc;
-    if (M > PVNET_RASTER_MAX_MESHES || q > PVNET_RASTER_MAX_INSTANCES || b > PVNET_RASTER_MAX_IMAGES) return PVNET_E_UNSUPPORTED;
-    if (!vertex_offset || !face_offset) return PVNET_E_BADARG;
-    if (vertex_offset[0] != 0 || face_offset[0] != 0 || vertex_offset[M] != P || face_offset[M] != T) return PVNET_E_BADARG;
-    for (int m = 0; m < M; ++m)
-        if (vertex_offset[m + 1] < vertex_offset[m] || face_offset[m + 1] < face_offset[m]) return PVNET_E_BADARG;
-    if (!out && !tri_out) return PVNET_E_BADARG;
-    if (q > 0 && (!mesh_id || !image_id || !label || !poses || !K)) return PVNET_E_BADARG;
-    if ((P > 0 && !vertices) || (T > 0 && !faces)) return PVNET_E_BADARG;
-    int max_v = 0, max_f = 0;
+    const Instances S = {vertices, faces, vertex_offset, face_offset, M, P, T, q, mesh_id, poses, K, k_per_instance, image_id, label, b, h, w};
+    int rc = 0, max_v, max_f;
     Table tab;
-    for (int i = 0; i < q; ++i) {
-        if (mesh_id[i] < 0 || mesh_id[i] >= M) return PVNET_E_BADARG;
-        if (label[i] < 1 || label[i] > 255) return PVNET_E_BADARG;
-        if (image_id[i] < 0 || image_id[i] >= b || (i > 0 && image_id[i] < image_id[i - 1])) return PVNET_E_BADARG;
-        max_v = std::max(max_v, vertex_offset[mesh_id[i] + 1] - vertex_offset[mesh_id[i]]);
-        max_f = std::max(max_f, face_offset[mesh_id[i] + 1] - face_offset[mesh_id[i]]);
-        tab.inst[i] = (uint32_t)mesh_id[i] | ((uint32_t)label[i] << 6) | ((uint32_t)image_id[i] << 14);
-    }
+    if ((rc = check_counts(S))) return rc;
+    if ((rc = check_tables(S))) return rc;
+    if (!out && !tri_out) return PVNET_E_BADARG;
+    if ((rc = check_arrays(S))) return rc;
+    if ((rc = check_instances(S, &tab, &max_f, &max_v))) return rc;
     if (b == 0) return 0;
     if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15u)) return PVNET_E_BADARG;
     if (ws_bytes < pvnet_raster_workspace_bytes(q, P, T, b, h, w)) return PVNET_E_WORKSPACE;
@@ -440,11 +416,6 @@ int pvnet_render(const double* vertices, const int32_t* faces, const int32_t* ve
     Inst* recs = reinterpret_cast<Inst*>(base + WS_HEAD);
     uint32_t* planes = reinterpret_cast<uint32_t*>(base + WS_HEAD + sizeof(Inst) * (size_t)q);
     if (q == 0) return out ? launch_expand(planes, nullptr, nullptr, 0, 0, b, h, w, out, s) : 0;
-    for (int i = q; i < PVNET_RASTER_MAX_INSTANCES; ++i) tab.inst[i] = 0u;
-    for (int m = 0; m <= PVNET_RASTER_MAX_MESHES; ++m) {
-        tab.voff[m] = vertex_offset[std::min(m, M)];
-        tab.foff[m] = face_offset[std::min(m, M)];
-    }
     hipLaunchKernelGGL(setup_kernel, dim3(1), dim3(1024), 0, s, tab, q, recs, status_out, counters);
     if ((rc = last_error())) return rc;
     ClearParams C;

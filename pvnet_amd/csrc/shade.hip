@@ -98,7 +98,7 @@ int pvnet_render_color(const double* vertices, const int32_t* faces, const int32
                        const double* normals, int shading, float ambient, const uint8_t* bg_color, const uint8_t* bg_image,
                        uint8_t* rgb_out, float* depth_out, uint8_t* label_out, int32_t* visible_out, int32_t* status_out, void* ws,
                        size_t ws_bytes, void* stream) {
-    const Scene S = {vertices, faces, vertex_offset, face_offset, M, P, T, q, mesh_id, poses, K, k_per_instance, image_id, label, b, h, w, far};
+    const Scene S = {{vertices, faces, vertex_offset, face_offset, M, P, T, q, mesh_id, poses, K, k_per_instance, image_id, label, b, h, w}, far};
     int rc, max_f;
     Table tab;
     Workspace W;

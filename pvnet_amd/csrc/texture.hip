@@ -141,7 +141,7 @@ int pvnet_render_textured(const double* vertices, const int32_t* faces, const in
                           const int32_t* tex_h, const int32_t* tex_w, int filter, int shading, float ambient, const uint8_t* bg_color,
                           const uint8_t* bg_image, uint8_t* rgb_out, float* depth_out, uint8_t* label_out, int32_t* visible_out,
                           int32_t* status_out, void* ws, size_t ws_bytes, void* stream) {
-    const Scene S = {vertices, faces, vertex_offset, face_offset, M, P, T, q, mesh_id, poses, K, k_per_instance, image_id, label, b, h, w, far};
+    const Scene S = {{vertices, faces, vertex_offset, face_offset, M, P, T, q, mesh_id, poses, K, k_per_instance, image_id, label, b, h, w}, far};
     int rc, max_f;
     TexturedTable tab;
     Workspace W;

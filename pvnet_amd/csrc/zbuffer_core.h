@@ -25,7 +25,7 @@ namespace pvd {
 namespace {
 
 // the limits and the status bits: equal in include/pvnet_depth.h, pvnet_shade.h and pvnet_texture.h under their own prefixes
-constexpr int LANE_PIXELS = 64, MAX_INSTANCES = 768, MAX_MESHES = 64, MAX_IMAGES = 65535, MAX_IMAGE_SIDE = 32768;
+constexpr int LANE_PIXELS = 64;   // (MAX_INSTANCES, MAX_MESHES, MAX_IMAGES, MAX_IMAGE_SIDE: mesh_core.h)
 constexpr int S_NONFINITE = 1, S_BEHIND = 2, S_BADFACE = 4;
 #define PVNET_ZBUFFER_CONSTANTS_ARE(PREFIX, SIDE)                                                                                       \
     static_assert(PREFIX##LANE_PIXELS == pvd::LANE_PIXELS && PREFIX##MAX_INSTANCES == pvd::MAX_INSTANCES &&                            \
@@ -46,14 +46,6 @@ struct Inst {   // one instance, as the kernels read it
     uint32_t dims;   // th << 16 | tw; 0: the mesh has no texture
 };
 static_assert(sizeof(Inst) == 32, "workspace layout: 16-byte aligned records");
-
-// the instance table as it travels in a setup kernel's arguments: mesh (6 bits) | label (8) << 6 | image (18) << 14
-struct Table {
-    uint32_t inst[MAX_INSTANCES];
-    int32_t voff[MAX_MESHES + 1], foff[MAX_MESHES + 1];
-};
-static_assert(sizeof(Table) <= 3800, "kernel arguments: 4 KB with the rest");
-static_assert(MAX_MESHES <= 64 && MAX_IMAGES < (1 << 18), "the packing of Table::inst");
 
 constexpr size_t WS_HEAD = 16;   // counters: [0] triangles that took the cooperative path
 
@@ -247,18 +239,7 @@ __device__ __forceinline__ void tri_body(const TriParams& P) {
 
 // ---- the host side ----------------------------------------------------------------------------------------------------------------------
 
-// the argument list the three entry points share
-struct Scene {
-    const double* vertices;
-    const int32_t *faces, *vertex_offset, *face_offset;
-    int M, P, T, q;
-    const int32_t* mesh_id;
-    const double *poses, *K;
-    int k_per_instance;
-    const int32_t *image_id, *label;
-    int b, h, w;
-    float far;
-};
+struct Scene : Instances { float far; };   // the argument list the three entry points share
 
 size_t zbuf_bytes(int b, int h, int w) { return ((size_t)b * (size_t)h * (size_t)w * 8 + 15) / 16 * 16; }
 
@@ -273,40 +254,14 @@ int last_error() {
     return e == hipSuccess ? 0 : (int)e;
 }
 
-// The validation, in the order the entry points have always returned their codes in.  First the counts, far, the sizes, the limits,
-// the mesh table and the arrays: 0 or the code.  A library's checks of its own scalars (all PVNET_E_BADARG) go before this call, those
-// of its own arrays and outputs between this call and check_instances.
+// mesh_core.h's validation through the arrays, far in its place: 0 or the code.  A library's checks of its own scalars (all
+// PVNET_E_BADARG) go before this call, those of its own arrays and outputs between this call and check_instances.
 int check_scene(const Scene& S) {
-    if (S.M < 1 || S.P < 0 || S.T < 0 || S.q < 0 || S.b < 0) return PVNET_E_BADARG;
+    int rc;
+    if ((rc = check_counts(S))) return rc;
     if (!(S.far > 0.f)) return PVNET_E_BADARG;   // (NaN too)
-    if (S.h < 2 || S.w < 2) return PVNET_E_BADARG;
-    if (S.h > MAX_IMAGE_SIDE || S.w > MAX_IMAGE_SIDE) return PVNET_E_UNSUPPORTED;
-    if (S.M > MAX_MESHES || S.q > MAX_INSTANCES || S.b > MAX_IMAGES) return PVNET_E_UNSUPPORTED;
-    if (!S.vertex_offset || !S.face_offset) return PVNET_E_BADARG;
-    if (S.vertex_offset[0] != 0 || S.face_offset[0] != 0 || S.vertex_offset[S.M] != S.P || S.face_offset[S.M] != S.T) return PVNET_E_BADARG;
-    for (int m = 0; m < S.M; ++m)
-        if (S.vertex_offset[m + 1] < S.vertex_offset[m] || S.face_offset[m + 1] < S.face_offset[m]) return PVNET_E_BADARG;
-    if (S.q > 0 && (!S.mesh_id || !S.image_id || !S.label || !S.poses || !S.K)) return PVNET_E_BADARG;
-    if ((S.P > 0 && !S.vertices) || (S.T > 0 && !S.faces)) return PVNET_E_BADARG;
-    return 0;
-}
-
-// Then the instances, packed into the table as they are checked; *max_f: the most faces a mesh of an instance has
-int check_instances(const Scene& S, Table* tab, int* max_f) {
-    *max_f = 0;
-    for (int i = 0; i < S.q; ++i) {
-        if (S.mesh_id[i] < 0 || S.mesh_id[i] >= S.M) return PVNET_E_BADARG;
-        if (S.label[i] < 1 || S.label[i] > 255) return PVNET_E_BADARG;
-        if (S.image_id[i] < 0 || S.image_id[i] >= S.b || (i > 0 && S.image_id[i] < S.image_id[i - 1])) return PVNET_E_BADARG;
-        *max_f = std::max(*max_f, S.face_offset[S.mesh_id[i] + 1] - S.face_offset[S.mesh_id[i]]);
-        tab->inst[i] = (uint32_t)S.mesh_id[i] | ((uint32_t)S.label[i] << 6) | ((uint32_t)S.image_id[i] << 14);
-    }
-    for (int i = S.q; i < MAX_INSTANCES; ++i) tab->inst[i] = 0u;
-    for (int m = 0; m <= MAX_MESHES; ++m) {
-        tab->voff[m] = S.vertex_offset[std::min(m, S.M)];
-        tab->foff[m] = S.face_offset[std::min(m, S.M)];
-    }
-    return 0;
+    if ((rc = check_tables(S))) return rc;
+    return check_arrays(S);
 }
 
 // Last the workspace and the size of the resolve grid (b > 0): the workspace's parts

@@ -21,84 +21,33 @@ in a graph.  PyTorch is plumbing only.  There is NO CPU fallback: without the li
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from ._abi import (DEPTH_MAX_INSTANCES, DEPTH_S_BADFACE, DEPTH_S_BEHIND, DEPTH_S_NONFINITE, _check,  # noqa: F401
-                   load_depth_library)
-from ._marshal import nbytes as _nbytes, ptr as _ptr, stream as _stream, workspace as _workspace
-from .render import DeviceMeshes, _camera, _poses
+from . import _mesh
+from ._abi import DEPTH_MAX_INSTANCES, DEPTH_S_BADFACE, DEPTH_S_BEHIND, DEPTH_S_NONFINITE  # noqa: F401
+from .render import DeviceMeshes
+
+_DEPTH = _mesh.Front("depth", DeviceMeshes, DEPTH_MAX_INSTANCES, "pvnet_render_depth")
 
 
 def depth_workspace_bytes(q, b, h, w, meshes=None):
     """bytes of workspace for q instances composed into b images of h x w pixels"""
-    P, T = (meshes.total_vertices, meshes.total_faces) if meshes is not None else (0, 0)
-    n = int(load_depth_library().pvnet_depth_workspace_bytes(int(q), P, T, int(b), int(h), int(w)))
-    if n == 0:
-        raise RuntimeError(f"depth_workspace_bytes: arguments out of range (q={q}, b={b}, h={h}, w={w}; h, w >= 2)")
-    return n
+    return _mesh.workspace_bytes("depth", q, b, h, w, meshes)
 
 
-def _out(out, shape, dtype, dev, what):
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == dtype and
-            tuple(out.shape) == tuple(shape) and out.is_contiguous()):
-        raise RuntimeError(f"{what} must be a contiguous {dtype} CUDA tensor of shape {tuple(shape)} on {dev}")
-    return out
-
-
-def _image_stretches(b, m, limit):
-    """(first image, end) of every stretch of whole images with at most ``limit`` instances, m per image: one library call each
-    (``shade.render_color`` splits the same way)"""
-    images = max(1, limit // m) if m else max(b, 1)
-    return [(i0, min(b, i0 + images)) for i0 in range(0, b, images)]
-
-
-def _render(meshes, mesh_ids, labels, poses, K, h, w, far, depth, label, visible, status, workspace):
-    """one pvnet_render_depth call per stretch of whole images with at most DEPTH_MAX_INSTANCES instances; ``poses`` [b,m,3,4]"""
-    lib = load_depth_library()
-    dev = poses.device
-    b, m = int(poses.shape[0]), int(poses.shape[1])
-    Kd, per = _camera(K, dev, (b, m))
-    vertices, faces, _ = meshes.on(dev)
-    flat = poses.view(-1, 3, 4)
-    with torch.cuda.device(dev):
-        for i0, i1 in _image_stretches(b, m, DEPTH_MAX_INSTANCES):
-            nb, n = i1 - i0, (i1 - i0) * m
-            s = i0 * m
-            ws = _workspace(workspace, depth_workspace_bytes(n, nb, h, w, meshes), dev, align=16, sized=True)
-            arr = lambda vals: (C.c_int32 * max(n, 1))(*vals)   # noqa: E731
-            _check(lib.pvnet_render_depth(
-                _ptr(vertices), _ptr(faces), meshes._c_voff, meshes._c_foff, meshes.count, meshes.total_vertices, meshes.total_faces, n,
-                arr(mesh_ids * nb), _ptr(flat[s:]) if n else None, _ptr(Kd[s:] if per else Kd), 1 if per else 0,
-                arr([i for i in range(nb) for _ in range(m)]), arr(labels * nb), nb, h, w, far,
-                _ptr(depth[i0:]) if depth is not None else None, _ptr(label[i0:]) if label is not None else None,
-                _ptr(visible[s:]) if visible is not None and n else None, _ptr(status[s:]) if status is not None and n else None,
-                _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_render_depth")
-
-
-def _checked(meshes, mesh_ids, labels, poses, h, w, far, limit=DEPTH_MAX_INSTANCES):
-    if not isinstance(meshes, DeviceMeshes):
-        raise RuntimeError("meshes must be a DeviceMeshes")
-    dev = poses.device if isinstance(poses, torch.Tensor) else None
-    poses = _poses(poses, dev, 4)
-    m, h, w, far = int(poses.shape[1]), int(h), int(w), float(far)
-    mesh_ids, labels = [int(x) for x in mesh_ids], [int(x) for x in labels]
-    if len(mesh_ids) != m or len(labels) != m or any(not 0 <= x < meshes.count for x in mesh_ids):
-        raise RuntimeError(f"mesh_ids and labels must have m={m} entries, mesh ids in 0 .. {meshes.count - 1}")
-    if any(not 1 <= x <= 255 for x in labels):
-        raise RuntimeError("labels must lie in 1 .. 255")
-    if h < 2 or w < 2:
-        raise RuntimeError("h and w must be at least 2")
-    if m > limit:
-        raise RuntimeError(f"at most {limit} instances per image")
-    if math.isnan(far) or not float(np.float32(far)) > 0:
-        raise RuntimeError("far must be a positive float32 (not NaN)")
-    return mesh_ids, labels, poses, h, w, far
+def _render(meshes, mesh_ids, labels, poses, K, h, w, far, out_depth, out_labels, workspace, return_visible, return_status):
+    """the checks and the calls of every function here; ``out_depth`` / ``out_labels``: ``(the caller's or None, its name)``, or None
+    for an image that is not written"""
+    mesh_ids, labels, poses, h, w, far = _mesh.check_scene(DeviceMeshes, meshes, mesh_ids, labels, poses, h, w, far, DEPTH_MAX_INSTANCES)
+    shape, dev = (int(poses.shape[0]), h, w), poses.device
+    depth = _mesh.check_out(out_depth[0], shape, torch.float32, dev, out_depth[1]) if out_depth else None
+    label = _mesh.check_out(out_labels[0], shape, torch.uint8, dev, out_labels[1]) if out_labels else None
+    return _mesh.compose(_DEPTH, meshes, mesh_ids, labels, poses, K, h, w, far, DEPTH_MAX_INSTANCES,
+                         lambda i0: (_mesh.at(depth, i0), _mesh.at(label, i0)), tuple(t for t in (depth, label) if t is not None),
+                         return_visible, return_status, workspace)
 
 
 def render_depth(meshes, mesh_ids, labels, poses, K, h, w, far=math.inf, out_depth=None, out_labels=None, workspace=None,
@@ -116,20 +65,8 @@ def render_depth(meshes, mesh_ids, labels, poses, K, h, w, far=math.inf, out_dep
     :return: ``(depth [b,h,w] float32, labels [b,h,w] uint8[, visible [b,m] int32][, status [b,m] int32])``: depth 0 and label 0 where
              nothing is kept; ``visible`` the pixels each instance wins; ``status`` its ``DEPTH_S_*`` bits
     """
-    mesh_ids, labels, poses, h, w, far = _checked(meshes, mesh_ids, labels, poses, h, w, far)
-    dev, b, m = poses.device, int(poses.shape[0]), int(poses.shape[1])
-    depth = _out(out_depth, (b, h, w), torch.float32, dev, "out_depth")
-    label = _out(out_labels, (b, h, w), torch.uint8, dev, "out_labels")
-    visible = torch.empty(b * m, dtype=torch.int32, device=dev) if return_visible else None
-    status = torch.empty(b * m, dtype=torch.int32, device=dev) if return_status else None
-    if b:
-        _render(meshes, mesh_ids, labels, poses, K, h, w, far, depth, label, visible, status, workspace)
-    res = (depth, label)
-    if return_visible:
-        res += (visible.view(b, m),)
-    if return_status:
-        res += (status.view(b, m),)
-    return res
+    return _render(meshes, mesh_ids, labels, poses, K, h, w, far, (out_depth, "out_depth"), (out_labels, "out_labels"), workspace,
+                   return_visible, return_status)
 
 
 def render_visible_labels(meshes, mesh_ids, labels, poses, K, h, w, far=math.inf, out=None, workspace=None, return_visible=False,
@@ -137,16 +74,8 @@ def render_visible_labels(meshes, mesh_ids, labels, poses, K, h, w, far=math.inf
     """The labels of ``render_depth`` alone (no depth image is written): the occlusion-correct counterpart of ``render.render_labels``.
 
     :return: ``labels [b,h,w]`` uint8; with ``return_visible`` / ``return_status`` a tuple with ``[b,m]`` int32 of each behind it"""
-    mesh_ids, labels, poses, h, w, far = _checked(meshes, mesh_ids, labels, poses, h, w, far)
-    dev, b, m = poses.device, int(poses.shape[0]), int(poses.shape[1])
-    label = _out(out, (b, h, w), torch.uint8, dev, "out")
-    visible = torch.empty(b * m, dtype=torch.int32, device=dev) if return_visible else None
-    status = torch.empty(b * m, dtype=torch.int32, device=dev) if return_status else None
-    if b:
-        _render(meshes, mesh_ids, labels, poses, K, h, w, far, None, label, visible, status, workspace)
-    if not (return_visible or return_status):
-        return label
-    return (label,) + ((visible.view(b, m),) if return_visible else ()) + ((status.view(b, m),) if return_status else ())
+    res = _render(meshes, mesh_ids, labels, poses, K, h, w, far, None, (out, "out"), workspace, return_visible, return_status)
+    return res if return_visible or return_status else res[0]
 
 
 def render_mesh_depth(RT, K, vert, face, h, w):
@@ -157,7 +86,5 @@ def render_mesh_depth(RT, K, vert, face, h, w):
     assert RT.shape == (3, 4) and K.shape == (3, 3)
     table = DeviceMeshes([(vert, face)])
     poses = torch.from_numpy(np.ascontiguousarray(RT)).to("cuda").view(1, 1, 3, 4)
-    mesh_ids, labels, poses, h, w, far = _checked(table, [0], [1], poses, h, w, math.inf)
-    depth = torch.empty((1, h, w), dtype=torch.float32, device=poses.device)
-    _render(table, mesh_ids, labels, poses, K, h, w, far, depth, None, None, None, None)   # the depth image alone
+    depth, = _render(table, [0], [1], poses, K, h, w, math.inf, (None, "out_depth"), None, None, False, False)   # the depth image alone
     return depth[0].cpu().numpy()

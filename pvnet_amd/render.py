@@ -25,6 +25,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _mesh
 from ._abi import (RASTER_MAX_IMAGES, RASTER_MAX_INSTANCES, RASTER_MAX_MESHES, RASTER_S_BADFACE, RASTER_S_BEHIND,  # noqa: F401
                    RASTER_S_NONFINITE, _check, load_raster_library)
 from ._marshal import nbytes as _nbytes, ptr as _ptr, stream as _stream, workspace as _workspace
@@ -120,6 +121,11 @@ class DeviceMeshes:
     def face_count(self, mesh_id):
         return int(self.face_offset[mesh_id + 1] - self.face_offset[mesh_id])
 
+    def table_arguments(self, dev):
+        """the seven arguments every ``pvnet_render*`` entry point opens with: vertices, faces, the two offset arrays, M, P, T"""
+        vertices, faces, _ = self.on(dev)
+        return _ptr(vertices), _ptr(faces), self._c_voff, self._c_foff, self.count, self.total_vertices, self.total_faces
+
     def on(self, dev):
         """(vertices, faces, centroids) on ``dev``, uploaded on first use"""
         dev = torch.device(dev)
@@ -131,20 +137,11 @@ class DeviceMeshes:
 
 def raster_workspace_bytes(q, h, w, meshes=None, b=None):
     """bytes of workspace for q instances of h x w pixels (``rasterize_triangles``: q = n images)"""
-    P, T = (meshes.total_vertices, meshes.total_faces) if meshes is not None else (0, 0)
-    n = int(load_raster_library().pvnet_raster_workspace_bytes(int(q), P, T, int(q if b is None else b), int(h), int(w)))
-    if n == 0:
-        raise RuntimeError(f"raster_workspace_bytes: arguments out of range (q={q}, h={h}, w={w}; h, w >= 2)")
-    return n
+    return _mesh.workspace_bytes("raster", q, q if b is None else b, h, w, meshes, told=f"q={q}, h={h}, w={w}")
 
 
 def _out(out, shape, dev):
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=dev)
-    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.uint8 and
-            tuple(out.shape) == tuple(shape) and out.is_contiguous()):
-        raise RuntimeError(f"out must be a contiguous uint8 CUDA tensor of shape {tuple(shape)} on {dev}")
-    return out
+    return _mesh.check_out(out, shape, torch.uint8, dev, "out", spelled="uint8")
 
 
 def rasterize_triangles(triangles_2d, h, w, out=None, workspace=None, return_status=False):
@@ -185,18 +182,9 @@ def mesh_binary_rasterization(triangles_2d, h, w):
     return rasterize_triangles(tri, h, w).cpu().numpy()
 
 
-def _device_f64(x, dev, what):
-    if isinstance(x, torch.Tensor):
-        if x.dtype != torch.float64:
-            raise RuntimeError(f"{what} must be float64")
-        return x.to(dev).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64))).to(dev)
-
-
 def _render(meshes, dev, mesh_ids, image_ids, labels, poses, K, k_per_instance, order, b, h, w, out, tri_out, status, workspace):
     """one pvnet_render call per stretch of at most RASTER_MAX_INSTANCES instances, cut at image boundaries; ``poses`` [q,3,4]"""
     lib = load_raster_library()
-    vertices, faces, _ = meshes.on(dev)
     q = len(mesh_ids)
     cuts, start = [], 0
     while start < q:   # stretches of whole images
@@ -216,49 +204,24 @@ def _render(meshes, dev, mesh_ids, image_ids, labels, poses, K, k_per_instance, 
             # the images of this stretch: from its first image (or 0) up to the next stretch's first image (or b)
             i0 = 0 if ci == 0 else image_ids[s]
             i1 = b if ci == len(cuts) - 1 else image_ids[e]
-            n = e - s
-            ws = _workspace(workspace, raster_workspace_bytes(n, h, w, meshes, i1 - i0) if h >= 2 and w >= 2 else 16, dev, align=16,
+            head = _mesh.argument_head(meshes, dev, mesh_ids[s:e], poses[s:], K[s:] if k_per_instance else K, k_per_instance,
+                                       [i - i0 for i in image_ids[s:e]], labels[s:e])
+            ws = _workspace(workspace, raster_workspace_bytes(e - s, h, w, meshes, i1 - i0) if h >= 2 and w >= 2 else 16, dev, align=16,
                             sized=True)
-            arr = lambda vals: (C.c_int32 * max(n, 1))(*vals)   # noqa: E731
-            ntri = sum(meshes.face_count(m) for m in mesh_ids[s:e])
-            _check(lib.pvnet_render(
-                _ptr(vertices), _ptr(faces), meshes._c_voff, meshes._c_foff, meshes.count, meshes.total_vertices, meshes.total_faces, n,
-                arr(mesh_ids[s:e]), _ptr(poses[s:]), _ptr(K[s:] if k_per_instance else K), 1 if k_per_instance else 0,
-                arr([i - i0 for i in image_ids[s:e]]), arr(labels[s:e]), _ptr(order[s:]) if order is not None else None, i1 - i0, h, w,
-                _ptr(out[i0:]) if out is not None else None, _ptr(tri_out[tri0:]) if tri_out is not None else None,
-                _ptr(status[s:]) if status is not None else None, _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_render")
-            tri0 += ntri
-
-
-def _poses(poses, dev, dims):
-    if not (isinstance(poses, torch.Tensor) and poses.is_cuda):
-        raise RuntimeError("poses must be a CUDA tensor (there is no CPU fallback)")
-    if poses.dtype != torch.float64 or poses.dim() != dims or tuple(poses.shape[-2:]) != (3, 4):
-        raise RuntimeError(f"poses must be float64 [{'b,m' if dims == 4 else 'n'},3,4], got {poses.dtype} {tuple(poses.shape)}")
-    return poses.contiguous()
-
-
-def _camera(K, dev, lead):
-    """-> (K on the device, per instance?) for K [3,3] or [*lead,3,3]"""
-    K = _device_f64(K, dev, "K")
-    if tuple(K.shape) == (3, 3):
-        return K, False
-    if tuple(K.shape) == tuple(lead) + (3, 3):
-        return K.reshape(-1, 3, 3), True
-    raise RuntimeError(f"K must be [3,3] or {tuple(lead) + (3, 3)}, got {tuple(K.shape)}")
+            _check(lib.pvnet_render(*head, _mesh.at(order, s), i1 - i0, h, w, _mesh.at(out, i0), _mesh.at(tri_out, tri0),
+                                    _mesh.at(status, s), _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_render")
+            tri0 += sum(meshes.face_count(m) for m in mesh_ids[s:e])
 
 
 def project_triangles(meshes, mesh_id, poses, K):
     """Stage P: the float32 triangles of mesh ``mesh_id`` under ``poses [n,3,4]`` (float64 CUDA) -> ``[n,tn,3,2]`` float32."""
-    if not isinstance(meshes, DeviceMeshes):
-        raise RuntimeError("meshes must be a DeviceMeshes")
+    _mesh.check_meshes(meshes, DeviceMeshes)
     mesh_id = int(mesh_id)
     if not 0 <= mesh_id < meshes.count:
         raise RuntimeError(f"mesh_id must lie in 0 .. {meshes.count - 1}")
-    dev = poses.device if isinstance(poses, torch.Tensor) else None
-    poses = _poses(poses, dev, 3)
-    n, tn = int(poses.shape[0]), meshes.face_count(mesh_id)
-    Kd, per = _camera(K, dev, (n,))
+    poses = _mesh.check_poses(poses, 3)
+    dev, n, tn = poses.device, int(poses.shape[0]), meshes.face_count(mesh_id)
+    Kd, per = _mesh.check_camera(K, dev, (n,))
     tri = torch.empty((n, tn, 3, 2), dtype=torch.float32, device=dev)
     if n and tn:
         _render(meshes, dev, [mesh_id] * n, list(range(n)), [1] * n, poses, Kd, per, None, n, 2, 2, None, tri.view(-1, 3, 2), None, None)
@@ -276,17 +239,15 @@ def render_masks(meshes, mesh_id, poses, K, h, w, out=None, workspace=None, retu
     :param workspace: None or a uint8 CUDA tensor of ``raster_workspace_bytes(n, h, w, meshes)`` bytes, 16-byte aligned
     :return: ``masks [n,h,w]`` uint8 (0 / 1); with ``return_status`` also ``[n]`` int32 of ``RASTER_S_*`` bits
     """
-    if not isinstance(meshes, DeviceMeshes):
-        raise RuntimeError("meshes must be a DeviceMeshes")
-    dev = poses.device if isinstance(poses, torch.Tensor) else None
-    poses = _poses(poses, dev, 3)
-    n, h, w = int(poses.shape[0]), int(h), int(w)
+    _mesh.check_meshes(meshes, DeviceMeshes)
+    poses = _mesh.check_poses(poses, 3)
+    dev, n, h, w = poses.device, int(poses.shape[0]), int(h), int(w)
     ids = [int(mesh_id)] * n if np.ndim(mesh_id) == 0 else [int(m) for m in mesh_id]
     if len(ids) != n or any(not 0 <= m < meshes.count for m in ids):
         raise RuntimeError(f"mesh_id: one id, or n={n} ids, in 0 .. {meshes.count - 1}")
     if h < 2 or w < 2:
         raise RuntimeError("h and w must be at least 2")
-    Kd, per = _camera(K, dev, (n,))
+    Kd, per = _mesh.check_camera(K, dev, (n,))
     out = _out(out, (n, h, w), dev)
     status = torch.empty(n, dtype=torch.int32, device=dev) if return_status else None
     if n:
@@ -305,21 +266,11 @@ def render_labels(meshes, mesh_ids, labels, poses, K, h, w, order=None, out=None
                      [m] for all images or [b,m] (a sequence, or an integer CUDA tensor)
     :return: ``labels [b,h,w]`` uint8; with ``return_status`` also ``[b,m]`` int32 of ``RASTER_S_*`` bits
     """
-    if not isinstance(meshes, DeviceMeshes):
-        raise RuntimeError("meshes must be a DeviceMeshes")
-    dev = poses.device if isinstance(poses, torch.Tensor) else None
-    poses = _poses(poses, dev, 4)
-    b, m, h, w = int(poses.shape[0]), int(poses.shape[1]), int(h), int(w)
-    mesh_ids, labels = [int(x) for x in mesh_ids], [int(x) for x in labels]
-    if len(mesh_ids) != m or len(labels) != m or any(not 0 <= x < meshes.count for x in mesh_ids):
-        raise RuntimeError(f"mesh_ids and labels must have m={m} entries, mesh ids in 0 .. {meshes.count - 1}")
-    if any(not 1 <= x <= 255 for x in labels):
-        raise RuntimeError("labels must lie in 1 .. 255")
-    if h < 2 or w < 2:
-        raise RuntimeError("h and w must be at least 2")
-    if m > RASTER_MAX_INSTANCES:
-        raise RuntimeError(f"at most {RASTER_MAX_INSTANCES} instances per image")
-    Kd, per = _camera(K, dev, (b, m))
+    _mesh.check_meshes(meshes, DeviceMeshes)
+    poses = _mesh.check_poses(poses, 4)
+    dev, b, m, h, w = poses.device, int(poses.shape[0]), int(poses.shape[1]), int(h), int(w)
+    mesh_ids, labels = _mesh.check_instances(meshes, mesh_ids, labels, m, h, w, RASTER_MAX_INSTANCES)
+    Kd, per = _mesh.check_camera(K, dev, (b, m))
     if order is None:
         cent = meshes.on(dev)[2][torch.as_tensor(mesh_ids, device=dev)] if m else torch.zeros((0, 3), dtype=torch.float64, device=dev)
         z = ((poses[:, :, 2, 0] * cent[:, 0] + poses[:, :, 2, 1] * cent[:, 1]) + poses[:, :, 2, 2] * cent[:, 2]) + poses[:, :, 2, 3]

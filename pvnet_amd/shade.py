@@ -21,20 +21,16 @@ in a graph.  PyTorch is plumbing only.  There is NO CPU fallback: without the li
 """
 from __future__ import annotations
 
-import collections
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
+from . import _mesh
 from ._abi import (SHADE_FLAT, SHADE_MAX_FACES, SHADE_MAX_INSTANCES, SHADE_NONE, SHADE_PHONG, SHADE_S_BADFACE,  # noqa: F401
-                   SHADE_S_BEHIND, SHADE_S_NONFINITE, _check, load_shade_library)
-from ._marshal import nbytes as _nbytes, ptr as _ptr, stream as _stream, workspace as _workspace
-from .depth import _checked, _image_stretches, _out   # the front end of the z-buffer: the same checks, the same split
-from .render import DeviceMeshes, _camera
-
-SHADING = {"none": SHADE_NONE, "flat": SHADE_FLAT, "phong": SHADE_PHONG}
+                   SHADE_S_BEHIND, SHADE_S_NONFINITE)
+from ._mesh import SHADING   # noqa: F401 (this module's name for it)
+from .render import DeviceMeshes
 
 
 def vertex_normals(vertices, faces):
@@ -102,11 +98,7 @@ class ColorMeshes(DeviceMeshes):
 
 def shade_workspace_bytes(q, b, h, w, meshes=None):
     """bytes of workspace for q instances composed into b images of h x w pixels"""
-    P, T = (meshes.total_vertices, meshes.total_faces) if meshes is not None else (0, 0)
-    n = int(load_shade_library().pvnet_shade_workspace_bytes(int(q), P, T, int(b), int(h), int(w)))
-    if n == 0:
-        raise RuntimeError(f"shade_workspace_bytes: arguments out of range (q={q}, b={b}, h={h}, w={w}; h, w >= 2)")
-    return n
+    return _mesh.workspace_bytes("shade", q, b, h, w, meshes)
 
 
 def render_color(meshes, mesh_ids, labels, poses, K, h, w, ambient=0.5, shading="flat", background=None, far=math.inf, out_rgb=None,
@@ -129,76 +121,12 @@ def render_color(meshes, mesh_ids, labels, poses, K, h, w, ambient=0.5, shading=
     :return: ``(rgb [b,h,w,3] uint8, depth [b,h,w] float32, labels [b,h,w] uint8[, visible [b,m] int32][, status [b,m] int32])``;
              depth, labels, visible and status are ``depth.render_depth``'s
     """
-    return _render(_SHADE, meshes, mesh_ids, labels, poses, K, h, w, ambient=ambient, shading=shading, background=background, far=far,
-                   out_rgb=out_rgb, out_depth=out_depth, out_labels=out_labels, workspace=workspace, return_visible=return_visible,
-                   return_status=return_status, max_instances=max_instances)
+    return _mesh.render_shaded(_SHADE, meshes, mesh_ids, labels, poses, K, h, w, ambient=ambient, shading=shading, background=background,
+                               far=far, out_rgb=out_rgb, out_depth=out_depth, out_labels=out_labels, workspace=workspace,
+                               return_visible=return_visible, return_status=return_status, max_instances=max_instances)
 
 
-# what tells render_color from texture.render_textured: the table they take, the limit, the workspace formula, the library, its entry point
-_FrontEnd = collections.namedtuple("_FrontEnd", "kind limit workspace_bytes load entry")
-_SHADE = _FrontEnd(ColorMeshes, SHADE_MAX_INSTANCES, shade_workspace_bytes, load_shade_library, "pvnet_render_color")
-
-
-def _render(front, meshes, mesh_ids, labels, poses, K, h, w, *, ambient, shading, background, far, out_rgb, out_depth, out_labels,
-            workspace, return_visible, return_status, max_instances, choice=None, extra=None):
-    """The body of ``render_color`` and of ``texture.render_textured``.  ``choice``: ``(name, value, allowed)`` of one more argument
-    that must be a key of ``allowed``, checked after ``shading``; ``extra(dev)``: the arguments the library takes between the normals
-    and the shading, as a tuple."""
-    kind, limit = front.kind, front.limit
-    if not isinstance(meshes, kind):
-        raise RuntimeError(f"meshes must be a {kind.__name__}")
-    max_instances = int(max_instances)
-    if not 1 <= max_instances <= limit:
-        raise RuntimeError(f"max_instances must lie in 1 .. {limit}")
-    mesh_ids, labels, poses, h, w, far = _checked(meshes, mesh_ids, labels, poses, h, w, far, max_instances)
-    if shading not in SHADING:
-        raise RuntimeError(f"shading must be one of {sorted(SHADING)}")
-    if choice is not None and choice[1] not in choice[2]:
-        raise RuntimeError(f"{choice[0]} must be one of {sorted(choice[2])}")
-    ambient = float(ambient)
-    if not (math.isfinite(ambient) and ambient >= 0):
-        raise RuntimeError("ambient must be finite and >= 0")
-    dev, b, m = poses.device, int(poses.shape[0]), int(poses.shape[1])
-    bg_image, bg_color = None, (0, 0, 0)
-    if isinstance(background, torch.Tensor):
-        bg_image = _out(background, (b, h, w, 3), torch.uint8, dev, "background")
-    elif background is not None:
-        bg_color = tuple(int(x) for x in background)
-        if len(bg_color) != 3 or any(not 0 <= x <= 255 for x in bg_color):
-            raise RuntimeError("background must be a colour triple in 0 .. 255 or a uint8 CUDA tensor [b,h,w,3]")
-    rgb = _out(out_rgb, (b, h, w, 3), torch.uint8, dev, "out_rgb")
-    depth = _out(out_depth, (b, h, w), torch.float32, dev, "out_depth")
-    label = _out(out_labels, (b, h, w), torch.uint8, dev, "out_labels")
-    visible = torch.empty(b * m, dtype=torch.int32, device=dev) if return_visible else None
-    status = torch.empty(b * m, dtype=torch.int32, device=dev) if return_status else None
-    if b:
-        entry = getattr(front.load(), front.entry)
-        between = extra(dev) if extra is not None else ()
-        Kd, per = _camera(K, dev, (b, m))
-        vertices, faces, _ = meshes.on(dev)
-        colors, normals = meshes.shading_on(dev)
-        flat = poses.view(-1, 3, 4)
-        c_bg = (C.c_uint8 * 3)(*bg_color)
-        with torch.cuda.device(dev):
-            for i0, i1 in _image_stretches(b, m, max_instances):
-                nb, n = i1 - i0, (i1 - i0) * m
-                s = i0 * m
-                ws = _workspace(workspace, front.workspace_bytes(n, nb, h, w, meshes), dev, align=16, sized=True)
-                arr = lambda vals: (C.c_int32 * max(n, 1))(*vals)   # noqa: E731
-                head = (_ptr(vertices), _ptr(faces), meshes._c_voff, meshes._c_foff, meshes.count, meshes.total_vertices,
-                        meshes.total_faces, n, arr(mesh_ids * nb), _ptr(flat[s:]) if n else None, _ptr(Kd[s:] if per else Kd),
-                        1 if per else 0, arr([i for i in range(nb) for _ in range(m)]), arr(labels * nb), nb, h, w, far, _ptr(colors),
-                        _ptr(normals) if shading == "phong" else None)
-                tail = (SHADING[shading], ambient, c_bg, _ptr(bg_image[i0:]) if bg_image is not None else None, _ptr(rgb[i0:]),
-                        _ptr(depth[i0:]), _ptr(label[i0:]), _ptr(visible[s:]) if visible is not None and n else None,
-                        _ptr(status[s:]) if status is not None and n else None, _ptr(ws), _nbytes(ws), _stream(dev))
-                _check(entry(*head, *between, *tail), front.entry)
-    res = (rgb, depth, label)
-    if return_visible:
-        res += (visible.view(b, m),)
-    if return_status:
-        res += (status.view(b, m),)
-    return res
+_SHADE = _mesh.Front("shade", ColorMeshes, SHADE_MAX_INSTANCES, "pvnet_render_color")
 
 
 # ---- PLY -------------------------------------------------------------------------------------------------------------------------------
@@ -210,10 +138,10 @@ def read_ply(path):
     """An ASCII or binary_little_endian PLY file -> ``{"vertices": [P,3] float64, "faces": [T,3] int32, "normals": [P,3] float64 or
     None, "colors": [P,3] uint8 or None}``.  Reads the vertex properties ``x y z``, ``nx ny nz`` and ``red green blue`` (others are
     skipped) and the face element's list property (``vertex_indices`` / ``vertex_index``), whose lists must all have three entries."""
-    return _read_ply(path)[0]
+    return parse_ply(path)[0]
 
 
-def _read_ply(path):
+def parse_ply(path):
     """(what ``read_ply`` returns, ``cols``: (property names, dtype) -> those vertex properties as columns, or None when one is missing):
     the parser behind ``read_ply`` and ``texture.read_textured_ply``"""
     with open(path, "rb") as fh:

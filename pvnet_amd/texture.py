@@ -26,9 +26,10 @@ import math
 import numpy as np
 import torch
 
-from ._abi import TEXTURE_BILINEAR, TEXTURE_MAX_INSTANCES, TEXTURE_MAX_SIDE, TEXTURE_NEAREST, load_texture_library
+from . import _mesh
+from ._abi import TEXTURE_BILINEAR, TEXTURE_MAX_INSTANCES, TEXTURE_MAX_SIDE, TEXTURE_NEAREST
 from ._marshal import ptr as _ptr
-from .shade import SHADING, ColorMeshes, _FrontEnd, _read_ply, _render   # noqa: F401 (SHADING: this module's name for it too)
+from .shade import SHADING, ColorMeshes, parse_ply   # noqa: F401 (SHADING: this module's name for it too)
 
 FILTER = {"nearest": TEXTURE_NEAREST, "bilinear": TEXTURE_BILINEAR}
 
@@ -116,11 +117,7 @@ class TexturedMeshes(ColorMeshes):
 
 def texture_workspace_bytes(q, b, h, w, meshes=None):
     """bytes of workspace for q instances composed into b images of h x w pixels: ``shade.shade_workspace_bytes``'s"""
-    P, T = (meshes.total_vertices, meshes.total_faces) if meshes is not None else (0, 0)
-    n = int(load_texture_library().pvnet_texture_workspace_bytes(int(q), P, T, int(b), int(h), int(w)))
-    if n == 0:
-        raise RuntimeError(f"texture_workspace_bytes: arguments out of range (q={q}, b={b}, h={h}, w={w}; h, w >= 2)")
-    return n
+    return _mesh.workspace_bytes("texture", q, b, h, w, meshes)
 
 
 def render_textured(meshes, mesh_ids, labels, poses, K, h, w, ambient=0.5, shading="flat", filter="nearest", background=None,  # noqa: A002
@@ -139,12 +136,13 @@ def render_textured(meshes, mesh_ids, labels, poses, K, h, w, ambient=0.5, shadi
         uv, texels = meshes.textures_on(dev)
         return _ptr(uv), _ptr(texels), meshes._c_toff, meshes._c_th, meshes._c_tw, FILTER[filter]
 
-    return _render(_TEXTURE, meshes, mesh_ids, labels, poses, K, h, w, ambient=ambient, shading=shading, background=background, far=far,
-                   out_rgb=out_rgb, out_depth=out_depth, out_labels=out_labels, workspace=workspace, return_visible=return_visible,
-                   return_status=return_status, max_instances=max_instances, choice=("filter", filter, FILTER), extra=extra)
+    return _mesh.render_shaded(_TEXTURE, meshes, mesh_ids, labels, poses, K, h, w, ambient=ambient, shading=shading, background=background,
+                               far=far, out_rgb=out_rgb, out_depth=out_depth, out_labels=out_labels, workspace=workspace,
+                               return_visible=return_visible, return_status=return_status, max_instances=max_instances,
+                               choice=("filter", filter, FILTER), extra=extra)
 
 
-_TEXTURE = _FrontEnd(TexturedMeshes, TEXTURE_MAX_INSTANCES, texture_workspace_bytes, load_texture_library, "pvnet_render_textured")
+_TEXTURE = _mesh.Front("texture", TexturedMeshes, TEXTURE_MAX_INSTANCES, "pvnet_render_textured")
 
 _UV_SPELLINGS = (("texture_u", "texture_v"), ("u", "v"), ("s", "t"))
 
@@ -154,7 +152,7 @@ def read_textured_ply(path):
     properties ``texture_u texture_v`` (what the reference's ``OpenGLRenderer.load_ply`` reads) or, failing those, ``u v`` or ``s t``.
     The texture image itself is a file of its own; load it with any image reader and hand it to ``TexturedMeshes`` as it was loaded.
     OBJ files, and PLY files whose faces carry per-corner ``texcoord`` lists or ``vt`` indices, are out of scope: one vertex, one uv."""
-    out, cols = _read_ply(path)
+    out, cols = parse_ply(path)
     out["uv"] = None
     for names in _UV_SPELLINGS:
         uv = cols(names, np.float32)

@@ -16,22 +16,12 @@ import pytest
 from pvnet_amd import _abi, build, render
 from tests import depth_restatement as DR
 from tests import raster_restatement as RS
+from tests.render_cases import BADARG, camera, i32, refuses_the_pvnet_render_list, rotation
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "pvnet_depth.h")).read()
-BADARG, WORKSPACE, UNSUPPORTED = -1, -2, -3
 EXPORTS = {"pvnet_depth_abi_version", "pvnet_depth_workspace_bytes", "pvnet_render_depth"}
 H, W = 48, 64
-
-
-def rotation(axis, angle):
-    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
-
-
-def camera(h, w):   # the camera of tests/golden/make_raster_golden.py
-    return np.array([[0.95 * w, 0.0, w / 2.0 + 0.37], [0.0, 0.97 * w, h / 2.0 - 0.21], [0.0, 0.0, 1.0]])
 
 
 @pytest.fixture(scope="module")
@@ -102,7 +92,6 @@ def test_workspace_bytes_is_monotone_and_rejects_bad_sizes(lib):
 
 def test_bad_arguments_are_rejected_without_a_device(lib):
     p = C.c_void_p(0x1000)   # never dereferenced: validation returns before any HIP call
-    i32 = lambda *v: (C.c_int32 * len(v))(*v)   # noqa: E731
     voff, foff = i32(0, 12, 20), i32(0, 20, 32)
     ws_n = lib.pvnet_depth_workspace_bytes(3, 20, 32, 2, 20, 24)
 
@@ -116,21 +105,7 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
         assert call(far=far) == BADARG, far
     assert call(depth=None, labels=None) == BADARG                 # no image output
     assert call(depth=None, labels=None, visible=p, status=p) == BADARG
-    # the pvnet_render list
-    assert call(h=1) == BADARG and call(w=1) == BADARG
-    for name in ("vertices", "faces", "voff", "foff", "mesh", "poses", "K", "image", "label", "ws"):
-        assert call(**{name: None}) == BADARG, name
-    assert call(image=i32(0, 1, 0)) == BADARG                      # decreasing image_id
-    assert call(image=i32(0, 1, 2)) == BADARG and call(image=i32(-1, 0, 1)) == BADARG   # outside 0 .. b-1
-    assert call(label=i32(1, 0, 3)) == BADARG and call(label=i32(1, 256, 3)) == BADARG and call(label=i32(-1, 2, 3)) == BADARG
-    assert call(mesh=i32(0, 2, 1)) == BADARG and call(mesh=i32(0, -1, 1)) == BADARG     # mesh_id out of range
-    assert call(voff=i32(1, 12, 20)) == BADARG and call(voff=i32(0, 12, 19)) == BADARG and call(foff=i32(0, 40, 32)) == BADARG
-    assert call(M=0) == BADARG and call(q=-1) == BADARG and call(b=-1) == BADARG
-    assert call(ws=C.c_void_p(0x1004)) == BADARG
-    assert call(nbytes=ws_n - 1) == WORKSPACE and call(nbytes=0) == WORKSPACE
-    assert call(M=_abi.DEPTH_MAX_MESHES + 1) == UNSUPPORTED and call(q=_abi.DEPTH_MAX_INSTANCES + 1) == UNSUPPORTED
-    assert call(w=_abi.DEPTH_MAX_SIDE + 1) == UNSUPPORTED and call(b=_abi.DEPTH_MAX_IMAGES + 1) == UNSUPPORTED
-    assert call(b=0, q=0) == 0                                      # nothing to do, nothing enqueued
+    refuses_the_pvnet_render_list(call, ws_n, _abi.DEPTH_MAX_MESHES, _abi.DEPTH_MAX_INSTANCES, _abi.DEPTH_MAX_SIDE, _abi.DEPTH_MAX_IMAGES)
 
 
 def test_assembly_one_atomic_minimum_nothing_contracted_and_the_register_rule():

@@ -16,10 +16,10 @@ import pytest
 
 from pvnet_amd import _abi, build
 from tests import raster_restatement as RS
+from tests.render_cases import BADARG, UNSUPPORTED, WORKSPACE, i32, refuses_the_pvnet_render_list
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "pvnet_raster.h")).read()
-BADARG, WORKSPACE, UNSUPPORTED = -1, -2, -3
 EXPORTS = {"pvnet_raster_abi_version", "pvnet_raster_workspace_bytes", "pvnet_raster_triangles", "pvnet_render"}
 
 
@@ -153,7 +153,6 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
     assert tri(n=_abi.RASTER_MAX_IMAGES + 1) == UNSUPPORTED and tri(h=_abi.RASTER_MAX_SIDE + 1) == UNSUPPORTED
     assert tri(n=0) == 0                                              # nothing to do, nothing enqueued
 
-    i32 = lambda *v: (C.c_int32 * len(v))(*v)   # noqa: E731
     voff, foff = i32(0, 12, 20), i32(0, 20, 32)
     ws_r = lib.pvnet_raster_workspace_bytes(3, 20, 32, 2, 20, 24)
 
@@ -162,21 +161,9 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
         return lib.pvnet_render(vertices, faces, voff, foff, M, P, T, q, mesh, poses, K, kper, image, label, order, b, h, w, out, tri_out,
                                 status, ws, nbytes, None)
 
-    assert render(h=1) == BADARG and render(w=1) == BADARG
-    for name in ("vertices", "faces", "voff", "foff", "mesh", "poses", "K", "image", "label", "ws"):
-        assert render(**{name: None}) == BADARG, name
     assert render(out=None) == BADARG                                # neither an image nor triangles asked for
-    assert render(image=i32(0, 1, 0)) == BADARG                      # decreasing image_id
-    assert render(image=i32(0, 1, 2)) == BADARG and render(image=i32(-1, 0, 1)) == BADARG   # outside 0 .. b-1
-    assert render(label=i32(1, 0, 3)) == BADARG and render(label=i32(1, 256, 3)) == BADARG and render(label=i32(-1, 2, 3)) == BADARG
-    assert render(mesh=i32(0, 2, 1)) == BADARG and render(mesh=i32(0, -1, 1)) == BADARG     # mesh_id out of range
-    assert render(voff=i32(1, 12, 20)) == BADARG and render(voff=i32(0, 12, 19)) == BADARG and render(foff=i32(0, 40, 32)) == BADARG
-    assert render(M=0) == BADARG and render(q=-1) == BADARG and render(b=-1) == BADARG
-    assert render(ws=C.c_void_p(0x1004)) == BADARG
-    assert render(nbytes=ws_r - 1) == WORKSPACE
-    assert render(M=_abi.RASTER_MAX_MESHES + 1) == UNSUPPORTED and render(q=_abi.RASTER_MAX_INSTANCES + 1) == UNSUPPORTED
-    assert render(w=_abi.RASTER_MAX_SIDE + 1) == UNSUPPORTED
-    assert render(b=0, q=0) == 0
+    refuses_the_pvnet_render_list(render, ws_r, _abi.RASTER_MAX_MESHES, _abi.RASTER_MAX_INSTANCES, _abi.RASTER_MAX_SIDE,
+                                  _abi.RASTER_MAX_IMAGES)
 
 
 def test_register_rule_and_no_fused_float32_arithmetic():

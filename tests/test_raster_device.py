@@ -13,38 +13,12 @@ import torch
 
 from pvnet_amd import _abi, render, synth
 from tests import raster_restatement as RS
+from tests.render_cases import camera, coop_count, cuda, dev, pose
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = np.load(os.path.join(ROOT, "tests", "golden", "raster.npz"))
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def cuda(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev())
-
-
-def rotation(axis, angle):
-    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
-
-
-def pose(axis, angle, t):
-    return np.concatenate([rotation(axis, angle), np.asarray(t, np.float64).reshape(3, 1)], 1)
-
-
-def camera(h, w):
-    return np.array([[0.95 * w, 0.0, w / 2.0 + 0.37], [0.0, 0.97 * w, h / 2.0 - 0.21], [0.0, 0.0, 1.0]])
-
-
-def coop_count(workspace):
-    """the triangles of the last call on this workspace that took the cooperative path (PVNET_RASTER_WS_COOP_COUNT_OFFSET = 0)"""
-    return int(workspace[:4].view(torch.int32).cpu()[0])
 
 
 def restated(tri, h, w):

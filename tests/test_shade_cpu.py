@@ -16,34 +16,12 @@ import pytest
 from pvnet_amd import _abi, build, render, shade
 from tests import depth_restatement as DR
 from tests import shade_restatement as SR
+from tests.render_cases import BADARG, UNSUPPORTED, camera, i32, pose, refuses_the_pvnet_render_list, smooth_colors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "pvnet_shade.h")).read()
-BADARG, WORKSPACE, UNSUPPORTED = -1, -2, -3
 EXPORTS = {"pvnet_shade_abi_version", "pvnet_shade_workspace_bytes", "pvnet_render_color"}
 H, W = 48, 64
-
-
-def rotation(axis, angle):
-    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
-
-
-def pose(axis, angle, t):
-    return np.concatenate([rotation(axis, angle), np.asarray(t, np.float64).reshape(3, 1)], 1)
-
-
-def camera(h, w):   # the camera of tests/golden/make_raster_golden.py
-    return np.array([[0.95 * w, 0.0, w / 2.0 + 0.37], [0.0, 0.97 * w, h / 2.0 - 0.21], [0.0, 0.0, 1.0]])
-
-
-def smooth_colors(vertices):
-    """vertex colours that are a smooth function of the position: 40 .. 215 in every channel"""
-    v = np.asarray(vertices, np.float64)
-    s = v / np.abs(v).max()
-    c = 127.5 + 87.5 * np.stack([np.sin(2.1 * s[:, 0] + 0.3), np.sin(1.7 * s[:, 1] - 0.8), np.cos(2.4 * s[:, 2] + 0.5)], 1)
-    return np.round(c).astype(np.uint8)
 
 
 @pytest.fixture(scope="module")
@@ -132,7 +110,6 @@ def test_workspace_bytes_is_monotone_and_rejects_bad_sizes(lib):
 
 def test_bad_arguments_are_rejected_without_a_device(lib):
     p = C.c_void_p(0x1000)   # never dereferenced: validation returns before any HIP call
-    i32 = lambda *v: (C.c_int32 * len(v))(*v)   # noqa: E731
     voff, foff = i32(0, 12, 20), i32(0, 20, 32)
     ws_n = lib.pvnet_shade_workspace_bytes(3, 20, 32, 2, 20, 24)
     black = (C.c_uint8 * 3)(0, 0, 0)
@@ -154,19 +131,7 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
     # the depth library's list
     for far in (0.0, -0.0, -1.0, float("-inf"), float("nan")):
         assert call(far=far) == BADARG, far
-    assert call(h=1) == BADARG and call(w=1) == BADARG
-    for name in ("vertices", "faces", "voff", "foff", "mesh", "poses", "K", "image", "label", "ws"):
-        assert call(**{name: None}) == BADARG, name
-    assert call(image=i32(0, 1, 0)) == BADARG                      # decreasing image_id
-    assert call(image=i32(0, 1, 2)) == BADARG and call(image=i32(-1, 0, 1)) == BADARG   # outside 0 .. b-1
-    assert call(label=i32(1, 0, 3)) == BADARG and call(label=i32(1, 256, 3)) == BADARG and call(label=i32(-1, 2, 3)) == BADARG
-    assert call(mesh=i32(0, 2, 1)) == BADARG and call(mesh=i32(0, -1, 1)) == BADARG     # mesh_id out of range
-    assert call(voff=i32(1, 12, 20)) == BADARG and call(voff=i32(0, 12, 19)) == BADARG and call(foff=i32(0, 40, 32)) == BADARG
-    assert call(M=0) == BADARG and call(q=-1) == BADARG and call(b=-1) == BADARG
-    assert call(ws=C.c_void_p(0x1004)) == BADARG
-    assert call(nbytes=ws_n - 1) == WORKSPACE and call(nbytes=0) == WORKSPACE
-    assert call(M=_abi.SHADE_MAX_MESHES + 1) == UNSUPPORTED and call(q=_abi.SHADE_MAX_INSTANCES + 1) == UNSUPPORTED
-    assert call(w=_abi.SHADE_MAX_SIDE + 1) == UNSUPPORTED and call(b=_abi.SHADE_MAX_IMAGES + 1) == UNSUPPORTED
+    refuses_the_pvnet_render_list(call, ws_n, _abi.SHADE_MAX_MESHES, _abi.SHADE_MAX_INSTANCES, _abi.SHADE_MAX_SIDE, _abi.SHADE_MAX_IMAGES)
     big = _abi.SHADE_MAX_FACES + 1   # a mesh with more faces than the word's 22 bits name
     assert call(M=1, voff=i32(0, 20), foff=i32(0, big), T=big, mesh=i32(0, 0, 0)) == UNSUPPORTED
     # the all-good call would reach the device: everything optional absent, b == 0 enqueues nothing

@@ -13,40 +13,12 @@ import torch
 
 from pvnet_amd import _abi, depth, render, shade
 from tests import shade_restatement as SR
+from tests.render_cases import camera, coop_count, cuda, dev, pose, smooth_colors
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(48, 64), (60, 80)]
 BG = (12, 200, 77)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def cuda(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev())
-
-
-def rotation(axis, angle):
-    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
-
-
-def pose(axis, angle, t):
-    return np.concatenate([rotation(axis, angle), np.asarray(t, np.float64).reshape(3, 1)], 1)
-
-
-def camera(h, w):
-    return np.array([[0.95 * w, 0.0, w / 2.0 + 0.37], [0.0, 0.97 * w, h / 2.0 - 0.21], [0.0, 0.0, 1.0]])
-
-
-def smooth_colors(vertices, phase=0.0):
-    v = np.asarray(vertices, np.float64)
-    s = v / np.abs(v).max()
-    c = 127.5 + 87.5 * np.stack([np.sin(2.1 * s[:, 0] + 0.3 + phase), np.sin(1.7 * s[:, 1] - 0.8 + phase), np.cos(2.4 * s[:, 2] + 0.5)], 1)
-    return np.round(c).astype(np.uint8)
 
 
 def table_of(meshes):
@@ -92,11 +64,6 @@ def same(got, want):
 
 def full(table, mesh_ids, labels, poses, K, h, w, **kw):
     return shade.render_color(table, mesh_ids, labels, cuda(poses), K, h, w, return_visible=True, return_status=True, **kw)
-
-
-def coop_count(workspace):
-    """the triangles of the last call on this workspace that took the cooperative path (PVNET_SHADE_WS_COOP_COUNT_OFFSET = 0)"""
-    return int(workspace[:4].view(torch.int32).cpu()[0])
 
 
 @pytest.mark.parametrize("shading", ["none", "flat", "phong"])

@@ -17,12 +17,13 @@ import pytest
 from pvnet_amd import _abi, build, render, shade, texture
 from tests import depth_restatement as DR
 from tests import shade_restatement as SR
-from tests import test_shade_cpu as TS   # its fixtures' helpers: poses, cameras, smooth colours, the ray caster
+from tests import test_shade_cpu as TS   # its oracle: the scenes, the ray caster, the GLSL shading; its PLY writer
 from tests import texture_restatement as TR
+from tests.render_cases import (BADARG, UNSUPPORTED, WORKSPACE, camera, i32, pose, refuses_the_pvnet_render_list, smooth_colors,
+                                smooth_texture, spherical_uv)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "pvnet_texture.h")).read()
-BADARG, WORKSPACE, UNSUPPORTED = -1, -2, -3
 EXPORTS = {"pvnet_texture_abi_version", "pvnet_texture_workspace_bytes", "pvnet_render_textured"}
 KERNELS = (b"texture_setup_kernel", b"texture_clear_kernel", b"texture_tri_kernel", b"texture_resolve_kernel")
 H, W = 48, 64
@@ -232,7 +233,6 @@ def test_workspace_bytes_is_the_shade_librarys(lib):
 
 def test_bad_arguments_are_rejected_without_a_device(lib):
     p = C.c_void_p(0x1000)   # never dereferenced: validation returns before any HIP call
-    i32 = lambda *v: (C.c_int32 * len(v))(*v)   # noqa: E731
     i64 = lambda *v: (C.c_int64 * len(v))(*v)   # noqa: E731
     voff, foff = i32(0, 12, 20), i32(0, 20, 32)
     ws_n = lib.pvnet_texture_workspace_bytes(3, 20, 32, 2, 20, 24)
@@ -288,34 +288,18 @@ def test_bad_arguments_are_rejected_without_a_device(lib):
     assert call(shading=2) == BADARG   # Phong without normals
     for far in (0.0, -1.0, float("nan")):
         assert call(far=far) == BADARG, far
-    assert call(h=1) == BADARG and call(w=1) == BADARG
-    for name in ("vertices", "faces", "voff", "foff", "mesh", "poses", "K", "image", "label", "ws"):
-        assert call(**{name: None}) == BADARG, name
-    assert call(image=i32(0, 1, 0)) == BADARG and call(image=i32(0, 1, 2)) == BADARG
-    assert call(label=i32(1, 0, 3)) == BADARG and call(label=i32(1, 256, 3)) == BADARG
-    assert call(mesh=i32(0, 2, 1)) == BADARG and call(mesh=i32(0, -1, 1)) == BADARG
-    assert call(voff=i32(1, 12, 20)) == BADARG and call(foff=i32(0, 40, 32)) == BADARG
-    assert call(M=0) == BADARG and call(q=-1) == BADARG and call(b=-1) == BADARG
-    assert call(ws=C.c_void_p(0x1004)) == BADARG
-    assert call(nbytes=ws_n - 1) == WORKSPACE and call(nbytes=0) == WORKSPACE
-    assert call(M=_abi.TEXTURE_MAX_MESHES + 1) == UNSUPPORTED and call(q=_abi.TEXTURE_MAX_INSTANCES + 1) == UNSUPPORTED
-    assert call(w=_abi.TEXTURE_MAX_IMAGE_SIDE + 1) == UNSUPPORTED and call(b=_abi.TEXTURE_MAX_IMAGES + 1) == UNSUPPORTED
+    refuses_the_pvnet_render_list(call, ws_n, _abi.TEXTURE_MAX_MESHES, _abi.TEXTURE_MAX_INSTANCES, _abi.TEXTURE_MAX_IMAGE_SIDE,
+                                  _abi.TEXTURE_MAX_IMAGES)
     big = _abi.TEXTURE_MAX_FACES + 1
     assert call(M=1, voff=i32(0, 20), foff=i32(0, big), T=big, mesh=i32(0, 0, 0), toff=i64(0, 15)) == UNSUPPORTED
 
 
 # ---- 6. TexturedMeshes -------------------------------------------------------------------------------------------------------------------
-def spherical_uv(vertices):
-    n = np.asarray(vertices, np.float64)
-    n = n / np.linalg.norm(n, axis=1, keepdims=True)
-    return np.stack([np.arctan2(n[:, 1], n[:, 0]) / (2 * np.pi) + 0.5, np.arccos(np.clip(n[:, 2], -1, 1)) / np.pi], 1)
-
-
 def test_textured_meshes_validation_and_packing():
     rng = np.random.default_rng(6)
     v, f = render.icosphere(1, 0.1)
     P = len(v)
-    col, uv = TS.smooth_colors(v), spherical_uv(v)
+    col, uv = smooth_colors(v), spherical_uv(v)
     rgb = rng.integers(0, 256, (5, 3, 3), dtype=np.uint8)
     rgba = np.concatenate([rgb, rng.integers(0, 256, (5, 3, 1), dtype=np.uint8)], 2)
     assert np.array_equal(texture.pack_texels(rgb), texture.pack_texels(rgba)) and texture.pack_texels(rgb).dtype == np.uint32
@@ -385,7 +369,7 @@ def write_ply(path, v, f, binary, uv=None, names=("texture_u", "texture_v"), col
 @pytest.mark.parametrize("binary", [False, True])
 def test_read_textured_ply_round_trips(tmp_path, binary):
     v, f = render.icosphere(1, 0.1)
-    v32, col = v.astype(np.float32), TS.smooth_colors(v)
+    v32, col = v.astype(np.float32), smooth_colors(v)
     uv = spherical_uv(v).astype(np.float32)
     for names in (("texture_u", "texture_v"), ("u", "v"), ("s", "t")):
         path = str(tmp_path / ("%s.ply" % names[0]))
@@ -463,7 +447,7 @@ def test_known_answer_every_texel_is_a_four_by_four_block():
 def test_perspective_and_affine_interpolation_differ_on_a_turned_quad():
     checker = np.zeros((16, 16, 3), np.uint8)
     checker[(np.add.outer(np.arange(16), np.arange(16)) % 2) == 0] = (250, 240, 230)
-    p = TS.pose((0, 1, 0), np.pi / 3, (0.0, 0.0, 0.6))   # the quad about its own centre: its near edge at z = 0.38, its far one at 0.82
+    p = pose((0, 1, 0), np.pi / 3, (0.0, 0.0, 0.6))   # the quad about its own centre: its near edge at z = 0.38, its far one at 0.82
     centred = (QUAD_V - (0.0, 0.0, 1.0),) + quad_mesh(checker)[1:]
     inst = [(0, p, QUAD_K, 0, 1)]
     layers = {}
@@ -481,14 +465,6 @@ def test_perspective_and_affine_interpolation_differ_on_a_turned_quad():
 
 
 # ---- 10. the independent ray caster ------------------------------------------------------------------------------------------------------
-def smooth_texture(n=64):
-    """a sum of sines in 40 .. 215 per channel, as tests/test_shade_cpu.py's smooth_colors builds its colours"""
-    y, x = np.mgrid[0:n, 0:n] / float(n)
-    c = 127.5 + 43.75 * np.stack([np.sin(2 * np.pi * x + 0.3) + np.sin(2 * np.pi * y - 0.8), np.sin(4 * np.pi * x - 0.8) + np.cos(2 * np.pi * y),
-                                  np.cos(2 * np.pi * (x + y) + 0.5) + np.sin(2 * np.pi * y + 1.1)], -1)
-    return np.round(c).astype(np.uint8)
-
-
 def atlas_box(sx, sy, sz):
     """render.box_mesh with four vertices of its own per side and a cell of a 3 x 2 atlas per side (inset by 1/16 of a cell): the same
     twelve triangles in the same order, so coverage and face indices are box_mesh's"""
@@ -595,7 +571,7 @@ def test_restatement_against_the_ray_caster(textured_oracle, name, shading):
 
 # ---- 11. against the depth and shade restatements ----------------------------------------------------------------------------------------
 def test_restated_geometry_is_the_depth_restatements_and_untextured_colour_the_shade_restatements():
-    K = TS.camera(H, W)
+    K = camera(H, W)
     rng = np.random.default_rng(20261019)
     tex = rng.integers(0, 256, (5, 3, 3), dtype=np.uint8)
     plain = TS.MESHES   # (vertices, faces, colours, normals)
@@ -607,9 +583,9 @@ def test_restated_geometry_is_the_depth_restatements_and_untextured_colour_the_s
         for img in range(2):
             for m in rng.choice(4, 3, replace=False):
                 t = (rng.uniform(-0.08, 0.08), rng.uniform(-0.05, 0.05), rng.uniform(0.4, 0.7))
-                inst.append((int(m), TS.pose(rng.normal(size=3), rng.uniform(0, np.pi), t), K, img, int(rng.integers(1, 256))))
+                inst.append((int(m), pose(rng.normal(size=3), rng.uniform(0, np.pi), t), K, img, int(rng.integers(1, 256))))
         scenes.append(inst)
-    p = TS.pose((1, 2, 3), 0.7, (0.02, -0.01, 0.5))
+    p = pose((1, 2, 3), 0.7, (0.02, -0.01, 0.5))
     scenes.append([(1, p, K, 0, 3), (0, p.copy(), K, 0, 7)])
     for inst in scenes:
         layers = {}

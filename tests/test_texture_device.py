@@ -12,32 +12,19 @@ import pytest
 import torch
 
 from pvnet_amd import _abi, depth, render, shade, texture
-from tests import test_shade_device as SD   # its helpers: poses, cameras, colours, backgrounds
+from tests import test_shade_device as SD   # its fixtures: the crossing bars, backgrounds, the comparison
 from tests import texture_restatement as TR
+from tests.render_cases import camera, coop_count, cuda, dev, pose, smooth_colors, smooth_texture, spherical_uv
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(48, 64), (60, 80)]
 BG = (12, 200, 77)
 FILTERS = ("nearest", "bilinear")
-pose, camera, cuda, dev = SD.pose, SD.camera, SD.cuda, SD.dev
 
 
 def random_texture(th, tw, seed=0, channels=3):
     return np.random.default_rng(1000 * th + tw + seed).integers(0, 256, (th, tw, channels), dtype=np.uint8)
-
-
-def smooth_texture(n=64):
-    y, x = np.mgrid[0:n, 0:n] / float(n)
-    c = 127.5 + 43.75 * np.stack([np.sin(2 * np.pi * x + 0.3) + np.sin(2 * np.pi * y - 0.8), np.sin(4 * np.pi * x - 0.8) + np.cos(2 * np.pi * y),
-                                  np.cos(2 * np.pi * (x + y) + 0.5) + np.sin(2 * np.pi * y + 1.1)], -1)
-    return np.round(c).astype(np.uint8)
-
-
-def spherical_uv(vertices):
-    n = np.asarray(vertices, np.float64)
-    n = n / np.linalg.norm(n, axis=1, keepdims=True)
-    return np.stack([np.arctan2(n[:, 1], n[:, 0]) / (2 * np.pi) + 0.5, np.arccos(np.clip(n[:, 2], -1, 1)) / np.pi], 1)
 
 
 def box_uv(vertices):
@@ -57,8 +44,8 @@ def crossing_bars():
     textured (64 x 64, smooth): textured and untextured instances interpenetrate in one image"""
     _, ids, labels, poses = SD.crossing_bars()
     bar, ball = render.box_mesh(0.25, 0.06, 0.05), render.icosphere(2, 0.04)
-    meshes = [(*bar, None, None, box_uv(bar[0]), random_texture(16, 16)), (*bar, SD.smooth_colors(bar[0]), None, None, None),
-              (*ball, SD.smooth_colors(ball[0], 1.0), None, spherical_uv(ball[0]), smooth_texture())]
+    meshes = [(*bar, None, None, box_uv(bar[0]), random_texture(16, 16)), (*bar, smooth_colors(bar[0]), None, None, None),
+              (*ball, smooth_colors(ball[0], 1.0), None, spherical_uv(ball[0]), smooth_texture())]
     assert ids == [0, 0, 1]
     return meshes, [0, 1, 2], labels, poses
 
@@ -76,11 +63,6 @@ same = SD.same
 
 def full(table, mesh_ids, labels, poses, K, h, w, **kw):
     return texture.render_textured(table, mesh_ids, labels, cuda(poses), K, h, w, return_visible=True, return_status=True, **kw)
-
-
-def coop_count(workspace):
-    """PVNET_TEXTURE_WS_COOP_COUNT_OFFSET = 0"""
-    return int(workspace[:4].view(torch.int32).cpu()[0])
 
 
 # ---- 1. filters and shadings -------------------------------------------------------------------------------------------------------------
@@ -119,7 +101,7 @@ def test_untextured_meshes_come_out_as_from_the_shade_library(size):
     K = camera(h, w)
     cmeshes, ids, labels, poses = SD.crossing_bars()
     near = render.box_mesh(0.3, 0.2, 0.2)
-    cmeshes = cmeshes + [(*near, SD.smooth_colors(near[0], 2.0))]
+    cmeshes = cmeshes + [(*near, smooth_colors(near[0], 2.0))]
     ids, labels = ids + [2], labels + [4]
     poses = np.concatenate([poses, np.stack([pose((2, 1, -1), 0.8, (0.18, 0.02, 0.62)), pose((2, 1, -1), 0.8, (0.18, 0.02, 0.42))])[:, None]], 1)
     ctable = shade.ColorMeshes(cmeshes)
@@ -216,7 +198,7 @@ def test_both_kernel_paths_the_cooperative_counter_and_the_tail(size):
     K = camera(h, w)
     small, box = render.icosphere(2, 0.1), render.box_mesh(0.3, 0.2, 0.2)
     table, rmeshes = table_of([(*small, None, None, spherical_uv(small[0]), random_texture(2, 2)),
-                               (*box, SD.smooth_colors(box[0], 2.0), None, box_uv(box[0]), random_texture(5, 3))])
+                               (*box, smooth_colors(box[0], 2.0), None, box_uv(box[0]), random_texture(5, 3))])
     ws = torch.empty(texture.texture_workspace_bytes(2, 1, h, w, table), dtype=torch.uint8, device=dev())
     far_ball = pose((1, 2, 3), 0.4, (0.0, 0.0, 0.9))[None, None]             # every face's box is a few pixels
     got = full(table, [0], [1], far_ball, K, h, w, shading="phong", filter="bilinear", workspace=ws)
@@ -235,7 +217,7 @@ def test_raw_call_without_colours_on_a_dirty_workspace_with_an_empty_image():
     K = camera(h, w)
     ball, box = render.icosphere(1, 0.1), render.box_mesh(0.15, 0.1, 0.2)
     table, rmeshes = table_of([(*ball, None, None, spherical_uv(ball[0]), random_texture(16, 16, channels=4)),
-                               (*box, SD.smooth_colors(box[0]), None, None, None),
+                               (*box, smooth_colors(box[0]), None, None, None),
                                (*box, None, None, box_uv(box[0]), random_texture(1, 1))])
     poses = np.stack([pose((1, 2, 3), 0.7, (0.02, -0.01, 0.5)), pose((2, 1, -1), 1.2, (0.04, 0.03, 0.6)), pose((3, -1, 2), 2.1, (-0.1, 0.05, 0.55))])
     lib = _abi.load_texture_library()
@@ -338,7 +320,7 @@ def test_front_end_rejects_what_it_cannot_render():
     with pytest.raises(RuntimeError):
         texture.render_textured(table, [0], [1], p.cpu(), K, h, w)                                      # a CPU tensor: no fallback
     with pytest.raises(RuntimeError):
-        texture.render_textured(shade.ColorMeshes([(*ball, SD.smooth_colors(ball[0]))]), [0], [1], p, K, h, w)   # no texture table
+        texture.render_textured(shade.ColorMeshes([(*ball, smooth_colors(ball[0]))]), [0], [1], p, K, h, w)   # no texture table
     none = torch.empty((2, 0, 3, 4), dtype=torch.float64, device=dev())
     got = texture.render_textured(table, [], [], none, K, h, w, background=BG, return_visible=True, return_status=True)
     assert (got[0].cpu() == torch.tensor(BG, dtype=torch.uint8)).all() and not got[1].any() and tuple(got[3].shape) == (2, 0)

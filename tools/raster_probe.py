@@ -25,14 +25,9 @@ sys.path.insert(0, ROOT)
 
 from pvnet_amd import render  # noqa: E402
 from tests import raster_restatement as RS  # noqa: E402
+from tests.render_cases import rotation  # noqa: E402
 
 B, H, W = 32, 480, 640
-
-
-def rotation(axis, angle):
-    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
 
 
 def make_poses(rng, n, spread=0.12):

@@ -30,6 +30,7 @@ TEX = 512
 
 def oracle_lines():
     """the ray-caster comparison of tests/test_texture_cpu.py, on the CPU: the figures its docstring records"""
+    from tests import render_cases as RC
     from tests import shade_restatement as SR
     from tests import test_shade_cpu as TS
     from tests import test_texture_cpu as TT
@@ -39,7 +40,7 @@ def oracle_lines():
              f"levels, bilinear filter, {TS.ORACLE_H} x {TS.ORACLE_W}, interior pixels"]
     (sv, sf, _, snrm), sp = TS.ORACLE_SCENES["sphere"]
     bv, bf, buv = TT.atlas_box(0.3, 0.22, 0.26)
-    scenes = {"sphere": ((sv, sf, snrm, TT.spherical_uv(sv)), sp), "box": ((bv, bf, shade.vertex_normals(bv, bf), buv), TS.ORACLE_SCENES["box"][1])}
+    scenes = {"sphere": ((sv, sf, snrm, RC.spherical_uv(sv)), sp), "box": ((bv, bf, shade.vertex_normals(bv, bf), buv), TS.ORACLE_SCENES["box"][1])}
     for name, ((v, f, nrm, uv), p) in sorted(scenes.items()):
         _, owner, _ = SR.instance_layers(v, f, p, TS.ORACLE_K, TS.ORACLE_H, TS.ORACLE_W)
         hits = TS.ray_hits(v, f, p, TS.ORACLE_K, TS.ORACLE_H, TS.ORACLE_W)
@@ -91,7 +92,7 @@ def device_lines(args):
     from raster_probe import make_poses, timed
     from shade_probe import colours
     from tests import texture_restatement as TR
-    from tests.test_texture_cpu import spherical_uv
+    from tests.render_cases import spherical_uv
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(1)
     K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]])
