@@ -15,9 +15,10 @@ _TAIL = ("TailParams", "fused_tail", "FusedTailNet")   # pvnet_amd.tail, on firs
 _DECODER = ("StageParams", "fused_stage", "FusedDecoderNet")   # pvnet_amd.decoder, on first use
 _STEM = ("StemParams", "fused_stem", "FusedStemNet")   # pvnet_amd.stem, on first use
 _TRUNK = ("ConvParams", "fused_conv3x3", "FusedBasicBlock", "FusedTrunkNet")   # pvnet_amd.trunk, on first use
+_NET = ("FusedNet",)   # pvnet_amd.net, on first use: the network class the four Fused*Net names are presets of
 
 __all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE, *_TAIL, *_DECODER, *_STEM,
-           *_TRUNK]
+           *_TRUNK, *_NET]
 
 
 def __getattr__(name):
@@ -36,4 +37,7 @@ def __getattr__(name):
     if name in _TRUNK:
         from . import trunk
         return getattr(trunk, name)
+    if name in _NET:
+        from . import net
+        return getattr(net, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

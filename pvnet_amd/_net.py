@@ -91,6 +91,17 @@ def new_or_checked_out(out, out_dtype, default_dtype, shape, dev, name="out"):
     return out
 
 
+def presets_in_net(module, *names):
+    """a module's ``__getattr__`` that resolves ``names`` in pvnet_amd/net.py on first use: net.py imports the four modules, so they
+    cannot import it while they load"""
+    def __getattr__(name):
+        if name in names:
+            from . import net
+            return getattr(net, name)
+        raise AttributeError(f"module {module!r} has no attribute {name!r}")
+    return __getattr__
+
+
 def conv_bn_act(net, name, who):
     """the ``Sequential`` of conv, bn, act that ``net`` has under ``name`` (the same in both spellings)"""
     seq = getattr(net, name, None)
@@ -108,7 +119,7 @@ class NetworkParts:
     (the upsample before conv4s, before conv2s and before convraw), ``stages`` (conv4s, conv2s) and ``convraw``, which both spell alike."""
 
     def __init__(self, net, who="NetworkParts"):
-        self.whole = getattr(net, "resnet18_8s", None)   # the reference's trunk, which its network calls whole
+        self.whole = getattr(net, "resnet18_8s", None)   # the reference's trunk, which its network calls whole and FusedNet piecewise
         try:
             if self.whole is not None:
                 t = self.whole
@@ -149,21 +160,6 @@ class NetworkParts:
     def eager_stem(self, x):
         x2s = self.stem_modules(x)
         return x2s, self.pool(x2s)
-
-    def behind_stem(self, p):
-        """(x4s, x8s, xfc) of the pooled tensor by the wrapped modules, piece by piece"""
-        x4s = self.layers[0](p)
-        x8s = self.layers[1](x4s)
-        return x4s, x8s, self.fc(self.layers[3](self.layers[2](x8s)))
-
-    def eager_trunk(self, x):
-        """(x2s, x4s, x8s, xfc) by the wrapped modules: the reference's trunk in the one call its network makes, the stand-in's piece
-        by piece"""
-        if self.whole is not None:
-            x2s, x4s, x8s, _, _, xfc = self.whole(x)
-            return x2s, x4s, x8s, xfc
-        x2s, p = self.eager_stem(x)
-        return (x2s,) + self.behind_stem(p)
 
     def eager_conv8s(self, xfc, x8s):
         return self.conv8s(torch.cat([xfc, x8s], 1))

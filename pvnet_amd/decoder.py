@@ -5,7 +5,7 @@ stage, concatenation with the trunk's skip features, 3 x 3 convolution with the 
 
     params = StageParams.from_network(net, "conv2s")     # folds the BatchNorm in float64 and packs the weights, once
     fm = fused_stage(lo, skip, params)                   # [b,co,h,w]; lo [b,cl,h/2,w/2] the previous stage, skip [b,64,h,w]
-    seg_pred, ver_pred = FusedDecoderNet(net)(image)     # trunk and conv8s under PyTorch, the fused stages, then the fused tail
+    seg_pred, ver_pred = FusedDecoderNet(net)(image)     # pvnet_amd/net.py: FusedNet with these stages and the tail fused
 
 There is one tier: operands rounded to bfloat16, float32 accumulation on the matrix pipe.  PyTorch is plumbing only.  There is NO CPU
 fallback: without the library, or with CPU tensors, these raise ``RuntimeError``.
@@ -13,13 +13,11 @@ fallback: without the library, or with CPU tensors, these raise ``RuntimeError``
 from __future__ import annotations
 
 import torch
-from torch import nn
 
 from ._abi import DECODER_F_PACKED, DECODER_SHAPES, DECODER_SKIP, _check, load_decoder_library
 from ._marshal import ptr as _ptr, stream as _stream, strides as _strides
-from ._net import (SLOPE, TYPE_CODES, NetworkParts, Params, check_conv_bn, check_input, conv_bn_act, fold_batchnorm, is_leaky,
-                   is_plain_conv, new_or_checked_out, pack_weights)
-from .tail import TailParams, fused_tail
+from ._net import (SLOPE, TYPE_CODES, Params, check_conv_bn, check_input, conv_bn_act, fold_batchnorm, is_leaky, is_plain_conv,
+                   new_or_checked_out, pack_weights, presets_in_net)
 
 STAGES = ("conv4s", "conv2s")   # the reference's attribute names, in the order the network runs them
 # the stages FusedDecoderNet fuses unless told otherwise: those that tools/decoder_probe.py measured faster than the eager stage by more
@@ -103,52 +101,4 @@ def fused_stage(lo, skip, params, *, out=None, out_dtype=None, packed=True):
     return out
 
 
-class FusedDecoderNet(nn.Module):
-    """A ``Resnet18_8s`` (the reference's, or the stand-in of tools/e2e_amd.py) for inference with the fused decoder: the wrapped
-    network's own trunk and ``conv8s`` run under PyTorch, the stages named in ``stages`` through ``fused_stage`` (a stage not named runs
-    its own modules), then ``fused_tail``.  Returns the reference's ``(seg_pred, ver_pred)``, as views of one tensor.
-
-    ``precision=None`` follows autocast: with float16 / bfloat16 features (as under ``torch.autocast``) the named stages and the
-    bfloat16 tail run; with float32 features the stages run the wrapped modules -- the library has no float32 tier -- and the tail
-    ``"f32"``, as ``FusedTailNet`` does.  ``"bf16"`` forces the fused stages and the bfloat16 tail, ``"f32"`` the modules and the float32
-    tail.  The output has the features' type."""
-
-    def __init__(self, net, stages=DEFAULT_STAGES, precision=None):
-        super().__init__()
-        if precision not in (None, "bf16", "f32"):
-            raise ValueError('precision must be None, "bf16" or "f32"')
-        stages = tuple(stages)
-        if not set(stages) <= set(STAGES) or len(set(stages)) != len(stages):
-            raise ValueError(f"stages must be drawn from {STAGES} (got {stages})")
-        self.net = net
-        self.precision = precision
-        self.stages = stages
-        self.seg_dim = int(net.seg_dim)
-        self.tail_params = TailParams.from_network(net)
-        self.stage_params = {s: StageParams.from_network(net, s) for s in stages}
-        self.parts = NetworkParts(net, type(self).__name__)
-
-    def _trunk(self, x):
-        """conv8s' output and the two skips, by the wrapped modules"""
-        x2s, x4s, x8s, xfc = self.parts.eager_trunk(x)
-        return self.parts.eager_conv8s(xfc, x8s), x4s, x2s
-
-    def _features(self, x):
-        """the output of ``conv2s`` and whether a fused stage may run on what the trunk handed over"""
-        fm, x4s, x2s = self._trunk(x)
-        fuse = self.precision == "bf16" or (self.precision is None and fm.dtype != torch.float32)
-        for k, (stage, skip) in enumerate(zip(STAGES, (x4s, x2s))):
-            if fuse and stage in self.stages:
-                fm = fused_stage(fm, skip, self.stage_params[stage])
-            else:
-                fm = self.parts.eager_stage(k, fm, skip)
-        return fm
-
-    @torch.no_grad()
-    def forward(self, x):
-        if self.net.training:
-            raise RuntimeError("FusedDecoderNet is inference only: call eval() on the wrapped network")
-        fm = self._features(x)
-        precision = self.precision or ("f32" if fm.dtype == torch.float32 else "bf16")
-        y = fused_tail(fm, x, self.tail_params, precision=precision)
-        return y[:, :self.seg_dim], y[:, self.seg_dim:]
+__getattr__ = presets_in_net(__name__, "FusedDecoderNet")   # the network class: pvnet_amd/net.py, which imports this module

@@ -5,7 +5,7 @@ PyTorch stem.
 
     params = StemParams.from_network(net)                # folds the BatchNorm in float64, once
     x2s, pooled = fused_stem(image, params)              # [b,64,Ho,Wo] (the decoder's skip input) and [b,64,Hp,Wp] (what layer1 takes)
-    seg_pred, ver_pred = FusedStemNet(net)(image)        # fused stem, the residual layers and conv8s under PyTorch, fused stages and tail
+    seg_pred, ver_pred = FusedStemNet(net)(image)        # pvnet_amd/net.py: FusedNet with the stem, the stages and the tail fused
 
 There is one tier: operands rounded to bfloat16, float32 accumulation on the matrix pipe.  PyTorch is plumbing only.  There is NO CPU
 fallback: without the library, or with CPU tensors, these raise ``RuntimeError``.
@@ -17,8 +17,8 @@ from torch import nn
 
 from ._abi import STEM_CIN, STEM_COUT, _check, load_stem_library
 from ._marshal import ptr as _ptr, stream as _stream, strides as _strides
-from ._net import TYPE_CODES, NetworkParts, Params, check_conv_bn, check_input, fold_batchnorm, is_plain_conv, new_or_checked_out
-from .decoder import DEFAULT_STAGES, FusedDecoderNet
+from ._net import (TYPE_CODES, NetworkParts, Params, check_conv_bn, check_input, fold_batchnorm, is_plain_conv, new_or_checked_out,
+                   presets_in_net)
 
 # whether FusedStemNet fuses the stem unless told otherwise: tools/stem_probe.py measured fused_stem faster than the eager stem and pool
 # by more than the spread of the eager rounds (profiles/stem_probe.txt) -- the rule decoder.DEFAULT_STAGES was set by
@@ -109,41 +109,4 @@ def fused_stem(image, params, *, out=None, out_dtype=None, pool=True):
     return x2s, pooled
 
 
-class FusedStemNet(FusedDecoderNet):
-    """``FusedDecoderNet`` with the trunk run piecewise: ``fused_stem``, then the wrapped network's own ``layer1 .. layer4`` and ``fc``
-    (the stand-in's ``l1 .. l4``, ``fc``) and ``conv8s`` under PyTorch, then the fused stages and the fused tail.  Returns the reference's
-    ``(seg_pred, ver_pred)``, as views of one tensor.
-
-    ``stem=False`` runs the wrapped stem modules: the network is then ``FusedDecoderNet``'s, bit for bit.  ``precision`` is
-    ``FusedDecoderNet``'s: ``None`` follows autocast -- the stem is fused where autocast is enabled for the image's device with float16 or
-    bfloat16, and x2s and the pooled tensor then have that type, as the eager stem's have; with float32 features the stem runs the
-    wrapped modules, because the library has one tier --, ``"bf16"`` forces the fused stem (with the image's type out, outside autocast),
-    ``"f32"`` the modules."""
-
-    def __init__(self, net, stem=DEFAULT_STEM, stages=DEFAULT_STAGES, precision=None):
-        super().__init__(net, stages=stages, precision=precision)
-        self.stem = bool(stem)
-        self.stem_params = StemParams.from_network(net) if self.stem else None
-        self.parts.require_fully_conv("FusedStemNet")
-        self._layers = self.parts.layers
-        self._trunk = self._trunk_piecewise
-
-    def _stem_dtype(self, x):
-        """the type the fused stem writes, or None where the wrapped modules run"""
-        if not self.stem or self.precision == "f32":
-            return None
-        if x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") in (torch.float16, torch.bfloat16):
-            return torch.get_autocast_dtype("cuda")
-        if self.precision == "bf16":
-            return x.dtype
-        return x.dtype if x.dtype in (torch.float16, torch.bfloat16) else None   # float32 features: the one tier does not serve them
-
-    def _stem(self, x):
-        """(x2s, the pooled tensor): fused, or by the wrapped modules"""
-        dtype = self._stem_dtype(x)
-        return self.parts.eager_stem(x) if dtype is None else fused_stem(x, self.stem_params, out_dtype=dtype)
-
-    def _trunk_piecewise(self, x):
-        x2s, p = self._stem(x)
-        x4s, x8s, xfc = self.parts.behind_stem(p)
-        return self.parts.eager_conv8s(xfc, x8s), x4s, x2s
+__getattr__ = presets_in_net(__name__, "FusedStemNet")   # the network class: pvnet_amd/net.py, which imports this module

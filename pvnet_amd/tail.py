@@ -5,7 +5,7 @@ to the seg / vertex channels -- ``up2storaw`` + ``cat`` + ``convraw`` of the ref
 
     params = TailParams.from_network(net)              # folds the BatchNorm in float64, once
     out = fused_tail(fm, image, params)                # [b,cout,h,w]; fm [b,32,h/2,w/2] is the output of conv2s, image [b,3,h,w]
-    seg_pred, ver_pred = FusedTailNet(net)(image)      # the wrapped network's trunk under PyTorch, then the fused tail
+    seg_pred, ver_pred = FusedTailNet(net)(image)      # pvnet_amd/net.py: FusedNet with only this piece fused
 
 ``seg_pred`` / ``ver_pred`` are views of one tensor; ``voting.EvalWrapper`` / ``PoseEvalWrapper`` and the ``_from_logits`` entries take
 them as they are.  PyTorch is plumbing only.  There is NO CPU fallback: without the library, or with CPU tensors, these raise
@@ -18,7 +18,8 @@ from torch import nn
 
 from ._abi import TAIL_BF16, TAIL_F32, TAIL_F_RAW, TAIL_MAX_COUT, TAIL_WIDTH, _check, load_tail_library
 from ._marshal import ptr as _ptr, stream as _stream, strides as _strides
-from ._net import SLOPE, TYPE_CODES, NetworkParts, Params, check_conv_bn, check_input, fold_batchnorm, is_leaky, is_plain_conv, new_or_checked_out
+from ._net import (SLOPE, TYPE_CODES, Params, check_conv_bn, check_input, fold_batchnorm, is_leaky, is_plain_conv, new_or_checked_out,
+                   presets_in_net)
 
 _PRECISIONS = {"bf16": TAIL_BF16, "f32": TAIL_F32}
 
@@ -112,34 +113,4 @@ def fused_tail(fm, image, params, *, precision="bf16", out=None, out_dtype=None,
     return out
 
 
-class FusedTailNet(nn.Module):
-    """A ``Resnet18_8s`` (the reference's, or the stand-in of tools/e2e_amd.py) for inference with the fused tail: the wrapped network's
-    own trunk and decoder modules run under PyTorch up to ``conv2s``, then ``fused_tail``.  Returns the reference's ``(seg_pred,
-    ver_pred)``, as views of one tensor.
-
-    ``precision=None`` follows autocast: the tail runs ``"bf16"`` when the trunk hands it float16 / bfloat16 features (as under
-    ``torch.autocast``) and ``"f32"`` for float32 features; ``"bf16"`` / ``"f32"`` fix it.  The output has the features' type."""
-
-    def __init__(self, net, precision=None):
-        super().__init__()
-        if precision is not None and precision not in _PRECISIONS:
-            raise ValueError('precision must be None, "bf16" or "f32"')
-        self.net = net
-        self.precision = precision
-        self.seg_dim = int(net.seg_dim)
-        self.params = TailParams.from_network(net)
-        self.parts = NetworkParts(net, "FusedTailNet")
-
-    def _features(self, x):
-        p = self.parts
-        x2s, x4s, x8s, xfc = p.eager_trunk(x)
-        return p.eager_stage(1, p.eager_stage(0, p.eager_conv8s(xfc, x8s), x4s), x2s)
-
-    @torch.no_grad()
-    def forward(self, x):
-        if self.net.training:
-            raise RuntimeError("FusedTailNet is inference only: call eval() on the wrapped network")
-        fm = self._features(x)
-        precision = self.precision or ("f32" if fm.dtype == torch.float32 else "bf16")
-        y = fused_tail(fm, x, self.params, precision=precision)
-        return y[:, :self.seg_dim], y[:, self.seg_dim:]
+__getattr__ = presets_in_net(__name__, "FusedTailNet")   # the network class: pvnet_amd/net.py, which imports this module

@@ -7,7 +7,7 @@ Inference only: no autograd, ``eval()`` BatchNorm; training keeps the PyTorch tr
     params = ConvParams.from_modules(conv, bn, act)           # folds the BatchNorm in float64 and packs the weights, once
     y = fused_conv3x3(x, params, residual=r)                  # [b,co,ho,wo]; src2= concatenates a second input behind the first
     y = FusedBasicBlock(block)(x)                             # two launches; a 1 x 1 downsample is one F.conv2d with its BatchNorm folded
-    seg_pred, ver_pred = FusedTrunkNet(net, layers=LAYERS)(image)   # fused stem, the named pieces fused, fused stages and tail
+    seg_pred, ver_pred = FusedTrunkNet(net, layers=LAYERS)(image)   # pvnet_amd/net.py: FusedNet under its first name
 
 There is one tier: operands rounded to bfloat16, float32 accumulation on the matrix pipe.  PyTorch is plumbing only.  There is NO CPU
 fallback: without the library, or with CPU tensors, these raise ``RuntimeError``.
@@ -20,10 +20,8 @@ from torch import nn
 
 from ._abi import TRUNK_ACT_LEAKY, TRUNK_ACT_NONE, TRUNK_ACT_RELU, TRUNK_GEOMETRIES, TRUNK_MAX_WIDTH, _check, load_trunk_library
 from ._marshal import ptr as _ptr, stream as _stream, strides as _strides
-from ._net import (SLOPE, TYPE_CODES, NetworkParts, Params, check_conv_bn, check_input, conv_bn_act, fold_batchnorm, is_leaky,
-                   is_plain_conv, new_or_checked_out, pack_weights)
-from .decoder import DEFAULT_STAGES
-from .stem import DEFAULT_STEM, FusedStemNet
+from ._net import (SLOPE, TYPE_CODES, NetworkParts, Params, check_conv_bn, check_input, fold_batchnorm, is_leaky, is_plain_conv,
+                   new_or_checked_out, pack_weights, presets_in_net)
 
 ACTS = {"none": TRUNK_ACT_NONE, "relu": TRUNK_ACT_RELU, "leaky": TRUNK_ACT_LEAKY}
 LAYERS = ("layer1", "layer2", "layer3", "layer4", "fc", "conv8s")   # the reference's attribute names, in the order the network runs them
@@ -169,44 +167,4 @@ class FusedBasicBlock(nn.Module):
         return fused_conv3x3(y, self.conv2, residual=self.residual(x))
 
 
-class FusedTrunkNet(FusedStemNet):
-    """``FusedStemNet`` with the pieces of the trunk named in ``layers`` -- drawn from ``LAYERS`` -- run through ``fused_conv3x3``:
-    ``layer1 .. layer4`` (the stand-in's ``l1 .. l4``) as ``FusedBasicBlock``s, ``fc`` as one launch, ``conv8s`` as one launch that
-    reads ``xfc`` and ``x8s`` as its two inputs, so its ``torch.cat`` is not made.  A piece not named runs its own modules;
-    ``layers=()`` is ``FusedStemNet``, bit for bit.  Returns the reference's ``(seg_pred, ver_pred)``, as views of one tensor.
-
-    ``precision`` is ``FusedStemNet``'s: ``None`` follows autocast -- the named pieces are fused where the features the stem handed
-    over are float16 or bfloat16, as they are under ``torch.autocast``; with float32 features they run the wrapped modules, because
-    the library has one tier --, ``"bf16"`` forces the fused pieces, ``"f32"`` the modules."""
-
-    def __init__(self, net, layers=DEFAULT_LAYERS, stem=DEFAULT_STEM, stages=DEFAULT_STAGES, precision=None):
-        super().__init__(net, stem=stem, stages=stages, precision=precision)
-        layers = tuple(layers)
-        if not set(layers) <= set(LAYERS) or len(set(layers)) != len(layers):
-            raise ValueError(f"layers must be drawn from {LAYERS} (got {layers})")
-        self.layers = layers
-        self.blocks = nn.ModuleDict({name: nn.ModuleList(FusedBasicBlock(blk) for blk in seq)
-                                     for name, seq in zip(LAYERS[:4], self.parts.layers) if name in layers})
-        self.fc_params, self.conv8s_params = (ConvParams.from_modules(*conv_bn_act(self.parts, name, "FusedTrunkNet")) if name in layers
-                                              else None for name in ("fc", "conv8s"))
-        if layers:   # with none named, FusedStemNet's own trunk stays: the same calls, so the same bits
-            self._trunk = self._trunk_fused
-
-    def _layer(self, k, x, fuse):
-        name = LAYERS[k]
-        if not (fuse and name in self.layers):
-            return self.parts.layers[k](x)
-        for blk in self.blocks[name]:
-            x = blk(x)
-        return x
-
-    def _trunk_fused(self, x):
-        x2s, p = self._stem(x)
-        fuse = self.precision == "bf16" or (self.precision is None and p.dtype != torch.float32)
-        x4s = self._layer(0, p, fuse)
-        x8s = self._layer(1, x4s, fuse)
-        x32s = self._layer(3, self._layer(2, x8s, fuse), fuse)
-        xfc = fused_conv3x3(x32s, self.fc_params) if fuse and "fc" in self.layers else self.parts.fc(x32s)
-        if fuse and "conv8s" in self.layers:
-            return fused_conv3x3(xfc, self.conv8s_params, src2=x8s), x4s, x2s
-        return self.parts.eager_conv8s(xfc, x8s), x4s, x2s
+__getattr__ = presets_in_net(__name__, "FusedTrunkNet")   # the network class: pvnet_amd/net.py, which imports this module

@@ -1,14 +1,13 @@
 """CPU-only checks of the fused decoder stages (include/pvnet_decoder.h, libpvnet_decoder.so, pvnet_amd/decoder.py): the registry rows
 and their place, the header's constants against pvnet_amd/_abi.py, every bad argument rejected before any HIP call, ``StageParams``'
-folding of the BatchNorm against torch's own, its packing of the weights against the header's formula and its refusals, both attribute
-spellings of the network (the reference's own class where its tree is present), and the restatement (tests/decoder_restatement.py): against torch's float64 composition of the real modules, against one-hot weights, and
-against planted mistakes, each of which the comparison's bar must catch.
+folding of the BatchNorm against torch's own, its packing of the weights against the header's formula and its refusals (the network
+class: tests/test_net_cpu.py), and the restatement (tests/decoder_restatement.py): against torch's float64 composition of the real
+modules, against one-hot weights, and against planted mistakes, each of which the comparison's bar must catch.
 What holds for every side library alike is in tests/test_side_libraries_cpu.py."""
 import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -22,7 +21,6 @@ from tests import decoder_cases as DC  # noqa: E402
 from tests import decoder_restatement as DR  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 HDR = open(os.path.join(ROOT, "include", "pvnet_decoder.h")).read()
 BADARG, UNSUPPORTED = -1, -3
 
@@ -192,85 +190,18 @@ def test_refusals():
         D.StageParams.from_network(net, "conv8s")
     with pytest.raises(ValueError):
         D.StageParams.from_network(nn.Sequential(), "conv2s")
-    with pytest.raises(ValueError):
-        D.FusedDecoderNet(net, stages=("conv8s",))
-    with pytest.raises(ValueError):
-        D.FusedDecoderNet(net, precision="fp8")
     with pytest.raises(RuntimeError):   # no CPU fallback
         D.fused_stage(torch.zeros(1, 64, 4, 4), torch.zeros(1, 64, 8, 8), D.StageParams.from_network(net, "conv2s"))
-    fused = D.FusedDecoderNet(net)
-    net.train()
-    with pytest.raises(RuntimeError, match="inference only"):
-        fused(torch.zeros(1, 3, 32, 48))
-    net.eval()
 
 
 def test_from_network_reads_the_reference_attribute_names():
-    net, x = DC.standin()
+    net, _ = DC.standin()
     for triple in DC.TRIPLES:
         stage = DC.STAGE_OF[triple]
         P = D.StageParams.from_network(net, stage)
         seq = getattr(net, stage)
         Q = D.StageParams.from_modules(seq[0], seq[1], act=seq[2])
         assert (P.cl, P.cs, P.co) == triple and torch.equal(P.w, Q.w) and torch.equal(P.bias, Q.bias) and torch.equal(P.packed, Q.packed)
-    fused = D.FusedDecoderNet(net)
-    assert fused.seg_dim == 2 and set(fused.stages) <= set(D.STAGES) and set(fused.stage_params) == set(fused.stages)
-    assert D.FusedDecoderNet(net, stages=()).stage_params == {}
-    # float32 features without a forced precision: the wrapped modules run, so the features are the stand-in's own -- on the CPU too
-    from tests.tail_cases import standin_features
-    with torch.no_grad():
-        assert torch.equal(fused._features(x), standin_features(net, x))
-
-
-REFERENCE_SCRIPT = r"""
-import sys, torch
-sys.path.insert(0, %(tools)r); sys.path.insert(0, %(root)r)
-import refshim
-refshim.install(%(ref)r)
-from tests import tail_cases as TC
-from pvnet_amd import decoder as D
-mine, x = TC.standin()
-for k in [k for k in sys.modules if k == "lib" or k.startswith("lib.")]:
-    del sys.modules[k]                           # the repo's drop-in overlay package is also called `lib`
-sys.path.insert(0, %(ref)r)
-import lib.networks.resnet as R
-R.model_zoo.load_url = lambda *a, **k: {}        # no network here
-R.ResNet.load_state_dict = lambda self, sd, *a, **k: None
-from lib.networks.model_repository import Resnet18_8s
-ref = Resnet18_8s(ver_dim=18, seg_dim=2).eval()
-with torch.no_grad():
-    for a, b in zip(ref.parameters(), mine.parameters()):
-        a.copy_(b)
-    for a, b in zip(ref.buffers(), mine.buffers()):
-        a.copy_(b)
-for stage in D.STAGES:
-    Pr, Pm = D.StageParams.from_network(ref, stage), D.StageParams.from_network(mine, stage)
-    assert all(torch.equal(a, b) for a, b in zip((Pr.w, Pr.bias, Pr.packed), (Pm.w, Pm.bias, Pm.packed)))
-Fr, Fm = D.FusedDecoderNet(ref), D.FusedDecoderNet(mine)
-with torch.no_grad():
-    tr, tm = Fr._trunk(x), Fm._trunk(x)          # conv8s' output and the two skips, under the reference's attribute names
-    assert [tuple(t.shape) for t in tr] == [(1, 128, 4, 6), (1, 64, 8, 12), (1, 64, 16, 24)]
-    assert all(torch.allclose(a, b, atol=1e-5, rtol=1e-5) for a, b in zip(tr, tm))
-    fr, fm = Fr._features(x), Fm._features(x)    # float32 features: the reference's own up8sto4s / conv4s / up4sto2s / conv2s
-assert fr.shape == (1, 32, 16, 24) and torch.allclose(fr, fm, atol=1e-5, rtol=1e-5)
-print("BOTH_SPELLINGS")
-"""
-
-
-def test_fused_decoder_net_takes_the_references_own_class_where_its_tree_is_present():
-    net, _ = DC.standin()
-
-    class Decoder(nn.Module):   # the decoder's attributes without a trunk of either spelling
-        def __init__(self):
-            super().__init__()
-            self.seg_dim, self.conv4s, self.conv2s, self.convraw = net.seg_dim, net.conv4s, net.conv2s, net.convraw
-
-    with pytest.raises(ValueError, match="neither"):
-        D.FusedDecoderNet(Decoder().eval())
-    if os.path.isdir(REF):   # loaded the way tests/test_tail_cpu.py loads it
-        code = REFERENCE_SCRIPT % dict(tools=os.path.join(ROOT, "tools"), root=ROOT, ref=REF)
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=ROOT)
-        assert r.returncode == 0 and "BOTH_SPELLINGS" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 # ---- 4. the restatement --------------------------------------------------------------------------------------------------------------------

@@ -184,49 +184,3 @@ def test_graph_capture_and_replay(D):
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, want2 if k == 2 else want1), k
-
-
-# ---- the network -----------------------------------------------------------------------------------------------------------------------------
-def test_fused_decoder_net_against_the_eager_standin_and_into_the_voting_layer(D):
-    from pvnet_amd import tail, voting
-    net, x = DC.standin()
-    assert tuple(x.shape) == (1, 3, 32, 48)
-    net, x = net.to(dev()), x.to(dev())
-    with torch.no_grad():
-        ref = torch.cat(net(x), 1).double()
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            eager = torch.cat(net(x), 1)
-    # e: what the EAGER network under the same autocast differs from the eager float32 network by
-    e = float((eager.double() - ref).abs().max())
-    fused = D.FusedDecoderNet(net, stages=D.STAGES)
-    with torch.autocast("cuda", dtype=torch.bfloat16):
-        seg, ver = fused(x)
-    torch.cuda.synchronize()
-    assert tuple(seg.shape) == (1, 2, 32, 48) and tuple(ver.shape) == (1, 18, 32, 48) and seg.dtype == ver.dtype == torch.bfloat16
-    assert seg.untyped_storage().data_ptr() == ver.untyped_storage().data_ptr()   # views of one tensor
-    d = float((torch.cat([seg, ver], 1).double() - ref).abs().max())
-    print(f"FusedDecoderNet, stand-in 1x3x32x48, autocast(bfloat16): eager differs from eager float32 by e = {e:.4e}, fused by {d:.4e} "
-          f"({d / e:.2f} e; the bar is 2 e)")
-    # two differently ordered bfloat16 computations of the same function may each sit e from it
-    assert e > 0 and d <= 2 * e
-    for stages in (("conv4s",), ("conv2s",), D.DEFAULT_STAGES):   # a stage not named runs its own modules
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            y = torch.cat(D.FusedDecoderNet(net, stages=stages)(x), 1)
-        assert float((y.double() - ref).abs().max()) <= 2 * e, stages
-    # without a fused stage it is FusedTailNet: the same modules in the same order, then the same launch
-    with torch.autocast("cuda", dtype=torch.bfloat16):
-        a, b_ = D.FusedDecoderNet(net, stages=())(x), tail.FusedTailNet(net)(x)
-    assert a[0].dtype == b_[0].dtype == torch.bfloat16 and torch.equal(a[0], b_[0]) and torch.equal(a[1], b_[1])
-    # float32 features: the wrapped modules and the float32 tail, under the bar tests/test_tail_device.py holds FusedTailNet to (the
-    # eager float32 network does not reproduce itself bit for bit from call to call -- two calls differ by 1e-7 --, so no equality
-    # here); "bf16" forces the fused stages
-    y32 = torch.cat(fused(x), 1)
-    assert y32.dtype == torch.float32 and torch.allclose(y32.double(), ref, atol=1e-5, rtol=1e-5)
-    forced = torch.cat(D.FusedDecoderNet(net, stages=D.STAGES, precision="bf16")(x), 1)
-    d32 = float((forced.double() - ref).abs().max())
-    print(f"precision=\"bf16\" on float32 features: {d32:.4e} = {d32 / e:.2f} e")
-    assert forced.dtype == torch.float32 and not torch.equal(forced, y32) and d32 <= 2 * e   # fewer roundings than under autocast
-    # the views go into the voting layer unchanged
-    kp = voting.EvalWrapper(round_hyp_num=128)(seg, ver)
-    torch.cuda.synchronize()
-    assert tuple(kp.shape) == (1, 9, 2)

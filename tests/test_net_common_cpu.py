@@ -75,7 +75,10 @@ def test_network_parts_resolves_the_standin_and_refuses_neither_spelling():
         P.require_fully_conv("test")   # the stand-in has no such switch
         x = tail_cases.standin()[1]
         with torch.no_grad():   # the wrapped modules in the stand-in's own order: the same bits
-            x2s, x4s, x8s, xfc = P.eager_trunk(x)
+            x2s, p = P.eager_stem(x)
+            x4s = P.layers[0](p)
+            x8s = P.layers[1](x4s)
+            xfc = P.fc(P.layers[3](P.layers[2](x8s)))
             fm = P.eager_stage(1, P.eager_stage(0, P.eager_conv8s(xfc, x8s), x4s), x2s)
             assert torch.equal(fm, tail_cases.standin_features(net, x))
 

@@ -1,14 +1,12 @@
 """CPU-only checks of the fused stem (include/pvnet_stem.h, libpvnet_stem.so, pvnet_amd/stem.py): the registry rows and their place, the
 header's constants against pvnet_amd/_abi.py, every bad argument rejected before any HIP call, ``StemParams``' folding of the BatchNorm
-against torch's own and its refusals, both attribute spellings of the network (the reference's own class where its tree is present), and
-the restatement (tests/stem_restatement.py): against torch's float64 composition, against the fixture recorded from the reference's own
-stem, against one-hot weights, and against planted mistakes, each of which the device tests' bars must catch.
+against torch's own and its refusals (the network class: tests/test_net_cpu.py), and the restatement (tests/stem_restatement.py):
+against torch's float64 composition, against the fixture recorded from the reference's own stem, against one-hot weights, and against planted mistakes, each of which the device tests' bars must catch.
 What holds for every side library alike is in tests/test_side_libraries_cpu.py."""
 import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,13 +16,11 @@ from torch import nn  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from pvnet_amd import _abi, build  # noqa: E402
-from pvnet_amd import decoder as D  # noqa: E402
 from pvnet_amd import stem as S  # noqa: E402
 from tests import stem_cases as SC  # noqa: E402
 from tests import stem_restatement as SR  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 HDR = open(os.path.join(ROOT, "include", "pvnet_stem.h")).read()
 BADARG, UNSUPPORTED = -1, -3
 shapes = pytest.mark.parametrize("shape", SC.SHAPES, ids=["x".join(map(str, s)) for s in SC.SHAPES])
@@ -175,103 +171,19 @@ def test_refusals():
     net.eval()
     with pytest.raises(ValueError, match="neither"):
         S.StemParams.from_network(nn.Sequential())
-    with pytest.raises(ValueError):
-        S.FusedStemNet(net, precision="fp8")
-    with pytest.raises(ValueError):
-        S.FusedStemNet(net, stages=("conv8s",))
     P = S.StemParams.from_network(net)
     with pytest.raises(RuntimeError):   # no CPU fallback
         S.fused_stem(torch.zeros(1, 3, 8, 8), P)
     with pytest.raises(RuntimeError):
         S.fused_stem(torch.zeros(1, 3, 8, 8), (P.w, P.bias))
-    fused = S.FusedStemNet(net)
-    net.train()
-    with pytest.raises(RuntimeError, match="inference only"):
-        fused(torch.zeros(1, 3, 32, 48))
-    net.eval()
 
 
-def test_from_network_reads_the_standins_attribute_names_and_the_float32_trunk_is_the_decoder_nets():
-    net, x = SC.standin()
+def test_from_network_reads_the_standins_attribute_names():
+    net, _ = SC.standin()
     P = S.StemParams.from_network(net)
     Q = S.StemParams.from_modules(net.stem[0], net.stem[1], act=net.stem[2], pool=net.pool)
     assert torch.equal(P.w, Q.w) and torch.equal(P.bias, Q.bias)
     assert P.on("cpu") is P.on(torch.device("cpu")) and torch.equal(P.on("cpu")[0], P.w)   # the device copies are kept
-    fused = S.FusedStemNet(net)
-    assert isinstance(fused, D.FusedDecoderNet) and fused.stem is S.DEFAULT_STEM and fused.stages == D.DEFAULT_STAGES
-    assert (fused.stem_params is not None) == S.DEFAULT_STEM and S.FusedStemNet(net, stem=False).stem_params is None
-    # float32 features without a forced precision: the wrapped modules run piecewise -- on the CPU too --, and give what FusedDecoderNet's
-    # whole trunk gives
-    with torch.no_grad():
-        for a, b_ in zip(fused._trunk(x), D.FusedDecoderNet(net)._trunk(x)):
-            assert torch.equal(a, b_)
-        from tests.tail_cases import standin_features
-        assert torch.equal(S.FusedStemNet(net, stem=True)._features(x), standin_features(net, x))
-
-
-REFERENCE_SCRIPT = r"""
-import sys, torch
-sys.path.insert(0, %(tools)r); sys.path.insert(0, %(root)r)
-import refshim
-refshim.install(%(ref)r)
-from tests import tail_cases as TC
-from pvnet_amd import decoder as D, stem as S
-mine, x = TC.standin()
-for k in [k for k in sys.modules if k == "lib" or k.startswith("lib.")]:
-    del sys.modules[k]                           # the repo's drop-in overlay package is also called `lib`
-sys.path.insert(0, %(ref)r)
-import lib.networks.resnet as R
-R.model_zoo.load_url = lambda *a, **k: {}        # no network here
-R.ResNet.load_state_dict = lambda self, sd, *a, **k: None
-from lib.networks.model_repository import Resnet18_8s
-ref = Resnet18_8s(ver_dim=18, seg_dim=2).eval()
-with torch.no_grad():
-    for a, b in zip(ref.parameters(), mine.parameters()):
-        a.copy_(b)
-    for a, b in zip(ref.buffers(), mine.buffers()):
-        a.copy_(b)
-Pr, Pm = S.StemParams.from_network(ref), S.StemParams.from_network(mine)
-assert torch.equal(Pr.w, Pm.w) and torch.equal(Pr.bias, Pm.bias)
-Fr, Fm = S.FusedStemNet(ref), S.FusedStemNet(mine)
-with torch.no_grad():
-    tr, tm, td = Fr._trunk(x), Fm._trunk(x), D.FusedDecoderNet(ref)._trunk(x)
-    assert [tuple(t.shape) for t in tr] == [(1, 128, 4, 6), (1, 64, 8, 12), (1, 64, 16, 24)]
-    assert all(torch.allclose(a, b, atol=1e-5, rtol=1e-5) for a, b in zip(tr, tm))
-    assert all(torch.equal(a, b) for a, b in zip(tr, td))   # piecewise, the reference's own forward
-# a trunk that is not the fully convolutional one is refused
-plain = Resnet18_8s(ver_dim=18, seg_dim=2).eval()
-plain.resnet18_8s.remove_avg_pool_layer = False
-try:
-    S.FusedStemNet(plain)
-except ValueError as e:
-    assert "fully_conv" in str(e)
-else:
-    raise AssertionError("not refused")
-plain.resnet18_8s.remove_avg_pool_layer, plain.resnet18_8s.fully_conv = True, False
-try:
-    S.FusedStemNet(plain, stem=False)
-except ValueError as e:
-    assert "fully_conv" in str(e)
-else:
-    raise AssertionError("not refused")
-print("BOTH_SPELLINGS")
-"""
-
-
-def test_fused_stem_net_takes_the_references_own_class_where_its_tree_is_present():
-    net, _ = SC.standin()
-
-    class Decoder(nn.Module):   # the decoder's attributes without a trunk of either spelling
-        def __init__(self):
-            super().__init__()
-            self.seg_dim, self.conv4s, self.conv2s, self.convraw = net.seg_dim, net.conv4s, net.conv2s, net.convraw
-
-    with pytest.raises(ValueError, match="neither"):
-        S.FusedStemNet(Decoder().eval())
-    if os.path.isdir(REF):   # loaded the way tests/test_decoder_cpu.py loads it
-        code = REFERENCE_SCRIPT % dict(tools=os.path.join(ROOT, "tools"), root=ROOT, ref=REF)
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=ROOT)
-        assert r.returncode == 0 and "BOTH_SPELLINGS" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 # ---- 4. the restatement --------------------------------------------------------------------------------------------------------------------

@@ -250,49 +250,3 @@ def test_graph_capture_and_replay(S):
         torch.cuda.synchronize()
         for got, want in zip(out, want2 if k == 2 else want1):
             assert torch.equal(got, want), k
-
-
-# ---- the network -----------------------------------------------------------------------------------------------------------------------------
-def test_fused_stem_net_against_the_eager_standin_and_into_the_voting_layer(S):
-    from pvnet_amd import decoder, voting
-    net, x = SC.standin()
-    assert tuple(x.shape) == (1, 3, 32, 48)
-    net, x = net.to(dev()), x.to(dev())
-    with torch.no_grad():
-        ref = torch.cat(net(x), 1).double()
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            eager = torch.cat(net(x), 1)
-    # e: what the EAGER network under the same autocast differs from the eager float32 network by
-    e = float((eager.double() - ref).abs().max())
-    fused = S.FusedStemNet(net, stem=True, stages=decoder.STAGES)
-    with torch.autocast("cuda", dtype=torch.bfloat16):
-        seg, ver = fused(x)
-    torch.cuda.synchronize()
-    assert tuple(seg.shape) == (1, 2, 32, 48) and tuple(ver.shape) == (1, 18, 32, 48) and seg.dtype == ver.dtype == torch.bfloat16
-    assert seg.untyped_storage().data_ptr() == ver.untyped_storage().data_ptr()   # views of one tensor
-    d = float((torch.cat([seg, ver], 1).double() - ref).abs().max())
-    print(f"FusedStemNet, stand-in 1x3x32x48, autocast(bfloat16): eager differs from eager float32 by e = {e:.4e}, fused by {d:.4e} "
-          f"({d / e:.2f} e; the bar is 2 e)")
-    # two differently ordered bfloat16 computations of the same function may each sit e from it
-    assert e > 0 and d <= 2 * e
-    # the fused stem did run, and its x2s is bfloat16 as the eager stem's under autocast
-    assert fused._stem_dtype(x) is None
-    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-        assert fused._stem_dtype(x) == torch.bfloat16
-        _, _, x2s = fused._trunk(x)
-        x2s_eager = net.stem(x)
-    assert x2s.dtype == x2s_eager.dtype == torch.bfloat16 and x2s.shape == x2s_eager.shape    # without the fused stem it is FusedDecoderNet: the same modules in the same order, then the same launches
-    with torch.autocast("cuda", dtype=torch.bfloat16):
-        a, b_ = S.FusedStemNet(net, stem=False)(x), decoder.FusedDecoderNet(net)(x)
-    assert a[0].dtype == b_[0].dtype == torch.bfloat16 and torch.equal(a[0], b_[0]) and torch.equal(a[1], b_[1])
-    # float32 features: the wrapped modules (the library has one tier) and the float32 tail, under FusedDecoderNet's bar
-    y32 = torch.cat(fused(x), 1)
-    assert y32.dtype == torch.float32 and torch.allclose(y32.double(), ref, atol=1e-5, rtol=1e-5)
-    forced = torch.cat(S.FusedStemNet(net, stem=True, stages=decoder.STAGES, precision="bf16")(x), 1)
-    d32 = float((forced.double() - ref).abs().max())
-    print(f"precision=\"bf16\" on a float32 image: {d32:.4e} = {d32 / e:.2f} e")
-    assert forced.dtype == torch.float32 and not torch.equal(forced, y32) and d32 <= 2 * e   # fewer roundings than under autocast
-    # the views go into the voting layer unchanged
-    kp = voting.ransac_voting_layer_v3_from_logits(seg, voting._field_view(ver), 128, inlier_thresh=0.99)
-    torch.cuda.synchronize()
-    assert tuple(kp.shape) == (1, 9, 2)

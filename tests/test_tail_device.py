@@ -227,44 +227,3 @@ def test_graph_capture_and_replay(T):
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, want2 if k == 2 else want1), k
-
-
-# ---- the network -----------------------------------------------------------------------------------------------------------------------------
-def test_fused_tail_net_against_the_eager_standin_and_into_the_voting_layer(T):
-    from pvnet_amd import voting
-    net, _ = TC.standin()
-    net = net.to(dev())
-    x = torch.randn(2, 3, 64, 96, generator=torch.Generator().manual_seed(60)).to(dev())
-    with torch.no_grad():
-        seg0, ver0 = net(x)
-    ref = torch.cat([seg0, ver0], 1).cpu()
-    fused = T.FusedTailNet(net)
-    seg, ver = fused(x)
-    torch.cuda.synchronize()
-    assert tuple(seg.shape) == (2, 2, 64, 96) and tuple(ver.shape) == (2, 18, 64, 96) and seg.dtype == torch.float32
-    assert seg.untyped_storage().data_ptr() == ver.untyped_storage().data_ptr()   # views of one tensor
-    assert torch.allclose(torch.cat([seg, ver], 1).cpu(), ref, atol=1e-5, rtol=1e-5)   # float32 features: the float32 tier, G9's bar
-    # stage for stage on the features the trunk produced, both tiers
-    with torch.no_grad():
-        fm = fused._features(x)
-    params = (fused.params.w1, fused.params.b1, fused.params.w2, fused.params.b2)
-    for precision in PRECISIONS:
-        hold_stages(T, fm.cpu(), x.cpu(), params, precision, fm_dev=fm, image_dev=x)
-    # the bfloat16 tier against the eager float32 network under the a-priori bound
-    seg_b, ver_b = T.FusedTailNet(net, precision="bf16")(x)
-    bound, _ = TR.bf16_bound(fm.cpu(), x.cpu(), *params)
-    yb = torch.cat([seg_b, ver_b], 1).cpu().double().numpy()
-    assert (np.abs(yb - ref.double().numpy()) <= bound + 1e-5 + 1e-5 * np.abs(ref.double().numpy())).all()
-    # under autocast the trunk hands over bfloat16 features: the bfloat16 tier, bfloat16 outputs, still views
-    with torch.autocast("cuda", dtype=torch.bfloat16):
-        seg_a, ver_a = fused(x)
-    assert seg_a.dtype == ver_a.dtype == torch.bfloat16 and not ver_a.is_contiguous()
-    # the views go straight into the voting layer: the key-points equal those from contiguous clones
-    field = ver_a.permute(0, 2, 3, 1).view(2, 64, 96, 9, 2)
-    kp = voting.ransac_voting_layer_v3_from_logits(seg_a, field, 128, inlier_thresh=0.99, seed=3)
-    field_c = ver_a.contiguous().permute(0, 2, 3, 1).view(2, 64, 96, 9, 2)
-    kp_c = voting.ransac_voting_layer_v3_from_logits(seg_a.contiguous(), field_c, 128, inlier_thresh=0.99, seed=3)
-    torch.cuda.synchronize()
-    assert tuple(kp.shape) == (2, 9, 2) and torch.equal(kp, kp_c)
-    kp_w = voting.EvalWrapper(round_hyp_num=128)(seg_a, ver_a)
-    assert tuple(kp_w.shape) == (2, 9, 2)

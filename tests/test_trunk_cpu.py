@@ -1,7 +1,7 @@
 """CPU-only checks of the fused trunk convolution (include/pvnet_trunk.h, libpvnet_trunk.so, pvnet_amd/trunk.py): the registry rows,
 the header's constants against pvnet_amd/_abi.py, every bad argument rejected before any HIP call, ``ConvParams``' folding
 of the BatchNorm against torch's own, its packing of the weights against the header's formula and its refusals, both attribute spellings
-of a block (the reference's own class where its tree is present), and the restatement (tests/trunk_restatement.py): against torch's
+of a block (the reference's own class: tests/test_net_cpu.py), and the restatement (tests/trunk_restatement.py): against torch's
 float64 ``F.conv2d``, against the reference's recorded trunk (tests/golden/trunk.npz), against one-hot weights, and against planted
 mistakes, each of which the device tests' bar must catch.
 What holds for every side library alike is in tests/test_side_libraries_cpu.py."""
@@ -9,7 +9,6 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -24,7 +23,6 @@ from tests import trunk_cases as TC  # noqa: E402
 from tests import trunk_restatement as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 HDR = open(os.path.join(ROOT, "include", "pvnet_trunk.h")).read()
 FIXTURE = os.path.join(ROOT, "tests", "golden", "trunk.npz")
 BADARG, UNSUPPORTED = -1, -3
@@ -190,7 +188,7 @@ def test_refusals():
         T.fused_conv3x3(torch.zeros(1, 64, 4, 4), T.ConvParams.from_modules(*ok[:2]))
 
 
-# ---- 4. the two spellings of a block and the network ----------------------------------------------------------------------------------------
+# ---- 4. the two spellings of a block (the network class: tests/test_net_cpu.py) ------------------------------------------------------------
 def test_fused_basic_block_reads_both_spellings_and_refuses_the_rest():
     net = TC.standin()
     blk = T.FusedBasicBlock(net.l2[0])   # the stand-in's: c1, b1, c2, b2, down
@@ -217,68 +215,6 @@ def test_fused_basic_block_reads_both_spellings_and_refuses_the_rest():
     bottleneck.conv3 = nn.Conv2d(64, 256, 1)
     with pytest.raises(ValueError, match="neither"):
         T.FusedBasicBlock(bottleneck)
-    fused = T.FusedTrunkNet(net, layers=T.LAYERS)
-    assert set(fused.blocks) == set(T.LAYERS[:4]) and all(len(v) == 2 for v in fused.blocks.values())
-    assert (fused.fc_params.cin, fused.fc_params.co, fused.fc_params.act) == (512, 256, "relu")
-    assert (fused.conv8s_params.cin, fused.conv8s_params.co, fused.conv8s_params.act) == (384, 128, "leaky")
-    none = T.FusedTrunkNet(net, layers=())
-    assert len(none.blocks) == 0 and none.fc_params is None and none.conv8s_params is None
-    # with nothing named the trunk method is FusedStemNet's own, so the bits are; with anything named it is this class's
-    from pvnet_amd.stem import FusedStemNet
-    assert none._trunk.__func__ is FusedStemNet._trunk_piecewise and fused._trunk.__func__ is T.FusedTrunkNet._trunk_fused
-    assert T.FusedTrunkNet(net, layers=("fc",))._trunk.__func__ is T.FusedTrunkNet._trunk_fused
-    assert set(T.DEFAULT_LAYERS) <= set(T.LAYERS)
-    # float32 features on the CPU: the wrapped modules run, whatever is named
-    from tests.tail_cases import standin_features
-    x = torch.randn(1, 3, 32, 48)
-    with torch.no_grad():
-        assert torch.equal(T.FusedTrunkNet(net, layers=T.LAYERS, stem=False)._features(x), standin_features(net, x))
-
-
-REFERENCE_SCRIPT = r"""
-import sys, torch
-sys.path.insert(0, %(tools)r); sys.path.insert(0, %(root)r)
-import refshim
-refshim.install(%(ref)r)
-from tests import trunk_cases as TC
-from pvnet_amd import trunk as T
-mine = TC.standin()
-for k in [k for k in sys.modules if k == "lib" or k.startswith("lib.")]:
-    del sys.modules[k]                           # the repo's drop-in overlay package is also called `lib`
-sys.path.insert(0, %(ref)r)
-import lib.networks.resnet as R
-R.model_zoo.load_url = lambda *a, **k: {}        # no network here
-R.ResNet.load_state_dict = lambda self, sd, *a, **k: None
-from lib.networks.model_repository import Resnet18_8s
-ref = Resnet18_8s(ver_dim=18, seg_dim=2).eval()
-with torch.no_grad():
-    for a, b in zip(ref.parameters(), mine.parameters()):
-        a.copy_(b)
-    for a, b in zip(ref.buffers(), mine.buffers()):
-        a.copy_(b)
-Fr, Fm = T.FusedTrunkNet(ref, layers=T.LAYERS), T.FusedTrunkNet(mine, layers=T.LAYERS)
-for name in T.LAYERS[:4]:
-    for br, bm, blk in zip(Fr.blocks[name], Fm.blocks[name], getattr(ref.resnet18_8s, name)):
-        assert isinstance(blk, R.BasicBlock)     # the reference's own class
-        assert all(torch.equal(a, b) for a, b in zip((br.conv1.packed, br.conv1.bias, br.conv2.packed, br.conv2.bias),
-                                                     (bm.conv1.packed, bm.conv1.bias, bm.conv2.packed, bm.conv2.bias)))
-        assert (br.down is None) == (bm.down is None) and (br.down is None or torch.equal(br.down[0], bm.down[0]))
-assert torch.equal(Fr.fc_params.packed, Fm.fc_params.packed) and torch.equal(Fr.conv8s_params.packed, Fm.conv8s_params.packed)
-try:
-    T.FusedBasicBlock(R.Bottleneck(64, 16))
-    raise SystemExit("the Bottleneck was taken")
-except ValueError:
-    pass
-print("BOTH_SPELLINGS")
-"""
-
-
-def test_fused_trunk_net_takes_the_references_own_basic_block_where_its_tree_is_present():
-    if not os.path.isdir(REF):
-        pytest.skip("the reference tree is not present")
-    code = REFERENCE_SCRIPT % dict(tools=os.path.join(ROOT, "tools"), root=ROOT, ref=REF)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0 and "BOTH_SPELLINGS" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 # ---- 5. the restatement --------------------------------------------------------------------------------------------------------------------

@@ -301,59 +301,3 @@ def test_fused_basic_block_against_the_eager_block(T, kind):
     worst = float((np.abs(out.cpu().double().numpy() - ref) / (lim + 1e-6 * E2["A"])).max())
     print(f"FusedBasicBlock {kind} against the eager float64 module: worst ratio to the bar {worst:.3f}")
     assert (np.abs(out.cpu().double().numpy() - ref) <= lim + 1e-6 * E2["A"]).all()
-
-
-def test_fused_trunk_net_against_the_eager_standin_and_into_the_voting_layer(T):
-    from pvnet_amd import decoder, stem, voting
-    from tests.tail_cases import standin
-    net, x = standin()
-    assert tuple(x.shape) == (1, 3, 32, 48)
-    net, x = net.to(dev()), x.to(dev())
-    with torch.no_grad():
-        ref = torch.cat(net(x), 1).double()
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            eager = torch.cat(net(x), 1)
-    # e: what the EAGER network under the same autocast differs from the eager float32 network by
-    e = float((eager.double() - ref).abs().max())
-    # layers=(): FusedStemNet, bit for bit -- its own trunk method, so the same modules in the same order, then the same launches.  The
-    # wrapped modules are the convolution library's, whose default choice for two of the stand-in's bfloat16 convolutions at this
-    # size (l2[0].c2, l3[1].c2) does not return the same bits from one call to the next; asked for deterministic algorithms it does,
-    # and only then is any network equal to itself, let alone to another
-    none, plain = T.FusedTrunkNet(net, layers=(), stages=decoder.STAGES), stem.FusedStemNet(net, stages=decoder.STAGES)
-    assert none._trunk.__func__ is stem.FusedStemNet._trunk_piecewise and len(none.blocks) == 0
-    was = torch.backends.cudnn.deterministic
-    torch.backends.cudnn.deterministic = True
-    try:
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            a, b_ = torch.cat(none(x), 1), torch.cat(plain(x), 1)
-    finally:
-        torch.backends.cudnn.deterministic = was
-    assert a.dtype == b_.dtype == torch.bfloat16 and torch.equal(a, b_)
-    a = (a[:, :2], a[:, 2:])
-    fused = T.FusedTrunkNet(net, layers=T.LAYERS, stem=True, stages=decoder.STAGES)
-    assert fused._trunk.__func__ is T.FusedTrunkNet._trunk_fused
-    with torch.autocast("cuda", dtype=torch.bfloat16):
-        seg, ver = fused(x)
-    torch.cuda.synchronize()
-    assert tuple(seg.shape) == (1, 2, 32, 48) and tuple(ver.shape) == (1, 18, 32, 48) and seg.dtype == ver.dtype == torch.bfloat16
-    assert seg.untyped_storage().data_ptr() == ver.untyped_storage().data_ptr()   # views of one tensor
-    assert not torch.equal(seg, a[0])                                             # the fused pieces did run
-    d = float((torch.cat([seg, ver], 1).double() - ref).abs().max())
-    print(f"FusedTrunkNet, all six pieces, stand-in 1x3x32x48, autocast(bfloat16): eager differs from eager float32 by e = {e:.4e}, "
-          f"fused by {d:.4e} ({d / e:.2f} e; the bar is 2 e)")
-    # two differently ordered bfloat16 computations of the same function may each sit e from it
-    assert e > 0 and d <= 2 * e
-    # float32 features: the wrapped modules (the library has one tier) and the float32 tail, under FusedDecoderNet's bar
-    y32 = torch.cat(fused(x), 1)
-    assert y32.dtype == torch.float32 and torch.allclose(y32.double(), ref, atol=1e-5, rtol=1e-5)
-    # each piece alone stays under the bar too, and a piece not named runs its modules
-    for name in T.LAYERS:
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            one = torch.cat(T.FusedTrunkNet(net, layers=(name,), stages=decoder.STAGES)(x), 1)
-        assert float((one.double() - ref).abs().max()) <= 2 * e, name
-    with pytest.raises(ValueError):
-        T.FusedTrunkNet(net, layers=("layer5",))
-    # the views go into the voting layer unchanged
-    kp = voting.ransac_voting_layer_v3_from_logits(seg, voting._field_view(ver), 128, inlier_thresh=0.99)
-    torch.cuda.synchronize()
-    assert tuple(kp.shape) == (1, 9, 2)

@@ -74,7 +74,7 @@ def main():
     sides = {"layer1": (64, h4, w4), "layer2": (64, h4, w4), "layer3": (128, h8, w8), "layer4": (256, h8, w8)}
     for k, name in enumerate(T.LAYERS[:4]):
         c, h, w = sides[name]
-        seq, blocks, launches = everything._layers[k], everything.blocks[name], []
+        seq, blocks, launches = everything.parts.layers[k], everything.blocks[name], []
         for blk in blocks:
             launches.append((blk.conv1, h, w))
             h, w = T.out_sizes(h, w, blk.conv1.stride)
