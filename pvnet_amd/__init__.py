@@ -15,10 +15,11 @@ _TAIL = ("TailParams", "fused_tail", "FusedTailNet")   # pvnet_amd.tail, on firs
 _DECODER = ("StageParams", "fused_stage", "FusedDecoderNet")   # pvnet_amd.decoder, on first use
 _STEM = ("StemParams", "fused_stem", "FusedStemNet")   # pvnet_amd.stem, on first use
 _TRUNK = ("ConvParams", "fused_conv3x3", "FusedBasicBlock", "FusedTrunkNet")   # pvnet_amd.trunk, on first use
+_POSES = {"pnp_classes_device": "pnp", "MultiPoseEvalWrapper": "voting"}   # one pose per (image, class) behind the per-class vote, on first use
 _NET = ("FusedNet",)   # pvnet_amd.net, on first use: the network class the four Fused*Net names are presets of
 
 __all__ = ["ransac_voting_layer_v3", "generate_hypothesis", "voting_for_hypothesis", "load_library", *_TEXTURE, *_TAIL, *_DECODER, *_STEM,
-           *_TRUNK, *_NET]
+           *_TRUNK, *_NET, *_POSES]
 
 
 def __getattr__(name):
@@ -37,6 +38,9 @@ def __getattr__(name):
     if name in _TRUNK:
         from . import trunk
         return getattr(trunk, name)
+    if name in _POSES:
+        import importlib
+        return getattr(importlib.import_module("." + _POSES[name], __name__), name)
     if name in _NET:
         from . import net
         return getattr(net, name)

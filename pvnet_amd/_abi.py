@@ -260,6 +260,21 @@ SHADE_PROTOTYPES = {
                            DEPTH_PROTOTYPES["pvnet_render_depth"][1][18:]),
 }
 
+# ---- libpvnet_poses.so (include/pvnet_poses.h): the pose solve behind the per-class vote -- one pose per (image, class) in one launch,
+# absent classes gated by the vote's status; it takes E_* and S_SKIPPED above, and its weight kinds are POSE_W_* ---------------------------
+POSES_LIB_PATH = os.path.join(_HERE, "libpvnet_poses.so")
+POSES_ABI_VERSION = 1
+POSES_W_NONE, POSES_W_EXPLICIT, POSES_W_COV_F32 = 0, 1, 2
+assert (POSES_W_NONE, POSES_W_EXPLICIT, POSES_W_COV_F32) == (POSE_W_NONE, POSE_W_EXPLICIT, POSE_W_COV_F32)
+POSES_MAX_PN, POSES_MAX_CLASSES, POSES_MAX_ITEMS = 64, 63, 178956970
+POSES_ABSENT = -3   # status of an item whose vote was skipped: zeros returned
+POSES_PROTOTYPES = {
+    "pvnet_poses_abi_version": (_int, []),
+    # pts2d + float64? + strides[4], pts3d, weights + kind, K + per image?, vote_status, b, nk, pn, max_iterations, rt, poses, status,
+    # stream
+    "pvnet_pose_solve_classes": (_int, [_ptr, _int, _i64p, _ptr, _ptr, _int, _ptr, _int, _ptr] + [_int] * 4 + [_ptr] * 4),
+}
+
 # ---- libpvnet_decoder.so (include/pvnet_decoder.h): a decoder stage in one launch -- upsample, concat, 3 x 3 convolution, LeakyReLU; it
 # takes E_* above ----------------------------------------------------------------------------------------------------------------------------
 DECODER_LIB_PATH = os.path.join(_HERE, "libpvnet_decoder.so")
@@ -355,6 +370,7 @@ SIDE_LIBRARIES = {
     "raster": SideLibrary(RASTER_LIB_PATH, RASTER_ABI_VERSION, RASTER_PROTOTYPES),
     "depth": SideLibrary(DEPTH_LIB_PATH, DEPTH_ABI_VERSION, DEPTH_PROTOTYPES),
     "shade": SideLibrary(SHADE_LIB_PATH, SHADE_ABI_VERSION, SHADE_PROTOTYPES),
+    "poses": SideLibrary(POSES_LIB_PATH, POSES_ABI_VERSION, POSES_PROTOTYPES),
     "trunk": SideLibrary(TRUNK_LIB_PATH, TRUNK_ABI_VERSION, TRUNK_PROTOTYPES),
     "stem": SideLibrary(STEM_LIB_PATH, STEM_ABI_VERSION, STEM_PROTOTYPES),
     "decoder": SideLibrary(DECODER_LIB_PATH, DECODER_ABI_VERSION, DECODER_PROTOTYPES),
@@ -425,6 +441,7 @@ load_classes_library = functools.partial(_load_side, "classes")
 load_raster_library = functools.partial(_load_side, "raster")
 load_depth_library = functools.partial(_load_side, "depth")
 load_shade_library = functools.partial(_load_side, "shade")
+load_poses_library = functools.partial(_load_side, "poses")
 load_stem_library = functools.partial(_load_side, "stem")
 load_decoder_library = functools.partial(_load_side, "decoder")
 load_tail_library = functools.partial(_load_side, "tail")

@@ -22,7 +22,8 @@ CSRC = os.path.join(HERE, "csrc")
 VOTE_TU = ["k1_mask.hip", "k2_compact.hip", "k3_hypotheses.hip", "k4_score_valu.hip", "k4_score_mfma.hip", "k4_score_exact.hip",
            "k4_score_cull.hip", "k5_refine.hip", "epilogues.hip", "pose_solve.hip", "pose_metrics.hip", "vote_host.hip"]
 SRC = [os.path.join(CSRC, f) for f in VOTE_TU + ["pvnet_nn.hip", "pvnet_rccl.hip"]]
-DEPS = SRC + [os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "k4_exact_body.h"), os.path.join(CSRC, "pvnet_rng.h"),
+_POSE_CORE = os.path.join(CSRC, "pose_core.h")         # the one copy of the device pose solver: pose_solve.hip here and pose_classes.hip
+DEPS = SRC + [os.path.join(CSRC, "vote_common.h"), os.path.join(CSRC, "k4_exact_body.h"), os.path.join(CSRC, "pvnet_rng.h"), _POSE_CORE,
               os.path.join(ROOT, "include", "pvnet_vote.h"), os.path.join(ROOT, "include", "pvnet_nn.h")]
 LIB = os.path.join(HERE, "libpvnet_vote.so")          # release: the knobs are constants, the kernels the defaults reach
 DEV_LIB = os.path.join(HERE, "libpvnet_vote_dev.so")  # -DPVNET_DEV: environment knobs + every kernel variant (knob tests, fuzz, tuning tools)
@@ -47,6 +48,7 @@ SIDE_LIBRARIES = {
     "raster": (["raster.hip"], "pvnet_raster.h", [_MESH_CORE]),     # poses and meshes -> silhouettes and label images
     "depth": (["depth.hip"], "pvnet_depth.h", [_ZBUFFER_CORE]),     # ... -> depth, occlusion-correct labels, visible pixel counts
     "shade": (["shade.hip"], "pvnet_shade.h", [_ZBUFFER_CORE, _PIXEL_COLOR]),       # ... -> shaded vertex-colour images over a background
+    "poses": (["pose_classes.hip"], "pvnet_poses.h", [_POSE_CORE]),   # key-points per (image, class) -> a pose each, absent classes gated
     "trunk": (["trunk.hip"], "pvnet_trunk.h", []),               # a 3x3 conv of the residual trunk: BatchNorm, residual, activation fused
     "stem": (["stem.hip"], "pvnet_stem.h", []),                  # the network's stem in one launch: 7x7/2 conv, ReLU, 3x3/2 max-pool
     "decoder": (["decoder.hip"], "pvnet_decoder.h", []),         # a decoder stage in one launch: upsample, concat, 3x3 conv, LeakyReLU

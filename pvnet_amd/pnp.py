@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from ._abi import POSE_W_COV_F32, POSE_W_EXPLICIT, POSE_W_NONE, _check, load_library
+from ._abi import POSE_W_COV_F32, POSE_W_EXPLICIT, POSE_W_NONE, POSES_ABSENT, _check, load_library, load_poses_library
 
 _PNP_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpvnet_pnp.so")
 _pnp_lib = None
@@ -337,4 +337,104 @@ def pnp_batch_device(points_3d, points_2d, camera_matrix, weights_2d=None, covar
             C.c_void_p(X.data_ptr()), C.c_void_p(W.data_ptr()) if W is not None else None, kind, C.c_void_p(K.data_ptr()),
             per_image, n, pn, int(max_iterations), None, C.c_void_p(poses.data_ptr()), C.c_void_p(status.data_ptr()),
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_pose_solve")
+    return poses, status
+
+
+# ---- one pose per (image, class) behind the per-class vote (pvnet_amd/csrc/pose_classes.hip, include/pvnet_poses.h) ---------------
+POSE_ABSENT = POSES_ABSENT   # status of an (image, class) whose vote was skipped: a zero pose, nothing solved
+
+
+def stack_class_points(points_3d):
+    """the classes' object points as one array-like [nk,pn,3]: a tensor / array is returned as it is, a list of nk arrays [pn,3] is
+    stacked (float64 numpy) -- every class needs the same pn, because the field has one set of vn channels"""
+    import torch
+    if not isinstance(points_3d, (list, tuple)):
+        return points_3d
+    sets = [p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p) for p in points_3d]
+    if not sets or any(s.ndim != 2 or s.shape[1] != 3 for s in sets):
+        raise RuntimeError("points_3d must be [nk,pn,3], or a list of nk arrays [pn,3]")
+    if len({s.shape[0] for s in sets}) != 1:
+        raise RuntimeError(f"every class needs the same number of object points (the field has one set of channels), got "
+                           f"{[s.shape[0] for s in sets]}")
+    return np.stack([np.asarray(s, np.float64) for s in sets])
+
+
+def pnp_classes_device(points_3d, points_2d, camera_matrix, weights_2d=None, covariance=None, vote_status=None, max_iterations=200,
+                       out=None):
+    """``pnp_batch_device`` for the output of the per-class vote: one pose per (image, class) in ONE launch, one wavefront per item,
+    every class with object points of its own, enqueued on the current stream -- no synchronisation, no host copy.  A solved item has
+    the bits of ``pnp_batch_device(points_3d[k], points_2d[:, k], ...)``: both kernels compile one copy of the solver.
+
+    :param points_3d:     [nk,pn,3] object points per class, or a list of nk arrays [pn,3] (CUDA tensor, or numpy: uploaded here)
+    :param points_2d:     [b,nk,pn,2] float32 or float64 CUDA tensor, any strides (what ``ransac_voting_layer_v2`` returns is read
+                          in place)
+    :param camera_matrix: [3,3] shared, or [b,3,3] per image -- the classes of an image share it (CUDA tensor or numpy)
+    :param weights_2d:    None, or [b,nk,pn,3] (wxx, wxy, wyy) per key-point
+    :param covariance:    None, or [b,nk,pn,2,2] covariances, weighted as ``pnp_batch_device`` weights them
+    :param vote_status:   None, or int32 [b,nk,pn]: ``ransac_voting_layer_v2(..., return_status=True)``'s second output.  An item
+                          with ``S_SKIPPED`` in any of its words is ABSENT: nothing of it is read, its pose is zeros and its status
+                          ``POSE_ABSENT``.  Without it every item is solved
+    :param out:           None, or caller-owned ``(poses [b,nk,3,4] float64, status [b,nk] int32)`` contiguous CUDA tensors
+    :return: ``(poses [b,nk,3,4] float64, status [b,nk] int32)`` on the device: status = LM iterations (>= 0), ``POSE_FAILED`` (-2)
+             when the linear start failed (zeros), or ``POSE_ABSENT`` (-3).  ``poses.view(b * nk, 3, 4)`` with
+             ``class_ids = torch.arange(nk).repeat(b)`` is what ``evaluation.pose_metrics_device`` takes.
+    """
+    import torch
+    if not isinstance(points_2d, torch.Tensor):
+        raise RuntimeError("points_2d must be a CUDA tensor [b,nk,pn,2]")
+    if points_2d.dim() != 4 or points_2d.shape[3] != 2 or points_2d.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"points_2d must be float32 / float64 [b,nk,pn,2], got {points_2d.dtype} {tuple(points_2d.shape)}")
+    if weights_2d is not None and covariance is not None:
+        raise ValueError("give weights_2d or covariance, not both")
+    b, nk, pn = (int(s) for s in points_2d.shape[:3])
+    points_3d = stack_class_points(points_3d)
+    if tuple(np.shape(points_3d)) != (nk, pn, 3):
+        raise RuntimeError(f"points_3d must be [nk,pn,3]={(nk, pn, 3)}, got {tuple(np.shape(points_3d))}")
+    if not points_2d.is_cuda:
+        raise RuntimeError("points_2d must be a CUDA tensor [b,nk,pn,2] (there is no CPU fallback)")
+    dev = points_2d.device
+    X = _device_tensor(points_3d, dev, torch.float64, "points_3d")
+    K = _device_tensor(camera_matrix, dev, torch.float64, "camera_matrix")
+    if tuple(K.shape) == (3, 3):
+        per_image = 0
+    elif tuple(K.shape) == (b, 3, 3):
+        per_image = 1
+    else:
+        raise RuntimeError(f"camera_matrix must be [3,3] or [b,3,3]={(b, 3, 3)}, got {tuple(K.shape)}")
+    kind, W = POSE_W_NONE, None
+    if weights_2d is not None:
+        kind, W = POSE_W_EXPLICIT, _device_tensor(weights_2d, dev, torch.float64, "weights_2d")
+        if tuple(W.shape) != (b, nk, pn, 3):
+            raise RuntimeError(f"weights_2d must be [b,nk,pn,3]={(b, nk, pn, 3)}, got {tuple(W.shape)}")
+    elif covariance is not None:
+        kind, W = POSE_W_COV_F32, _device_tensor(covariance, dev, torch.float32, "covariance")
+        if tuple(W.shape) != (b, nk, pn, 2, 2):
+            raise RuntimeError(f"covariance must be [b,nk,pn,2,2]={(b, nk, pn, 2, 2)}, got {tuple(W.shape)}")
+    if vote_status is not None:
+        if not (isinstance(vote_status, torch.Tensor) and vote_status.is_cuda and vote_status.device == dev and
+                vote_status.dtype == torch.int32 and tuple(vote_status.shape) == (b, nk, pn)):
+            raise RuntimeError(f"vote_status must be an int32 CUDA tensor of shape {(b, nk, pn)} on {dev}")
+        vote_status = vote_status.contiguous()
+    if b * nk == 0 and out is None:
+        return torch.empty((b, nk, 3, 4), dtype=torch.float64, device=dev), torch.empty((b, nk), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        if out is None:
+            poses = torch.empty((b, nk, 3, 4), dtype=torch.float64, device=dev)
+            status = torch.empty((b, nk), dtype=torch.int32, device=dev)
+        else:
+            poses, status = out
+            if not (poses.is_cuda and poses.device == dev and poses.dtype == torch.float64 and poses.is_contiguous() and
+                    tuple(poses.shape) == (b, nk, 3, 4)):
+                raise RuntimeError(f"out[0] must be a contiguous float64 CUDA tensor of shape {(b, nk, 3, 4)} on {dev}")
+            if not (status.is_cuda and status.device == dev and status.dtype == torch.int32 and status.is_contiguous() and
+                    tuple(status.shape) == (b, nk)):
+                raise RuntimeError(f"out[1] must be a contiguous int32 CUDA tensor of shape {(b, nk)} on {dev}")
+        if b * nk == 0:
+            return poses, status
+        _check(load_poses_library().pvnet_pose_solve_classes(
+            C.c_void_p(points_2d.data_ptr()), int(points_2d.dtype == torch.float64), (C.c_int64 * 4)(*points_2d.stride()),
+            C.c_void_p(X.data_ptr()), C.c_void_p(W.data_ptr()) if W is not None else None, kind, C.c_void_p(K.data_ptr()), per_image,
+            C.c_void_p(vote_status.data_ptr()) if vote_status is not None else None, b, nk, pn, int(max_iterations), None,
+            C.c_void_p(poses.data_ptr()), C.c_void_p(status.data_ptr()),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pvnet_pose_solve_classes")
     return poses, status

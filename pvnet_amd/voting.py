@@ -658,6 +658,74 @@ class PoseEvalWrapper(torch.nn.Module):
         return (poses, status, kpts, cov) if return_all else poses
 
 
+class MultiPoseEvalWrapper(torch.nn.Module):
+    """``PoseEvalWrapper`` for several objects: class logits (or a label image) and the field in, one pose per (image, class) out, on
+    the device.  The per-class vote (``ransac_voting_layer_v2_from_logits`` on logits, ``ransac_voting_layer_v2`` on labels) and then
+    ``pnp.pnp_classes_device`` on the same stream, gated by the vote's status: three enqueues, no synchronisation.  A class that is
+    not in an image (fewer than ``min_num`` pixels) has a zero pose and status ``pnp.POSE_ABSENT``; nothing is solved for it.
+
+    points_3d [nk,pn,3] (or a list of nk arrays [pn,3]) are the classes' object points, class k + 1 in row k, pn = the field's vn;
+    they and K [3,3] are uploaded once per device.  ``forward(..., K=Ks)`` takes per-image intrinsics [b,3,3] instead.
+
+    ``forward`` returns poses [b,nk,3,4] float64; with ``return_all=True`` ``(poses, status, kpts, vote_status)`` -- status [b,nk] as
+    ``pnp_classes_device``, kpts [b,nk,pn,2] and vote_status [b,nk,pn] as the vote returns them.  ``poses.view(b * nk, 3, 4)`` with
+    ``class_ids = torch.arange(nk).repeat(b)`` goes into ``evaluation.pose_metrics_device`` as it is.
+
+    Keyword-only: ``seed`` (the vote's), ``workspace`` and ``kpts_out`` (the vote's ``workspace`` and ``out``) and ``out`` (the solve's
+    ``(poses, status)``) are passed through, so that with all of them caller-owned the whole step can be captured in a graph.  The
+    uncertainty form (covariances per class) is not produced here; ``pnp_classes_device`` takes ``covariance`` from a caller who has
+    them."""
+
+    def __init__(self, points_3d, K, round_hyp_num=512, inlier_thresh=0.99, max_num=30000, min_num=5, max_iterations=200):
+        super().__init__()
+        import numpy as np
+        from . import pnp
+        points_3d = pnp.stack_class_points(points_3d)
+        if isinstance(points_3d, torch.Tensor):
+            points_3d = points_3d.detach().cpu().numpy()
+        self.points_3d = np.ascontiguousarray(points_3d, np.float64)
+        self.K = np.ascontiguousarray(K, np.float64)
+        if self.points_3d.ndim != 3 or self.points_3d.shape[0] < 1 or self.points_3d.shape[2] != 3:
+            raise RuntimeError(f"points_3d must be [nk,pn,3], got {self.points_3d.shape}")
+        if self.K.shape != (3, 3):
+            raise RuntimeError(f"K must be [3,3] (per-image intrinsics go to forward), got {self.K.shape}")
+        self.round_hyp_num, self.inlier_thresh, self.max_num, self.min_num = round_hyp_num, inlier_thresh, max_num, min_num
+        self.max_iterations = max_iterations
+        self._uploaded = {}
+
+    def _constants(self, dev):
+        if dev not in self._uploaded:
+            self._uploaded[dev] = (torch.from_numpy(self.points_3d).to(dev), torch.from_numpy(self.K).to(dev))
+        return self._uploaded[dev]
+
+    def forward(self, seg_pred_or_labels, vertex_pred, use_argmax=True, K=None, return_all=False, *, seed=None, workspace=None,
+                kpts_out=None, out=None):
+        from . import pnp
+        nk, pn = self.points_3d.shape[:2]
+        src = seg_pred_or_labels
+        if not (isinstance(src, torch.Tensor) and isinstance(vertex_pred, torch.Tensor)):
+            raise TypeError("seg_pred_or_labels and vertex_pred must be torch tensors")
+        if vertex_pred.dim() != 4 or vertex_pred.shape[1] != 2 * pn:
+            raise RuntimeError(f"vertex_pred must be [b,2 vn,h,w] with vn = {pn}, the classes' point count, got {tuple(vertex_pred.shape)}")
+        if use_argmax and not (src.dim() == 4 and src.shape[1] == nk + 1):
+            raise RuntimeError(f"seg_pred must be [b,C,h,w] with C = {nk + 1} (the classes and the background), got {tuple(src.shape)}")
+        if not use_argmax and src.dim() != 3:
+            raise RuntimeError(f"labels must be [b,h,w], got {tuple(src.shape)}")
+        if not (src.is_cuda and vertex_pred.is_cuda):
+            raise RuntimeError("seg_pred_or_labels and vertex_pred must be CUDA tensors (there is no CPU fallback)")
+        vertex_pred = _field_view(vertex_pred)
+        X, K0 = self._constants(vertex_pred.device)
+        K = K0 if K is None else K
+        kw = dict(inlier_thresh=self.inlier_thresh, min_num=self.min_num, max_num=self.max_num, seed=seed, return_status=True,
+                  workspace=workspace, out=kpts_out)
+        if use_argmax:
+            kpts, vote_status = ransac_voting_layer_v2_from_logits(src, vertex_pred, self.round_hyp_num, **kw)
+        else:
+            kpts, vote_status = ransac_voting_layer_v2(src, vertex_pred, nk + 1, self.round_hyp_num, **kw)
+        poses, status = pnp.pnp_classes_device(X, kpts, K, vote_status=vote_status, max_iterations=self.max_iterations, out=out)
+        return (poses, status, kpts, vote_status) if return_all else poses
+
+
 def _ws_tail(L: Layout, max_num: int, ws: torch.Tensor):
     return [L.b, L.h, L.w, L.vn, L.hn, max_num, C.c_void_p(ws.data_ptr()), C.c_size_t(L.total_bytes),
             C.c_void_p(torch.cuda.current_stream(ws.device).cuda_stream)]
