@@ -22,7 +22,10 @@ extern "C" {
 /* Device pointers; only enqueues on `stream` (no allocation, no synchronisation).
  *   ref_pts [b,pn1,dim] f32, que_pts [b,pn2,dim] f32, idxs [b,pn2] i32 (output),
  *   workspace: pvnet_nearest_workspace_bytes(b, pn2) bytes, 256-byte aligned (one packed (distance, index) word per
- *   query, the running minimum over the reference tiles).
+ *   query, the running minimum over the reference tiles); read only when the reference cloud is split into more than
+ *   one slice, otherwise it may be null.
+ * pn1 may be 0 (an empty reference cloud): ref_pts is then not read and may be null, and every query answers index 0,
+ * as the reference's scan from `min_idx = 0` does.  pn2 must be at least 1.
  * Returns 0, a positive hipError_t, or a negative PVNET_E_* code (include/pvnet_vote.h). */
 size_t pvnet_nearest_workspace_bytes(int b, int pn2);
 int pvnet_nearest_point_idx(const float* ref_pts, const float* que_pts, int32_t* idxs, int b, int pn1, int pn2, int dim,

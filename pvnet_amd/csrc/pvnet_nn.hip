@@ -109,7 +109,9 @@ size_t pvnet_nearest_workspace_bytes(int b, int pn2) {
 
 int pvnet_nearest_point_idx(const float* ref_pts, const float* que_pts, int32_t* idxs, int b, int pn1, int pn2, int dim,
                             int exclude_self, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!ref_pts || !que_pts || !idxs || b <= 0 || pn1 < 0 || pn2 <= 0 || (dim != 2 && dim != 3)) return PVNET_E_BADARG;
+    // an empty reference cloud may come with a null pointer: with r1 == r0 the kernel's tile loop reads nothing of it
+    if ((!ref_pts && pn1 > 0) || !que_pts || !idxs || b <= 0 || pn1 < 0 || pn2 <= 0 || (dim != 2 && dim != 3))
+        return PVNET_E_BADARG;
     if (b > 65535) return PVNET_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int qblocks = (pn2 + NN_T - 1) / NN_T;
