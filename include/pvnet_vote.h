@@ -110,7 +110,9 @@ typedef struct PvnetVoteLayout {
     int32_t hn_pad;         /* hgroups * 64 * hpl                                                           */
     size_t off_ctrl;        /* int32 [b][8]: tn0, tn, status, item_base, nchunks, origin x, origin y, rho (float bits); then [8] global: total items,
                                (1,7) culling statistics, (2,3) stage-timer ticks, (4,5) band statistics (PVNET_F_BAND_STATS), (6) layout
-                               fingerprint; then int32 [b][vn][2] band origins, then int32 [b][vn] 1 = key-point disc-culled */
+                               fingerprint; then int32 [b][vn][2] band origins, then int32 [b][vn] 1 = key-point disc-culled, then
+                               int32 [8] the call's flags, then int32 [b][2] per image (1 = the compaction launch's origin block left
+                               this image's band origins, vote and rho before the hypothesis launch; the image's culling vote) */
     size_t off_bits;        /* uint64 [b][words]           foreground bit mask (as the mask has it: before thinning) */
     size_t off_pix;         /* int32  [b][cap]             linear pixel index y*w+x of compacted pixel t    */
     size_t off_rec;         /* float4 [b][vn][cap]         record (x, y, ux, uy): pixel and its RAW direction for the

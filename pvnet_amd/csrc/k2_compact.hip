@@ -6,13 +6,141 @@ namespace pvd {
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------
+// The ORIGIN block: one extra block per image of an exact-mode launch (vn <= KP_MAX).  What K3's blocks need to know about their
+// image -- per key-point the origin of the rounding band, the image's culling vote, band_rho(tn) -- depends on the image alone, and
+// until round 12 every one of the 37 blocks per image of the hypothesis launch worked it out for itself (kp_preamble) so that no
+// block had to wait for another.  This block works it out ONCE, before that launch starts, and it waits for nobody either: it
+// reads only what K1 left (segment counts, bit words) and the field itself.
+//   The estimate reads 17 slots of the image's pixel list (origin_slot(): eight fixed pairs + the median pixel).  An image that is
+// not thinned keeps every foreground pixel in raster order, so slot t is the t-th set bit of the mask: its segment from a scan of
+// the segment counts, its word from a scan of the segment's 64 popcounts, its bit by the popcount bisection of `locate` below.  The
+// pixels' directions come straight from the field with compact_kernel's own addressing (ld_elem<VT>, vs*, bi / src_div): bit for
+// bit the records the compaction blocks write beside this one -- exact-mode records keep the raw direction.  Then the arithmetic of
+// kp_origin_vote() (vote_common.h), which is what kp_preamble runs.
+//   A THINNED image (tn0 > max_num) keeps a random subset: its list is not the mask's.  The block clears OR_READY and K3's blocks
+// of that image run kp_preamble as before.  Dead images (tn0 < min_num, tn = 0) get origin (0, 0) and vote 0, as kp_preamble gives.
+// ------------------------------------------------------------------------------------------------------------
+template <int VT>
+__device__ __forceinline__ void origin_block(const VoteParams& P, int bi) {
+    __shared__ KpShared S;
+    __shared__ int s_sum[4];
+    __shared__ int s_seg[ORIGIN_SLOTS], s_rank[ORIGIN_SLOTS], s_pixel[ORIGIN_SLOTS];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int32_t* sg = P.seg0 + bi * P.nseg;
+    auto wave_scan = [&](int c) {   // inclusive, over the wave's lanes
+        int incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += t;
+        }
+        return incl;
+    };
+    int tot = 0;
+    for (int j = tid; j < P.nseg; j += 256) tot += sg[j];
+    tot = wave_reduce_add(tot);
+    if (lane == 0) s_sum[wave] = tot;
+    __syncthreads();
+    const int tn0 = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    int32_t* const ready = origin_ready_ptr(P, bi);
+    if (tn0 > P.max_num) {   // block-uniform: thinned
+        if (tid == 0) ready[OR_READY] = 0;
+        return;
+    }
+    const int usable = P.cap - PAD;
+    const int tn = tn0 < usable ? tn0 : usable;   // what the block of the last segment writes to C_TN
+    const bool live = tn0 >= P.min_num && tn > 0;
+    if (live) {   // block-uniform
+        if (tid < ORIGIN_SLOTS) s_seg[tid] = s_rank[tid] = s_pixel[tid] = 0;   // (every slot below is found exactly once: tn <= the sum of the counts)
+        // ---- the segment of every slot: thread = segment, 256 at a time; [excl, excl + c) are the list slots of its pixels
+        int carry = 0;
+        for (int j0 = 0; j0 < P.nseg; j0 += 256) {
+            __syncthreads();   // (s_sum of the previous trip / of the total has been read)
+            const int j = j0 + tid;
+            const int c = j < P.nseg ? sg[j] : 0;
+            const int incl = wave_scan(c);
+            if (lane == 63) s_sum[wave] = incl;
+            __syncthreads();
+            int excl = carry + incl - c;
+            for (int i = 0; i < wave; ++i) excl += s_sum[i];
+            if (c > 0)
+#pragma unroll 1   // (unrolled, the 17 slot ranks -- scalar values -- are kept across the whole block and scalar registers run out)
+                for (int s = 0; s < ORIGIN_SLOTS; ++s) {
+                    const int r = origin_slot(s, tn) - excl;
+                    if ((unsigned)r < (unsigned)c) {
+                        s_seg[s] = j;
+                        s_rank[s] = r;
+                    }
+                }
+            carry += s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+        }
+        __syncthreads();
+        // ---- the pixel of every slot: a wave per slot, lane = word of the slot's segment
+        const uint64_t* bw = P.bits + (size_t)bi * P.words;
+        for (int s = wave; s < ORIGIN_SLOTS; s += 4) {
+            const int wi = s_seg[s] * SEG_WORDS + lane;
+            const unsigned long long wd = wi < P.words ? bw[wi] : 0ull;
+            const int c = __popcll(wd);
+            int r = s_rank[s] - (wave_scan(c) - c);
+            if ((unsigned)r < (unsigned)c) {   // one lane: the bit of rank r in its word
+                int bitpos = 0;
+#pragma unroll
+                for (int st = 32; st > 0; st >>= 1) {
+                    const int cc = __popcll((wd >> bitpos) & ((1ull << st) - 1ull));
+                    const int take = ~((r - cc) >> 31);  // r >= cc
+                    bitpos += st & take;
+                    r -= cc & take;
+                }
+                s_pixel[s] = wi * 64 + bitpos;
+            }
+        }
+        __syncthreads();
+    }
+    // ---- candidate j of key-point kk: the records of slots j and NCAND + j, as the compaction blocks write them
+    const int kk = tid / NCAND, j = tid % NCAND;
+    const bool mine = tid < P.vn * NCAND;
+    float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+    int pm = 0;
+    if (live) {
+        pm = s_pixel[2 * NCAND];
+        if (mine) {
+            const int64_t vimg = (int64_t)(bi / P.src_div) * P.vs0 + (int64_t)kk * P.vs3;
+            const int pa = s_pixel[j], pb = s_pixel[NCAND + j];
+            const int ya = pa / P.w, xa = pa - ya * P.w;
+            const int yb = pb / P.w, xb = pb - yb * P.w;
+            const int64_t va = vimg + (int64_t)ya * P.vs1 + (int64_t)xa * P.vs2;
+            const int64_t vb = vimg + (int64_t)yb * P.vs1 + (int64_t)xb * P.vs2;
+            q0 = make_float4((float)xa, (float)ya, ld_elem<VT>(P.vertex, va), ld_elem<VT>(P.vertex, va + P.vs4));
+            q1 = make_float4((float)xb, (float)yb, ld_elem<VT>(P.vertex, vb), ld_elem<VT>(P.vertex, vb + P.vs4));
+        }
+    }
+    kp_origin_vote(P, tn, live, pm, mine, q0, q1, S);
+    if (tid < P.vn) {
+        int32_t* o = band_origin_ptr(P, (size_t)bi * P.vn + tid);
+        o[0] = S.org[tid * 2];
+        o[1] = S.org[tid * 2 + 1];
+    }
+    if (tid == 0) {
+        ready[OR_VOTE] = (P.cull && live && image_culled(S, P.vn)) ? 1 : 0;
+        P.ctrl[bi * CTRL_STRIDE + C_RHO] = (int)__float_as_uint(band_rho(tn));
+        ready[OR_READY] = 1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // K2: order-preserving compaction + direction gather          (ransac_voting_gpu.py:542-546)
+// One block per (segment, image, group of K2_KG key-points); an exact-mode launch (compact_origin()) has one more block per image
+// behind the segments', the origin block above.
 // ------------------------------------------------------------------------------------------------------------
 template <bool LITERAL, int K2_KG, int VT>  // K2_KG key-points per block: grid.z = ceil(vn / K2_KG); VT: field element type
 __global__ __launch_bounds__(256) void compact_kernel(VoteParams P) {
     if (K2_KG == 1) PVNET_SPARE_VGPRS(39); else if (K2_KG <= 3) PVNET_SPARE_VGPRS(47); else PVNET_SPARE_VGPRS(87);
     small_stage_prio();
     const int bi = blockIdx.y;
+    if (LITERAL && K2_KG == 3 && (int)blockIdx.x >= P.nseg) {   // block-uniform: the image's origin block (only launch_compact's exact-mode grid has it)
+        if (blockIdx.z == 0) origin_block<VT>(P, bi);
+        return;
+    }
     const int w0 = blockIdx.x * K2_WORDS_PER_BLOCK;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint64_t* bw = P.bits + (size_t)bi * P.words;
@@ -27,7 +155,7 @@ __global__ __launch_bounds__(256) void compact_kernel(VoteParams P) {
     // the image's foreground count (tn0) and the pixels kept before this block = sums over the segment counts
     // (<= a few hundred ints)
     const int32_t* sg = P.seg0 + bi * P.nseg;
-    const bool last = blockIdx.x == gridDim.x - 1;
+    const bool last = (int)blockIdx.x == P.nseg - 1;
     if (!last && sg[blockIdx.x] == 0) return;  // block-uniform: most of the image is background
     int part = 0, tot = 0;
     for (int j = threadIdx.x; j < P.nseg; j += 256) {
@@ -185,7 +313,10 @@ __global__ __launch_bounds__(256) void compact_kernel(VoteParams P) {
 
 int launch_compact(const VoteParams& P, hipStream_t s, bool literal, int kg) {
     dim3 grid(P.nseg, P.b, (P.vn + kg - 1) / kg);
-    const dim3 g3(P.nseg, P.b, (P.vn + 2) / 3);
+    // the calls whose K3 blocks look for stored band origins (hypothesis_kernel's kp_origin) get the origin block: one more column of
+    // blocks, of which the one at z = 0 works and the others leave at once
+    const bool origin = !literal && P.mode && P.exact && P.vn <= KP_MAX;
+    const dim3 g3(P.nseg + (origin ? 1 : 0), P.b, (P.vn + 2) / 3);
     (void)grid;
 #ifdef PVNET_DEV
 #define PV_K2(VT)                                                                                                  \

@@ -20,7 +20,8 @@ __device__ __forceinline__ int plan_item_count(const VoteParams& P, int j, int* 
 
 
 // culled: the disc-culling body of the scoring launch scores this image's key-points (their items carry the mark)
-__device__ __forceinline__ void plan_image(const VoteParams& P, int bi, bool culled) {
+// rho_here: K2's origin block did not leave C_RHO for this image (a thinned image, or a call without band origins)
+__device__ __forceinline__ void plan_image(const VoteParams& P, int bi, bool culled, bool rho_here) {
     constexpr int NT = 256;
     __shared__ int s_part[NT / 64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -42,8 +43,8 @@ __device__ __forceinline__ void plan_image(const VoteParams& P, int bi, bool cul
         P.ctrl[bi * CTRL_STRIDE + C_OX] = pm % P.w;
         P.ctrl[bi * CTRL_STRIDE + C_OY] = pm / P.w;
         if (!nch) P.ctrl[bi * CTRL_STRIDE + C_STATUS] |= PVNET_S_SKIPPED;
-        P.ctrl[bi * CTRL_STRIDE + C_RHO] = (int)__float_as_uint(band_rho(tn));   // (the scoring kernels' staging: a scalar load per item instead of a
-                                                                                  //  correctly rounded square root per item and wave)
+        if (rho_here)   // (the scoring kernels' staging: a scalar load per item instead of a correctly rounded square root per item and wave)
+            P.ctrl[bi * CTRL_STRIDE + C_RHO] = (int)__float_as_uint(band_rho(tn));
         if (culled && n > 0) call_flags_ptr(P)[CF_ANY_CULLED] = 1;   // (zeroed by K2; every writer writes the same)
         if (bi == P.b - 1) {
             P.ctrl[P.b * CTRL_STRIDE] = base + n;  // total number of work items
@@ -65,9 +66,10 @@ __device__ __forceinline__ void plan_image(const VoteParams& P, int bi, bool cul
 
 // ------------------------------------------------------------------------------------------------------------
 // K3: hypotheses                                               (ransac_voting_gpu.py:547,554; kernel.cu:11-49)
-// One launch, three kinds of block per image (all of image bi on XCD bi % 8): ceil(hn vn / 256) blocks of one thread per (hypothesis,
-// key-point); one block that plans the scoring work items; and, where the layout supports disc culling, one block per key-point
-// that -- IF that key-point is culled -- sorts its hypotheses along a Hilbert curve and describes every tile of 32 by a disc.
+// One launch, three kinds of block per image (all of image bi on XCD bi % 8): vn ceil(hn / 256) blocks of one thread per hypothesis
+// of ONE key-point (the key-point's record, hypothesis, count and column bases and its band origin are scalar); one block that plans
+// the scoring work items; and, where the layout supports disc culling, one block per key-point that -- IF that key-point is culled
+// -- sorts its hypotheses along a Hilbert curve and describes every tile of 32 by a disc.
 // ------------------------------------------------------------------------------------------------------------
 // position of (x, y) on the Hilbert curve of a 2^bits x 2^bits grid (consecutive positions are neighbouring cells)
 __device__ __forceinline__ uint32_t hilbert_index(uint32_t x, uint32_t y, int bits) {
@@ -84,8 +86,9 @@ __device__ __forceinline__ uint32_t hilbert_index(uint32_t x, uint32_t y, int bi
 }
 
 
-// What every K3 block works out for itself about its image before anything else (cheap -- 8 vn intersections -- and no block then
-// waits for another): per key-point the ORIGIN of the exact mode's rounding band and whether the key-point is DISC-CULLED.
+// What every K3 block needs to know about its image before anything else: per key-point the ORIGIN of the exact mode's rounding band
+// and whether the key-point is DISC-CULLED.  K2's origin block leaves both in ctrl (origin_ready_ptr()) for every image that is not
+// thinned; the blocks of a thinned image work them out for themselves (8 vn intersections, and no block then waits for another).
 //   origin   eight candidate intersections from FIXED pixel pairs spread over the foreground list (records t and t + tn / 2), their
 //            component-wise median, rounded to integers.  It only scales the band -- no result depends on it -- so a bad estimate
 //            (fewer than three usable candidates: the image's median pixel instead) costs re-evaluations, never correctness.
@@ -101,82 +104,20 @@ __device__ __forceinline__ uint32_t hilbert_index(uint32_t x, uint32_t y, int bi
 //            Any choice gives the same counts; a wrong one only costs time.
 //            (Round 6 also tried the candidates' medians and ranks through lane shuffles instead of LDS + barriers: ds_bpermute made
 //            the preamble 5 k cycles longer, quad permutes + ds_swizzle 2 k -- r07a, r07b; the LDS form stays.)
-struct KpShared {
-    float cand[KP_MAX * NCAND * 2];
-    float med[KP_MAX * 2];
-    int org[KP_MAX * 2];
-    int vote[KP_MAX];      // 1: this key-point's candidates say "cull"
-};
-__device__ __forceinline__ bool image_culled(const KpShared& S, int vn) {   // (after kp_preamble's last barrier; every thread the same)
-    int votes = 0;
-    for (int kk = 0; kk < vn; ++kk) votes += S.vote[kk];
-    return 2 * votes > vn;
-}
+// (KpShared, image_culled() and the arithmetic itself, kp_origin_vote(): vote_common.h -- shared with K2's origin block, which works
+//  the same answer out ONCE per image before this launch starts wherever the image is not thinned; kp_preamble is what every block
+//  of a thinned image still runs for itself)
 __device__ __forceinline__ void kp_preamble(const VoteParams& P, int bi, int tn, bool live, KpShared& S) {
     int pm = 0;
     if (live) pm = P.pix[(size_t)bi * P.cap + tn / 2];
     const int kk = threadIdx.x / NCAND, j = threadIdx.x % NCAND;
     const bool mine = (int)threadIdx.x < P.vn * NCAND;
-    if (mine) {
-        float cx = __uint_as_float(0x7FC00000u), cy = cx;   // NaN = no candidate
-        if (live) {
-            const int ta = (int)(((long long)(2 * j + 1) * tn) >> 4);
-            int tb = ta + tn / 2;
-            tb = tb >= tn ? tb - tn : tb;
-            const float4 q0 = P.rec[((size_t)bi * P.vn + kk) * P.cap + ta], q1 = P.rec[((size_t)bi * P.vn + kk) * P.cap + tb];
-            float hx0, hy0;
-            hyp_intersect(q0.z, q0.w, q0.x, q0.y, q1.z, q1.w, q1.x, q1.y, hx0, hy0);
-            if ((hx0 != 0.f || hy0 != 0.f) && fabsf(hx0) < 1048576.f && fabsf(hy0) < 1048576.f) { cx = hx0; cy = hy0; }
-        }
-        S.cand[threadIdx.x * 2] = cx;
-        S.cand[threadIdx.x * 2 + 1] = cy;
+    float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
+    if (mine && live) {
+        q0 = P.rec[((size_t)bi * P.vn + kk) * P.cap + origin_slot(j, tn)];
+        q1 = P.rec[((size_t)bi * P.vn + kk) * P.cap + origin_slot(NCAND + j, tn)];
     }
-    __syncthreads();
-    // median by rank, one thread per candidate (no arrays in registers: this kernel's small VGPR allocation is what lets two of
-    // its workgroups start beside a resident scoring kernel): candidate j is the median of a coordinate when n / 2 valid
-    // ones sort before it (NaN compares false: never counted, never the median)
-    const float* cand = S.cand + (mine ? kk : 0) * NCAND * 2;
-    int n = 0;
-    if (mine) {
-        int rx = 0, ry = 0;
-        const float vx = cand[2 * j], vy = cand[2 * j + 1];
-        for (int m2 = 0; m2 < NCAND; ++m2) {
-            const float ux = cand[2 * m2], uy = cand[2 * m2 + 1];
-            n += ux == ux ? 1 : 0;
-            rx += (ux < vx || (ux == vx && m2 < j)) ? 1 : 0;
-            ry += (uy < vy || (uy == vy && m2 < j)) ? 1 : 0;
-        }
-        if (vx == vx && rx == n / 2) S.med[kk * 2] = vx;
-        if (vy == vy && ry == n / 2) S.med[kk * 2 + 1] = vy;
-    }
-    __syncthreads();
-    if (mine && n >= 3) {   // the candidates' spread: the median of their (Chebyshev) distances from the median point
-        const float mx = S.med[kk * 2], my = S.med[kk * 2 + 1];
-        const float dj = fmaxf(fabsf(cand[2 * j] - mx), fabsf(cand[2 * j + 1] - my));
-        int rank = 0;
-        for (int m2 = 0; m2 < NCAND; ++m2) {
-            const float d2 = fmaxf(fabsf(cand[2 * m2] - mx), fabsf(cand[2 * m2 + 1] - my));
-            rank += (d2 < dj || (d2 == dj && m2 < j)) ? 1 : 0;
-        }
-        if (dj == dj && rank == n / 2) {
-            // Is the key-point a better origin than the median pixel?  With hypotheses spread S about it, at distance D from
-            // the object (radius Ro), the band bound (R + rho)(1 + r / rho) is about (S + rho)(1 + (D + Ro) / rho) there and
-            // (D + S + rho)(1 + Ro / rho) about the median pixel: take the smaller.  (Fields whose lines are nearly parallel
-            // scatter their intersections over 1e5 px: S ~ D -- the median pixel; the benchmark field: S ~ 3 px -- the key-point.)
-            const float rho = band_rho(tn), ro = rho * (1.f / 0.6f);
-            const float dist = fmaxf(fabsf(mx - (float)(pm % P.w)), fabsf(my - (float)(pm / P.w)));
-            const bool kp = (dj + rho) * (1.f + (dist + ro) / rho) < (dist + dj + rho) * (1.f + ro / rho);
-            S.org[kk * 2] = kp ? (int)rintf(mx) : pm % P.w;
-            S.org[kk * 2 + 1] = kp ? (int)rintf(my) : pm / P.w;
-        }
-        if (dj == dj && rank == (n / 2 > n - 2 ? n / 2 : n - 2))   // the largest distance but one (n <= 4: the median one)
-            S.vote[kk] = P.cull == 1 || (P.cull == 2 && dj <= P.cull_q * band_rho(tn) * P.tau) ? 1 : 0;
-    } else if (mine && j == 0) {   // fewer than three usable candidates
-        S.org[kk * 2] = pm % P.w;
-        S.org[kk * 2 + 1] = pm / P.w;
-        S.vote[kk] = (P.cull == 1 && live) ? 1 : 0;
-    }
-    __syncthreads();
+    kp_origin_vote(P, tn, live, pm, mine, q0, q1, S);
 }
 
 // The block of a CULLED key-point: generates the key-point's hypotheses once more (the same draws, the same arithmetic as the
@@ -227,7 +168,7 @@ __device__ __forceinline__ void cull_block_load(const VoteParams& P, int bi, int
 }
 // (requesting the first records before the preamble -- the block is one chain of dependent waits -- gained nothing for a culled call
 //  and cost a call without culled key-points 0.5 us: r06l)
-__device__ __forceinline__ void cull_block(const VoteParams& P, int bi, int k, int tn, const KpShared& S, float2* s_h, uint32_t* s_key,
+__device__ __forceinline__ void cull_block(const VoteParams& P, int bi, int k, int tn, int org_x, int org_y, float2* s_h, uint32_t* s_key,
                                            long long k3_t0) {
     constexpr int NT = 256, E = CULL_HN / NT;
     const int tid = threadIdx.x;
@@ -238,7 +179,7 @@ __device__ __forceinline__ void cull_block(const VoteParams& P, int bi, int k, i
 #endif
     PV_K3_STAMP(0);   // preamble done
     const float rho = band_rho(tn);
-    const float ox = (float)S.org[k * 2], oy = (float)S.org[k * 2 + 1];
+    const float ox = (float)org_x, oy = (float)org_y;
     // ---- this key-point's hypotheses (kernel.cu:11-49), caller order: thread t takes h = t, t + 256, ...; two pairs of records in
     //      flight at a time (three do not fit the kernel's 40 registers), the next requested as soon as a pair has been consumed
     static_assert(E == 4, "cull_block: four hypotheses per thread");
@@ -405,7 +346,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(20))) void hypo
     // Workgroups go to the 8 XCDs round-robin by linear id; every block of image bi is placed on XCD bi % 8 so that
     // the two random 16-byte record reads per hypothesis (several per 128-byte line of the image's records) hit
     // that XCD's L2 after the first touch instead of crossing the fabric once per XCD.
-    const int nbd = (P.hn * P.vn + 255) / 256;               // hypothesis blocks per image
+    const int nhb = (P.hn + 255) / 256;                      // hypothesis blocks per key-point
+    const int nbd = nhb * P.vn;                              // hypothesis blocks per image
     const int nb = nbd + 1 + (!LITERAL && P.cull ? P.vn : 0);   // + the plan block + one block per key-point that may be culled
     const int slot = blockIdx.x >> 3;
     const int bi = (slot / nb) * 8 + (blockIdx.x & 7);
@@ -426,25 +368,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(20))) void hypo
     if (!LITERAL && blk > nbd && !batch_ok) return;
     __shared__ KpShared S;
     const bool kp_origin = !LITERAL && P.mode && P.exact && P.vn <= KP_MAX;   // block-uniform
-    // the thread's own hypothesis: its two records are requested NOW, so that they travel while the origin is worked out
-    const int i = blk * 256 + threadIdx.x;
-    const int hh = i / P.vn, hk = i - hh * P.vn;
+    // K2's origin block left this image's origins, vote and C_RHO (block-uniform scalar loads; every image that is not thinned)
+    const bool ready = kp_origin && origin_ready_ptr(P, bi)[OR_READY] != 0;
+    // the block's key-point (uniform) and the thread's own hypothesis of it: its two records are requested NOW, so that they travel
+    // while the origin is fetched or worked out.  The draw counter stays (h vn + k) 2 + j: every hypothesis is what it always was.
+    const int kb = blk < nbd ? blk / nhb : (blk > nbd ? blk - nbd - 1 : 0);
+    const size_t bk = (size_t)bi * P.vn + kb;
+    const int h = (blk - kb * nhb) * 256 + (int)threadIdx.x;
+    const bool own = blk < nbd && h < P.hn;
     float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
-    if (blk < nbd && live && i < P.hn * P.vn) {
+    if (own && live) {
         int t0, t1;
-        draw_pair(P, bi, i, tn, t0, t1);
-        q0 = P.rec[((size_t)bi * P.vn + hk) * P.cap + t0];  // (x, y, direction) of the two pixels
-        q1 = P.rec[((size_t)bi * P.vn + hk) * P.cap + t1];
+        draw_pair(P, bi, h * P.vn + kb, tn, t0, t1);
+        const float4* const rk = P.rec + bk * P.cap;
+        q0 = rk[t0];  // (x, y, direction) of the two pixels
+        q1 = rk[t1];
     }
-    if (kp_origin) {
+    int org_x = 0, org_y = 0;   // the band origin of key-point kb (block-uniform)
+    bool votes = false;
+    if (ready) {
+        const int32_t* const o = band_origin_ptr(P, bk);
+        org_x = o[0];
+        org_y = o[1];
+        votes = origin_ready_ptr(P, bi)[OR_VOTE] != 0;
+        if (blk == 0 && (int)threadIdx.x < P.vn)   // (the batch gate is this launch's to apply: K2 decides it while the origin block runs)
+            *kp_cull_ptr(P, (size_t)bi * P.vn + threadIdx.x) = (votes && batch_ok) ? 1 : 0;
+    } else if (kp_origin) {
         kp_preamble(P, bi, tn, live, S);
         if (blk == 0 && (int)threadIdx.x < P.vn) {   // for the scoring kernel's staging (a_rows_exact) and the epilogues
-            const size_t bk = (size_t)bi * P.vn + threadIdx.x;
-            int32_t* o = band_origin_ptr(P, bk);
+            const size_t bt = (size_t)bi * P.vn + threadIdx.x;
+            int32_t* o = band_origin_ptr(P, bt);
             o[0] = S.org[threadIdx.x * 2];
             o[1] = S.org[threadIdx.x * 2 + 1];
-            *kp_cull_ptr(P, bk) = (P.cull && live && batch_ok && image_culled(S, P.vn)) ? 1 : 0;
+            *kp_cull_ptr(P, bt) = (P.cull && live && batch_ok && image_culled(S, P.vn)) ? 1 : 0;
         }
+        org_x = S.org[kb * 2];
+        org_y = S.org[kb * 2 + 1];
+        votes = P.cull && live && image_culled(S, P.vn);
     } else if (!LITERAL && P.mode && P.exact && blk == 0) {   // more than KP_MAX key-points: the image's median pixel for all of them
         int pm = 0;
         if (live) pm = P.pix[(size_t)bi * P.cap + tn / 2];
@@ -457,46 +417,60 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(20))) void hypo
     }
     // (fill_params: P.cull implies the exact mode and vn <= KP_MAX) this image's key-points go to the scoring launch's disc-culling body
     // -- when the image's key-points vote for it AND the previous batch's majority did (CF_BATCH_OK, vote_common.h)
-    const bool votes = !LITERAL && P.cull && kp_origin && live && image_culled(S, P.vn);
     const bool culling = votes && batch_ok;
     if (blk == nbd) {      // one extra block per image plans its scoring work items (consumed by the next launches only)
         if (votes && P.cull == 2 && threadIdx.x == 0) atomicAdd(call_flags_ptr(P) + CF_VOTES_NOW, 1);
-        plan_image(P, bi, culling);
+        plan_image(P, bi, culling, !ready);
         return;
     }
-    if (blk > nbd) {       // the block of key-point blk - nbd - 1: sorted operands and tile discs, if that key-point is culled
+    if (blk > nbd) {       // the block of key-point kb: sorted operands and tile discs, if that key-point is culled
         __shared__ float2 s_h[CULL_HN];
         __shared__ uint32_t s_key[CULL_HN];
-        const int k = blk - nbd - 1;
-        if (culling) cull_block(P, bi, k, tn, S, s_h, s_key, k3_t0);   // (block-uniform)
+        if (culling) cull_block(P, bi, kb, tn, org_x, org_y, s_h, s_key, k3_t0);   // (block-uniform)
         return;
     }
-    if (i < P.hn * P.vn) {
-    const int h = hh, k = hk;
-    float hx = 0.f, hy = 0.f;
-    if (live) {
-        const float2 d0 = rec_dir(q0), d1 = rec_dir(q1);
-        hyp_intersect(d0.x, d0.y, q0.x, q0.y, d1.x, d1.y, q1.x, q1.y, hx, hy);
-    }
-    P.hyp[((size_t)bi * P.vn + k) * P.hn_pad + h] = make_float2(hx, hy);
-    if (P.atomic_counts) P.counts[((size_t)bi * P.vn + k) * P.hn_pad + h] = 0;  // K4 accumulates into it
-    if (!LITERAL && P.mode && !culling) {  // the same hypothesis about the band origin, as a bf16x3 B operand column
-        float ox = 0.f, oy = 0.f;                         // (a culled key-point's columns are written, in sorted order, by its own block)
-        if (kp_origin) {
-            ox = (float)S.org[k * 2];
-            oy = (float)S.org[k * 2 + 1];
-        } else if (live) {
-            const int pm = P.pix[(size_t)bi * P.cap + tn / 2];  // the origin plan_image() records for this image
-            ox = (float)(pm % P.w);
-            oy = (float)(pm / P.w);
+    float2* const hyp_k = P.hyp + bk * P.hn_pad;
+    int32_t* const counts_k = P.counts + bk * P.hn_pad;
+    uint4* const hypb_k = P.hypb + bk * P.hn_pad * 2;
+    const bool columns = !LITERAL && P.mode && !culling;   // (a culled key-point's columns are written, in sorted order, by its own block)
+    if (own) {
+        float hx = 0.f, hy = 0.f;
+        if (live) {
+            const float2 d0 = rec_dir(q0), d1 = rec_dir(q1);
+            hyp_intersect(d0.x, d0.y, q0.x, q0.y, d1.x, d1.y, q1.x, q1.y, hx, hy);
         }
-        uint4 lo, hi;
-        if (P.exact) b_col_exact(hx - ox, hy - oy, band_rho(tn), P.kband, lo, hi);
-        else b_col(hx - ox, hy - oy, lo, hi);
-        uint4* o = P.hypb + (((size_t)bi * P.vn + k) * P.hn_pad + h) * 2;
-        o[0] = lo;
-        o[1] = hi;
+        hyp_k[h] = make_float2(hx, hy);
+        if (P.atomic_counts) counts_k[h] = 0;  // K4 accumulates into it
+        if (columns) {  // the same hypothesis about the band origin, as a bf16x3 B operand column
+            float ox = (float)org_x, oy = (float)org_y;
+            if (!kp_origin && live) {
+                const int pm = P.pix[(size_t)bi * P.cap + tn / 2];  // the origin plan_image() records for this image
+                ox = (float)(pm % P.w);
+                oy = (float)(pm / P.w);
+            }
+            uint4 lo, hi;
+            if (P.exact) {
+                const float rho = ready ? __uint_as_float((unsigned)P.ctrl[bi * CTRL_STRIDE + C_RHO]) : band_rho(tn);   // (the same bits)
+                b_col_exact(hx - ox, hy - oy, rho, P.kband, lo, hi);
+            } else {
+                b_col(hx - ox, hy - oy, lo, hi);
+            }
+            hypb_k[h * 2] = lo;
+            hypb_k[h * 2 + 1] = hi;
+        }
     }
+    // the key-point's last block also gives the padding columns hn .. hn_pad a defined content that never votes: the zero hypothesis,
+    // a zero count and the zero column (x = 0 for every live pixel: no vote; the scoring bodies drop the padding columns' flags).
+    // (block-uniform; no trip at all where hn = hn_pad, the benchmark's shape among them)
+    if (blk - kb * nhb == nhb - 1) {
+        for (int hp = P.hn + (int)threadIdx.x; hp < P.hn_pad; hp += 256) {
+            hyp_k[hp] = make_float2(0.f, 0.f);
+            if (P.atomic_counts) counts_k[hp] = 0;
+            if (columns) {
+                hypb_k[hp * 2] = make_uint4(0u, 0u, 0u, 0u);
+                hypb_k[hp * 2 + 1] = make_uint4(0u, 0u, 0u, pk(0u, 0x3F80u));
+            }
+        }
     }
 }
 
@@ -504,8 +478,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(20))) void hypo
 }  // namespace
 
 int launch_hypotheses(const VoteParams& P, hipStream_t s, bool literal) {
-    // per image: the hypothesis blocks, the plan block and -- where key-points may be disc-culled -- one block per key-point
-    dim3 grid((unsigned)(((P.hn * P.vn + 255) / 256 + 1 + (!literal && P.cull ? P.vn : 0)) * ((P.b + 7) / 8) * 8));
+    // per image: the hypothesis blocks of every key-point, the plan block and -- where key-points may be disc-culled -- one block per key-point
+    dim3 grid((unsigned)(((P.hn + 255) / 256 * P.vn + 1 + (!literal && P.cull ? P.vn : 0)) * ((P.b + 7) / 8) * 8));
     if (literal) hipLaunchKernelGGL(hypothesis_kernel<true>, grid, dim3(256), 0, s, P);
     else hipLaunchKernelGGL(hypothesis_kernel<false>, grid, dim3(256), 0, s, P);
     return 0;

@@ -19,7 +19,8 @@ __device__ constexpr float kF1e6 = 0x1.0c6f7ap-20f;
 
 constexpr int CTRL_STRIDE = 8;
 enum { C_TN0 = 0, C_TN = 1, C_STATUS = 2, C_ITEM_BASE = 3, C_NCHUNKS = 4, C_OX = 5, C_OY = 6,
-       C_RHO = 7 };   // band_rho(tn) as float bits: worked out once per image by the plan block, read by every scoring work item
+       C_RHO = 7 };   // band_rho(tn) as float bits: worked out once per image by K2's origin block (a thinned image: by K3's plan
+                      // block), read by every scoring work item
 
 constexpr int SEG_WORDS = 64;          // a segment = 64 words = 4096 pixels: the unit of K1 / K2 workgroups
 #ifndef PVNET_K1_WAVES
@@ -478,6 +479,100 @@ constexpr int NCAND = 8, KP_MAX = 32;      // candidate intersections per key-po
 // item descriptors; this copy is for the epilogues that read a finished workspace: band_margin_kernel, the debug views)
 __device__ __forceinline__ int32_t* kp_cull_ptr(const VoteParams& P, size_t bk) {
     return P.ctrl + (size_t)(P.b + 1) * CTRL_STRIDE + 2 * (size_t)P.b * P.vn + bk;
+}
+
+// per image, int32 [b][2] behind the call's flags: [OR_READY] 1 = K2's origin block (k2_compact.hip) left this image's band origins,
+// its culling vote and C_RHO before the hypothesis launch started -- K3's blocks read them instead of working them out; 0 = the image
+// is thinned (tn0 > max_num: the list K2 writes is not the mask's) and every K3 block runs kp_preamble for itself.  [OR_VOTE] the
+// image's culling vote (P.cull, the live gate and the key-points' majority folded in).  Written by every exact-mode call with
+// vn <= KP_MAX -- the calls whose K3 blocks read them; no other call looks.
+constexpr int OR_READY = 0, OR_VOTE = 1;
+__device__ __forceinline__ int32_t* origin_ready_ptr(const VoteParams& P, int bi) {
+    return P.ctrl + (size_t)(P.b + 1) * CTRL_STRIDE + 3 * (size_t)P.b * P.vn + 8 + 2 * (size_t)bi;
+}
+
+// The band origin and the culling vote of every key-point of ONE image (the text above kp_preamble in k3_hypotheses.hip says what
+// they are): worked out by one block of 256 threads, thread (kk, j) = (tid / NCAND, tid % NCAND) holding the two records q0, q1 of
+// candidate j of key-point kk (mine: tid < vn NCAND), pm = the image's median pixel.  Ends with a barrier: S.org and S.vote are whole.
+struct KpShared {
+    float cand[KP_MAX * NCAND * 2];
+    float med[KP_MAX * 2];
+    int org[KP_MAX * 2];
+    int vote[KP_MAX];      // 1: this key-point's candidates say "cull"
+};
+__device__ __forceinline__ bool image_culled(const KpShared& S, int vn) {   // (after kp_origin_vote's last barrier; every thread the same)
+    int votes = 0;
+    for (int kk = 0; kk < vn; ++kk) votes += S.vote[kk];
+    return 2 * votes > vn;
+}
+__device__ __forceinline__ void kp_origin_vote(const VoteParams& P, int tn, bool live, int pm, bool mine, const float4& q0, const float4& q1,
+                                               KpShared& S) {
+    const int kk = threadIdx.x / NCAND, j = threadIdx.x % NCAND;
+    if (mine) {
+        float cx = __uint_as_float(0x7FC00000u), cy = cx;   // NaN = no candidate
+        if (live) {
+            float hx0, hy0;
+            hyp_intersect(q0.z, q0.w, q0.x, q0.y, q1.z, q1.w, q1.x, q1.y, hx0, hy0);
+            if ((hx0 != 0.f || hy0 != 0.f) && fabsf(hx0) < 1048576.f && fabsf(hy0) < 1048576.f) { cx = hx0; cy = hy0; }
+        }
+        S.cand[threadIdx.x * 2] = cx;
+        S.cand[threadIdx.x * 2 + 1] = cy;
+    }
+    __syncthreads();
+    // median by rank, one thread per candidate (no arrays in registers: the hypothesis kernel's small VGPR allocation is what lets two
+    // of its workgroups start beside a resident scoring kernel): candidate j is the median of a coordinate when n / 2 valid
+    // ones sort before it (NaN compares false: never counted, never the median)
+    const float* cand = S.cand + (mine ? kk : 0) * NCAND * 2;
+    int n = 0;
+    if (mine) {
+        int rx = 0, ry = 0;
+        const float vx = cand[2 * j], vy = cand[2 * j + 1];
+        for (int m2 = 0; m2 < NCAND; ++m2) {
+            const float ux = cand[2 * m2], uy = cand[2 * m2 + 1];
+            n += ux == ux ? 1 : 0;
+            rx += (ux < vx || (ux == vx && m2 < j)) ? 1 : 0;
+            ry += (uy < vy || (uy == vy && m2 < j)) ? 1 : 0;
+        }
+        if (vx == vx && rx == n / 2) S.med[kk * 2] = vx;
+        if (vy == vy && ry == n / 2) S.med[kk * 2 + 1] = vy;
+    }
+    __syncthreads();
+    if (mine && n >= 3) {   // the candidates' spread: the median of their (Chebyshev) distances from the median point
+        const float mx = S.med[kk * 2], my = S.med[kk * 2 + 1];
+        const float dj = fmaxf(fabsf(cand[2 * j] - mx), fabsf(cand[2 * j + 1] - my));
+        int rank = 0;
+        for (int m2 = 0; m2 < NCAND; ++m2) {
+            const float d2 = fmaxf(fabsf(cand[2 * m2] - mx), fabsf(cand[2 * m2 + 1] - my));
+            rank += (d2 < dj || (d2 == dj && m2 < j)) ? 1 : 0;
+        }
+        if (dj == dj && rank == n / 2) {
+            // Is the key-point a better origin than the median pixel?  With hypotheses spread S about it, at distance D from
+            // the object (radius Ro), the band bound (R + rho)(1 + r / rho) is about (S + rho)(1 + (D + Ro) / rho) there and
+            // (D + S + rho)(1 + Ro / rho) about the median pixel: take the smaller.  (Fields whose lines are nearly parallel
+            // scatter their intersections over 1e5 px: S ~ D -- the median pixel; the benchmark field: S ~ 3 px -- the key-point.)
+            const float rho = band_rho(tn), ro = rho * (1.f / 0.6f);
+            const float dist = fmaxf(fabsf(mx - (float)(pm % P.w)), fabsf(my - (float)(pm / P.w)));
+            const bool kp = (dj + rho) * (1.f + (dist + ro) / rho) < (dist + dj + rho) * (1.f + ro / rho);
+            S.org[kk * 2] = kp ? (int)rintf(mx) : pm % P.w;
+            S.org[kk * 2 + 1] = kp ? (int)rintf(my) : pm / P.w;
+        }
+        if (dj == dj && rank == (n / 2 > n - 2 ? n / 2 : n - 2))   // the largest distance but one (n <= 4: the median one)
+            S.vote[kk] = P.cull == 1 || (P.cull == 2 && dj <= P.cull_q * band_rho(tn) * P.tau) ? 1 : 0;
+    } else if (mine && j == 0) {   // fewer than three usable candidates
+        S.org[kk * 2] = pm % P.w;
+        S.org[kk * 2 + 1] = pm / P.w;
+        S.vote[kk] = (P.cull == 1 && live) ? 1 : 0;
+    }
+    __syncthreads();
+}
+// the list slots of the estimate: candidate j pairs slot j with slot NCAND + j; slot 2 NCAND is the image's median pixel
+constexpr int ORIGIN_SLOTS = 2 * NCAND + 1;
+__device__ __forceinline__ int origin_slot(int s, int tn) {
+    if (s == 2 * NCAND) return tn / 2;
+    const int ta = (int)(((long long)(2 * (s & (NCAND - 1)) + 1) * tn) >> 4);
+    if (s < NCAND) return ta;
+    const int tb = ta + tn / 2;
+    return tb >= tn ? tb - tn : tb;
 }
 
 // Work items of a scoring launch owned by this workgroup.  Workgroups go to the 8 XCDs round-robin by linear id

@@ -97,9 +97,11 @@ int band_fold1(int forced) {
 // pvnet_vote_tuning_reload() may change between a vote and an epilogue that reads the vote's workspace.  Every vote stamps
 // the layout it used into ctrl's global row; the epilogue kernels compare it with the layout THEY were handed and answer NaN
 // instead of reading the old workspace at new offsets.
+constexpr uint64_t CTRL_BLOCK_REVISION = 2;   // 2: "origin ready" + vote words int32 [b][2] behind the call's flags (they fit the block's
+                                              // 256-byte padding at some shapes, so total_bytes alone would not tell)
 int layout_fingerprint(const PvnetVoteLayout& L) {
     uint64_t x = 0x9E3779B97F4A7C15ull;
-    const uint64_t v[] = {(uint64_t)L.chunk, (uint64_t)L.hpl, (uint64_t)L.wg_g, (uint64_t)L.reserved_, (uint64_t)L.cap,
+    const uint64_t v[] = {CTRL_BLOCK_REVISION, (uint64_t)L.chunk, (uint64_t)L.hpl, (uint64_t)L.wg_g, (uint64_t)L.reserved_, (uint64_t)L.cap,
                           (uint64_t)L.hn_pad, (uint64_t)L.off_rec, (uint64_t)L.off_hyp, (uint64_t)L.off_counts,
                           (uint64_t)L.off_win, (uint64_t)L.total_bytes, (uint64_t)L.cull, (uint64_t)L.off_perm, (uint64_t)L.off_hypc};
     for (uint64_t e : v) { x ^= e + 0x9E3779B97F4A7C15ull + (x << 6) + (x >> 2); }
@@ -398,8 +400,9 @@ int pvnet_vote_layout(int b, int h, int w, int vn, int hn, int max_num, PvnetVot
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
     L->nseg = (L->words + SEG_WORDS - 1) / SEG_WORDS;
     // ctrl rows [b + 1][8], then the exact mode's band origins int32 [b][vn][2] (band_origin_ptr()), then which key-points are
-    // disc-culled int32 [b][vn] (kp_cull_ptr()), then the call's flags int32 [8] (call_flags_ptr())
-    L->off_ctrl = take(sizeof(int32_t) * (CTRL_STRIDE * (size_t)(b + 1) + 3 * (size_t)b * vn + 8));
+    // disc-culled int32 [b][vn] (kp_cull_ptr()), then the call's flags int32 [8] (call_flags_ptr()), then per image "origin ready" and
+    // the culling vote int32 [b][2] (origin_ready_ptr(): left by K2's origin block, read by K3)
+    L->off_ctrl = take(sizeof(int32_t) * (CTRL_STRIDE * (size_t)(b + 1) + 3 * (size_t)b * vn + 8 + 2 * (size_t)b));
     // [2][b][nseg] int32 (the second array holds the mask's segment counts; the first is unused since round 2), then,
     // when thinning is possible (max_num < h*w), the segments' cumulative histograms uint16 [b][nseg][THIN_BINS]
     L->off_seg = take(align_up(sizeof(int32_t) * 2 * (size_t)b * L->nseg, 16) +
