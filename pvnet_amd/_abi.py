@@ -144,6 +144,22 @@ TARGETS_PROTOTYPES = {
     "pvnet_head_grad_kp": (_int, _KP_HEAD + [_ptr, _ptr, _i64p, _ptr, _i64p, _ptr, _ptr, _size, _ptr]),
 }
 
+# ---- libpvnet_class_targets.so (include/pvnet_class_targets.h): the same for label images -- hcoords [b,nk,vn,3] and weight_scale
+# [b,nk] per class, picked by the pixel's label; it takes the HEAD_F_* flags, TARGETS_F_MOTION and the HEAD_S_* bits above ----------------
+CLASS_TARGETS_LIB_PATH = os.path.join(_HERE, "libpvnet_class_targets.so")
+CLASS_TARGETS_ABI_VERSION = 1
+CLASS_TARGETS_MAX_CLASSES = 64   # classes including the background (CLASSES_MAX below, by value)
+CLASS_TARGETS_MAX_TABLE = 1024   # (classes - 1) * vn, at most
+CLASS_TARGETS_PROTOTYPES = {
+    "pvnet_class_targets_abi_version": (_int, []),
+    # pvnet_vertex_targets' arguments with class_num behind weight_scale
+    "pvnet_vertex_targets_classes": (_int, [_ptr, _int, _i64p, _f64p, _f32p] + [_int] * 5 + [C.c_uint32, _ptr, _i64p, _ptr, _i64p, _ptr]),
+    "pvnet_head_metrics_ckp_workspace_bytes": (_size, [_int] * 3),
+    "pvnet_head_metrics_ckp": (_int, list(TARGETS_PROTOTYPES["pvnet_head_metrics_kp"][1])),
+    "pvnet_head_grad_ckp_workspace_bytes": (_size, [_int] * 3),
+    "pvnet_head_grad_ckp": (_int, list(TARGETS_PROTOTYPES["pvnet_head_grad_kp"][1])),
+}
+
 # ---- libpvnet_augment.so (include/pvnet_augment.h): the augmentation of a training batch; it takes the MASK_* codes and E_* above ---
 AUGMENT_LIB_PATH = os.path.join(_HERE, "libpvnet_augment.so")
 AUGMENT_ABI_VERSION = 1
@@ -364,6 +380,7 @@ SIDE_LIBRARIES = {
     "head": SideLibrary(HEAD_LIB_PATH, HEAD_ABI_VERSION, HEAD_PROTOTYPES),
     "train": SideLibrary(TRAIN_LIB_PATH, TRAIN_ABI_VERSION, TRAIN_PROTOTYPES),
     "targets": SideLibrary(TARGETS_LIB_PATH, TARGETS_ABI_VERSION, TARGETS_PROTOTYPES),
+    "class_targets": SideLibrary(CLASS_TARGETS_LIB_PATH, CLASS_TARGETS_ABI_VERSION, CLASS_TARGETS_PROTOTYPES),
     "augment": SideLibrary(AUGMENT_LIB_PATH, AUGMENT_ABI_VERSION, AUGMENT_PROTOTYPES),
     "color": SideLibrary(COLOR_LIB_PATH, COLOR_ABI_VERSION, COLOR_PROTOTYPES),
     "classes": SideLibrary(CLASSES_LIB_PATH, CLASSES_ABI_VERSION, CLASSES_PROTOTYPES),
@@ -435,6 +452,7 @@ def _load_side(name: str) -> C.CDLL:
 load_head_library = functools.partial(_load_side, "head")
 load_train_library = functools.partial(_load_side, "train")
 load_targets_library = functools.partial(_load_side, "targets")
+load_class_targets_library = functools.partial(_load_side, "class_targets")
 load_augment_library = functools.partial(_load_side, "augment")
 load_color_library = functools.partial(_load_side, "color")
 load_classes_library = functools.partial(_load_side, "classes")

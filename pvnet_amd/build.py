@@ -41,6 +41,8 @@ SIDE_LIBRARIES = {
     "head": (["head_metrics.hip"], "pvnet_head.h", []),          # the head metrics of a validation step
     "train": (["head_grad.hip"], "pvnet_train.h", []),           # the backward of the head losses of a training step
     "targets": (["head_targets.hip"], "pvnet_targets.h", []),    # the targets from key-points, the head fused with them
+    "class_targets": (["class_targets.hip"], "pvnet_class_targets.h",   # the same from a label image and key-points per class
+                      [os.path.join(ROOT, "include", "pvnet_targets.h"), os.path.join(ROOT, "include", "pvnet_classes.h")]),
     "augment": (["augment.hip"], "pvnet_augment.h", [_AUGMENT_WARP]),   # the inputs of a training step: warp, normalise, key-points
     "color": (["color_jitter.hip"], "pvnet_color.h",              # the colour jitter, alone or fused behind that warp
               [_AUGMENT_WARP, os.path.join(ROOT, "include", "pvnet_augment.h")]),

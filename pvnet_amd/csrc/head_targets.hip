@@ -3,7 +3,7 @@
 //
 // The reference makes `vertex` and `vertex_weights` on the host, per sample (compute_vertex_hcoords, lib/datasets/linemod_dataset.py
 // :68-81 and :224-227), and ships 76 bytes per pixel to the device; both are a function of the mask and of 27 numbers per image.
-// kp_target below is that function for one pixel and one key-point; nothing else here makes a target.
+// kp_target (kp_target.h) is that function for one pixel and one key-point; nothing else here makes a target.
 //
 // This file holds the key-point target source, KpSource -- the policy of head_common.h's per-pixel bodies that computes a pixel's
 // weight and targets in registers where MemSource loads them --, the one kernel that writes the targets out, and the head's kernels
@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "head_common.h"
+#include "kp_target.h"
 #include "pvnet_targets.h"
 
 // no contraction: vx vx + vy vy and hx - x hz round as the reference's separate numpy operations do
@@ -56,22 +57,7 @@ using namespace pvh;
 #define KP_GRAD_FINAL_SPARE 31
 #define KP_GRAD_STATUS_SPARE 23
 
-// ---- THE definition (linemod_dataset.py:72-77): the target of the pixel (x, y) with mask == 1 for the key-point (hx, hy, hz).  Every
-//      operation is one IEEE float64 operation, in the reference's order; the result is rounded once to float32 ----------------------
-__device__ __forceinline__ void kp_target(double hx, double hy, double hz, int x, int y, bool motion, float& tx, float& ty) {
-    double vx = hx - (double)x * hz, vy = hy - (double)y * hz;
-    if (!motion) {
-        double n = sqrt(vx * vx + vy * vy);
-        if (n < 1e-3) n = n + 1e-3;
-        vx = vx / n;
-        vy = vy / n;
-    }
-    tx = (float)vx;
-    ty = (float)vy;
-}
-
-// the weight of a pixel: the mask's value as float32 (mask.float()) times the image's scale
-__device__ __forceinline__ float kp_weight(long long m, float scale) { return (float)m * scale; }
+// (THE definition of a target, kp_target, and the weight of a pixel, kp_weight: kp_target.h, shared with class_targets.hip)
 
 // ---- the key-point source: where the mask is, and the target source made of it (the interface is stated at MemSource) -------------
 struct KpSource {

@@ -12,6 +12,9 @@
   device from the mask and the loader's ``hcoords`` (the reference's ``compute_vertex_hcoords``, lib/datasets/linemod_dataset.py:68-81,
   bit for bit), either written out or computed in registers inside the head's forward and backward, which then never read a target
   (pvnet_amd/csrc/head_targets.hip, libpvnet_targets.so; C ABI and the definition: include/pvnet_targets.h).
+* ``vertex_targets_classes_device`` and the ``*_from_class_keypoints`` forms -- the same for images of several objects: the key-points
+  of a pixel are picked by its label (pvnet_amd/csrc/class_targets.hip, libpvnet_class_targets.so; the definition:
+  include/pvnet_class_targets.h).
 * ``ValStep`` -- the whole step on the current stream: head metrics, then ``voting.PoseEvalWrapper`` (fused arg-max voting and the
   pose solve), then the pose metrics ``Evaluator.evaluate_batch`` records (``evaluation.pose_metrics_device``); one host copy at the
   end.  ``enqueue`` is the part a graph captures.
@@ -23,8 +26,9 @@ from __future__ import annotations
 import torch
 
 from ._abi import (HEAD_F_LOGITS_BF16, HEAD_F_LOGITS_F16, HEAD_F_NT_ALL, HEAD_F_NT_NONE, HEAD_F_VERTEX_BF16,  # noqa: F401
-                   HEAD_F_VERTEX_F16, HEAD_S_BAD_LABEL, MASK_I32, MASK_I64, MASK_U8, TARGETS_F_MOTION, _check, load_head_library,
-                   load_targets_library, load_train_library)
+                   HEAD_F_VERTEX_F16, HEAD_S_BAD_LABEL, MASK_I32, MASK_I64, MASK_U8, TARGETS_F_MOTION, CLASS_TARGETS_MAX_CLASSES,
+                   CLASS_TARGETS_MAX_TABLE, _check, load_class_targets_library, load_head_library, load_targets_library,
+                   load_train_library)
 from ._marshal import nbytes as _nbytes, opt_strides as _opt_strides, ptr as _ptr, stream as _stream, strides as _strides, \
     workspace as _workspace
 
@@ -157,6 +161,12 @@ class HeadMetrics(torch.nn.Module):
         """the same four values from the loader's ``hcoords`` instead of the target field (``head_metrics_from_keypoints``)"""
         losses, _, _ = head_metrics_from_keypoints(seg_pred, vertex_pred, mask, hcoords, weight_scale, sigma=self.sigma,
                                                    use_motion=use_motion)
+        return tuple(losses.to(torch.float32).unbind(1))
+
+    def from_class_keypoints(self, seg_pred, vertex_pred, labels, hcoords, weight_scale=None, use_motion=False):
+        """the same four values from a label image and key-points per class (``head_metrics_from_class_keypoints``)"""
+        losses, _, _ = head_metrics_from_class_keypoints(seg_pred, vertex_pred, labels, hcoords, weight_scale, sigma=self.sigma,
+                                                         use_motion=use_motion)
         return tuple(losses.to(torch.float32).unbind(1))
 
 
@@ -325,21 +335,166 @@ def head_grad_from_keypoints(seg_pred, vertex_pred, mask, hcoords, upstream, wei
     return grad_seg, grad_vertex, status
 
 
+# ---- the targets of several objects: a label image and key-points per class (libpvnet_class_targets.so) ------------------------------
+def _class_keypoint_inputs(labels, hcoords, weight_scale, class_num=None):
+    """the checks the class key-point entries share -> (device, b, h, w, class_num, vn, hcoords [b,C-1,vn,3] float64 contiguous,
+    weight_scale [b,C-1] float32 or None).  ``class_num``: what the logits say C is, where there are logits."""
+    for name, t in (("labels", labels), ("hcoords", hcoords)) + ((("weight_scale", weight_scale),) if weight_scale is not None else ()):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name} must be a CUDA tensor (there is no CPU fallback)")
+    dev = labels.device
+    if labels.dim() != 3 or labels.dtype not in _MASK_CODES:
+        raise RuntimeError(f"labels must be [b,h,w], uint8, bool, int32 or int64, got {tuple(labels.shape)} {labels.dtype}")
+    b, h, w = (int(x) for x in labels.shape)
+    want = "[b,C-1,vn,3]" if class_num is None else f"[b,C-1,vn,3] with C-1={class_num - 1}"
+    if hcoords.device != dev or hcoords.dim() != 4 or hcoords.shape[0] != b or hcoords.shape[1] < 1 or hcoords.shape[2] < 1 or \
+            hcoords.shape[3] not in (2, 3) or hcoords.dtype not in (torch.float32, torch.float64) or \
+            (class_num is not None and hcoords.shape[1] != class_num - 1):
+        raise RuntimeError(f"hcoords must be {want} (or [b,C-1,vn,2]: hz = 1) float32 or float64 on {dev} with b={b}: row k holds the "
+                           f"key-points of class k + 1; got {tuple(hcoords.shape)} {hcoords.dtype}")
+    nk, vn = int(hcoords.shape[1]), int(hcoords.shape[2])
+    if nk + 1 > CLASS_TARGETS_MAX_CLASSES or nk * vn > CLASS_TARGETS_MAX_TABLE:
+        raise RuntimeError(f"hcoords [b,C-1,vn,3]: at most {CLASS_TARGETS_MAX_CLASSES} classes (the background counted) and "
+                           f"(C-1) * vn <= {CLASS_TARGETS_MAX_TABLE}, got C-1={nk}, vn={vn}")
+    hc = hcoords.to(torch.float64)   # (float32 widens exactly)
+    if hc.shape[3] == 2:
+        hc = torch.cat([hc, torch.ones_like(hc[..., :1])], 3)
+    hc = hc.contiguous()
+    if weight_scale is not None:
+        if weight_scale.device != dev or tuple(weight_scale.shape) not in ((b,), (b, nk)) or not weight_scale.dtype.is_floating_point:
+            raise RuntimeError(f"weight_scale must be a floating-point tensor of shape {(b,)} or [b,C-1]={(b, nk)} on {dev}")
+        weight_scale = weight_scale.to(torch.float32)
+        if weight_scale.dim() == 1:
+            weight_scale = weight_scale[:, None].expand(b, nk)   # one factor per image, for every class
+        weight_scale = weight_scale.contiguous()
+    return dev, b, h, w, nk + 1, vn, hc, weight_scale
+
+
+def vertex_targets_classes_device(labels, hcoords, weight_scale=None, use_motion=False, out=None):
+    """``vertex_targets_device`` for images of several objects: the key-points of a pixel are picked by its label, in ONE launch
+    (include/pvnet_class_targets.h states the definition).  Enqueued on the current stream -- no synchronisation, no host copy.
+
+    :param labels:       [b,h,w] uint8 / bool / int32 / int64 CUDA tensor, any strides: 0 is the background, k + 1 the class of row k
+    :param hcoords:      [b,C-1,vn,3] homogeneous 2-D key-points per class (float64, or float32 which widens exactly); [b,C-1,vn,2] is
+                         taken as hz = 1.  C, the class count with the background, is at most 64 and (C-1) * vn at most 1024
+    :param weight_scale: None (1), [b] (one factor per image) or [b,C-1] (one per image and class)
+    :param use_motion:   the targets are not normalised
+    :param out:          None, or caller-owned float32 ``(vertex [b,2vn,h,w], vertex_weights [b,1,h,w])``, ANY strides; either may be
+                         ``None`` to skip that output
+    :return: ``(vertex, vertex_weights)``.  On the pixels of label k + 1 both equal, bit for bit, what ``vertex_targets_device`` gives
+             for the binary mask ``labels == k + 1`` and ``hcoords[:, k]``; every other pixel (label 0, negative, >= C) has targets
+             +0 and weight 0 -- a selection by label, not a sum over the classes.  With C = 2 on a 0/1 mask that is
+             ``vertex_targets_device`` itself; a mask VALUE of 2 weighs 0 here and 2 there, the one deliberate difference."""
+    lib = load_class_targets_library()
+    dev, b, h, w, class_num, vn, hc, weight_scale = _class_keypoint_inputs(labels, hcoords, weight_scale)
+    with torch.cuda.device(dev):
+        if out is None:
+            vertex = torch.empty((b, 2 * vn, h, w), dtype=torch.float32, device=dev)
+            weights = torch.empty((b, 1, h, w), dtype=torch.float32, device=dev)
+        else:
+            vertex, weights = out
+            for t, shape, name in ((vertex, (b, 2 * vn, h, w), "out[0]"), (weights, (b, 1, h, w), "out[1]")):
+                if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and
+                                          tuple(t.shape) == shape):
+                    raise RuntimeError(f"{name} must be a float32 CUDA tensor of shape {shape} on {dev}")
+            if vertex is None and weights is None:
+                raise RuntimeError("out: at least one of the two outputs must be asked for")
+        if b == 0:
+            return vertex, weights
+        _check(lib.pvnet_vertex_targets_classes(
+            _ptr(labels), _MASK_CODES[labels.dtype], _strides(labels, (0, 1, 2)), _ptr(hc),
+            _ptr(weight_scale), class_num, b, h, w, vn, TARGETS_F_MOTION if use_motion else 0,
+            _ptr(vertex), _opt_strides(vertex, (0, 1, 2, 3)), _ptr(weights), _opt_strides(weights, (0, 2, 3)),
+            _stream(dev)), "pvnet_vertex_targets_classes")
+    return vertex, weights
+
+
+def _ckp_head_inputs(seg_pred, vertex_pred, labels, hcoords, weight_scale, flags, use_motion):
+    """the checks ``head_metrics_from_class_keypoints`` and ``head_grad_from_class_keypoints`` share"""
+    for name, t in (("seg_pred", seg_pred), ("vertex_pred", vertex_pred)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name} must be a CUDA tensor (there is no CPU fallback)")
+    if seg_pred.dim() != 4 or seg_pred.shape[1] < 2:
+        raise RuntimeError(f"seg_pred must be [b,C,h,w] with C >= 2, got {tuple(seg_pred.shape)}")
+    dev, b, h, w, nc, vn, hc, weight_scale = _class_keypoint_inputs(labels, hcoords, weight_scale, class_num=int(seg_pred.shape[1]))
+    if seg_pred.device != dev or vertex_pred.device != dev:
+        raise RuntimeError("seg_pred, vertex_pred, labels and hcoords must live on the same device")
+    if (seg_pred.shape[0], seg_pred.shape[2], seg_pred.shape[3]) != (b, h, w):
+        raise RuntimeError(f"seg_pred must be [b,C,h,w] with (b,h,w)={(b, h, w)}, got {tuple(seg_pred.shape)}")
+    if tuple(vertex_pred.shape) != (b, 2 * vn, h, w):
+        raise RuntimeError(f"vertex_pred must be [b,2vn,h,w]={(b, 2 * vn, h, w)}, got {tuple(vertex_pred.shape)}")
+    if seg_pred.dtype not in _LOGITS_FLAGS or vertex_pred.dtype not in _VERTEX_FLAGS:
+        raise RuntimeError("seg_pred and vertex_pred must be float32, float16 or bfloat16")
+    flags = int(flags) | _LOGITS_FLAGS[seg_pred.dtype] | _VERTEX_FLAGS[vertex_pred.dtype] | (TARGETS_F_MOTION if use_motion else 0)
+    return dev, b, nc, h, w, vn, hc, weight_scale, flags
+
+
+def head_metrics_from_class_keypoints(seg_pred, vertex_pred, labels, hcoords, weight_scale=None, sigma=1.0, use_motion=False, out=None,
+                                      workspace=None, flags=0):
+    """``head_metrics_device`` on the targets of ``vertex_targets_classes_device(labels, hcoords, weight_scale, use_motion)`` without
+    making them.  ``seg_pred`` is [b,C,h,w] and ``hcoords`` [b,C-1,vn,3]: the logits' class count is the targets'.  Same ``(losses,
+    counts, status)``, bit for bit; the other parameters are those of ``head_metrics_device``."""
+    lib = load_class_targets_library()
+    dev, b, nc, h, w, vn, hc, weight_scale, flags = _ckp_head_inputs(seg_pred, vertex_pred, labels, hcoords, weight_scale, flags, use_motion)
+    with torch.cuda.device(dev):
+        losses, counts, status = _metric_outputs(out, b, dev)
+        if b == 0:
+            return losses, counts, status
+        ws = _workspace(workspace, lib.pvnet_head_metrics_ckp_workspace_bytes(b, h, w), dev)
+        _check(lib.pvnet_head_metrics_ckp(
+            _ptr(seg_pred), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            _ptr(vertex_pred), _strides(vertex_pred, (0, 1, 2, 3)),
+            _ptr(hc), _ptr(weight_scale),
+            _ptr(labels), _MASK_CODES[labels.dtype], _strides(labels, (0, 1, 2)),
+            b, h, w, vn, float(sigma), flags,
+            _ptr(losses), _ptr(counts), _ptr(status),
+            _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_head_metrics_ckp")
+    return losses, counts, status
+
+
+def head_grad_from_class_keypoints(seg_pred, vertex_pred, labels, hcoords, upstream, weight_scale=None, sigma=1.0, use_motion=False,
+                                   need=(True, True), out=None, workspace=None, flags=0):
+    """``head_grad_device`` on the targets of ``vertex_targets_classes_device(labels, hcoords, weight_scale, use_motion)`` without
+    making them.  Same ``(grad_seg, grad_vertex, status)``, bit for bit; ``upstream``, ``need``, ``out``, ``workspace`` and ``flags`` as
+    there."""
+    lib = load_class_targets_library()
+    dev, b, nc, h, w, vn, hc, weight_scale, flags = _ckp_head_inputs(seg_pred, vertex_pred, labels, hcoords, weight_scale, flags, use_motion)
+    with torch.cuda.device(dev):
+        grad_seg, grad_vertex, status = _grad_outputs(seg_pred, vertex_pred, upstream, need, out, b, dev)
+        if b == 0:
+            return grad_seg, grad_vertex, status
+        ws = _workspace(workspace, lib.pvnet_head_grad_ckp_workspace_bytes(b, h, w), dev)
+        _check(lib.pvnet_head_grad_ckp(
+            _ptr(seg_pred), _strides(seg_pred, (0, 1, 2, 3)), nc,
+            _ptr(vertex_pred), _strides(vertex_pred, (0, 1, 2, 3)),
+            _ptr(hc), _ptr(weight_scale),
+            _ptr(labels), _MASK_CODES[labels.dtype], _strides(labels, (0, 1, 2)),
+            b, h, w, vn, float(sigma), flags, _ptr(upstream),
+            _ptr(grad_seg), _opt_strides(grad_seg, (0, 1, 2, 3)), _ptr(grad_vertex), _opt_strides(grad_vertex, (0, 1, 2, 3)),
+            _ptr(status), _ptr(ws), _nbytes(ws), _stream(dev)), "pvnet_head_grad_ckp")
+    return grad_seg, grad_vertex, status
+
+
 def _upstream(grad_seg_loss, grad_vertex_loss, b, dev):
     """[b,2] float64 from the two incoming gradients of a backward; a missing one is zeros"""
     cols = [torch.zeros((b,), dtype=torch.float64, device=dev) if g is None else g.to(torch.float64) for g in (grad_seg_loss, grad_vertex_loss)]
     return torch.stack(cols, 1)
 
 
+_CLASS_KEYPOINTS = 2   # ``keypoints`` of ``_HeadLossFn``: the third target source (False: loaded targets, True: key-points per image)
+
+
 class _HeadLossFn(torch.autograd.Function):
-    """The four forms of ``HeadLoss``.  ``apply(pred, pred2, seg_dim, mask, source, source2, sigma, use_motion, keypoints)``:
+    """The six forms of ``HeadLoss``.  ``apply(pred, pred2, seg_dim, mask, source, source2, sigma, use_motion, keypoints)``:
 
     * the predictions are ``(pred, pred2) = (seg_pred, vertex_pred)`` with ``seg_dim`` None, or the two channel slices of the ONE tensor
       ``pred`` at ``seg_dim`` (``pred2`` None): the backward then writes both halves into one gradient tensor of its shape;
-    * the targets are ``(source, source2) = (vertex, vertex_weights)``, or with ``keypoints`` ``(hcoords, weight_scale or None)``.
+    * the targets are ``(source, source2) = (vertex, vertex_weights)``, or with ``keypoints`` ``(hcoords, weight_scale or None)``:
+      ``True`` for one set per image, ``_CLASS_KEYPOINTS`` for one per class, picked by the label (``mask`` is a label image then).
 
-    forward: ``head_metrics_device`` / ``head_metrics_from_keypoints``; backward: ONE ``head_grad_device`` /
-    ``head_grad_from_keypoints`` on the saved inputs -- with key-points those are the predictions, the mask and the key-points only."""
+    forward: ``head_metrics_device`` / ``head_metrics_from_keypoints`` / ``head_metrics_from_class_keypoints``; backward: ONE
+    ``head_grad_device`` / ``head_grad_from_keypoints`` / ``head_grad_from_class_keypoints`` on the saved inputs -- with key-points
+    those are the predictions, the mask and the key-points only."""
 
     @staticmethod
     def _predictions(pred, pred2, seg_dim):
@@ -348,7 +503,10 @@ class _HeadLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, pred2, seg_dim, mask, source, source2, sigma, use_motion, keypoints):
         seg_pred, vertex_pred = _HeadLossFn._predictions(pred, pred2, seg_dim)
-        if keypoints:
+        if keypoints == _CLASS_KEYPOINTS:
+            losses, _, _ = head_metrics_from_class_keypoints(seg_pred, vertex_pred, mask, source, source2, sigma=sigma,
+                                                             use_motion=use_motion)
+        elif keypoints:
             losses, _, _ = head_metrics_from_keypoints(seg_pred, vertex_pred, mask, source, source2, sigma=sigma, use_motion=use_motion)
         else:
             losses, _, _ = head_metrics_device(seg_pred, vertex_pred, mask, source, source2, sigma=sigma)
@@ -372,7 +530,10 @@ class _HeadLossFn(torch.autograd.Function):
         upstream = _upstream(g_seg, g_vertex, pred.shape[0], pred.device)
         grad = torch.empty_like(pred) if packed else None
         out = _HeadLossFn._predictions(grad, None, ctx.seg_dim) if packed else None
-        if ctx.keypoints:
+        if ctx.keypoints == _CLASS_KEYPOINTS:
+            grad_seg, grad_vertex, _ = head_grad_from_class_keypoints(seg_pred, vertex_pred, mask, source, upstream, source2,
+                                                                      sigma=ctx.sigma, use_motion=ctx.use_motion, need=need, out=out)
+        elif ctx.keypoints:
             grad_seg, grad_vertex, _ = head_grad_from_keypoints(seg_pred, vertex_pred, mask, source, upstream, source2, sigma=ctx.sigma,
                                                                 use_motion=ctx.use_motion, need=need, out=out)
         else:
@@ -398,7 +559,13 @@ class HeadLoss(torch.nn.Module):
     other key-point entry).  Forward and backward compute a pixel's target in registers; the autograd functions save the predictions,
     the mask and the key-points only.
     Same values and gradients as the two forms above on ``vertex_targets_device(mask, hcoords, weight_scale)``, bit for bit; no
-    gradient for the mask, the key-points or the scale."""
+    gradient for the mask, the key-points or the scale.
+
+    ``from_class_keypoints(seg_pred, vertex_pred, labels, hcoords, weight_scale=None, use_motion=False)`` and
+    ``packed_from_class_keypoints(head_out, seg_dim, labels, hcoords, ...)`` are the same for images of several objects: ``labels`` is a
+    label image, ``hcoords [b,C-1,vn,3]`` holds the key-points of class k + 1 in row k and ``weight_scale`` is None, [b] or [b,C-1]
+    (``vertex_targets_classes_device`` states the definition).  They equal the first two forms on its output bit for bit and save the
+    predictions, the labels and the key-points only."""
 
     def __init__(self, sigma=1.0):
         super().__init__()
@@ -423,6 +590,14 @@ class HeadLoss(torch.nn.Module):
     def packed_from_keypoints(self, head_out, seg_dim, mask, hcoords, weight_scale=None, use_motion=False):
         return _HeadLossFn.apply(head_out, None, self._seg_dim(head_out, seg_dim), mask, hcoords, weight_scale, self.sigma,
                                  bool(use_motion), True)
+
+    def from_class_keypoints(self, seg_pred, vertex_pred, labels, hcoords, weight_scale=None, use_motion=False):
+        return _HeadLossFn.apply(seg_pred, vertex_pred, None, labels, hcoords, weight_scale, self.sigma, bool(use_motion),
+                                 _CLASS_KEYPOINTS)
+
+    def packed_from_class_keypoints(self, head_out, seg_dim, labels, hcoords, weight_scale=None, use_motion=False):
+        return _HeadLossFn.apply(head_out, None, self._seg_dim(head_out, seg_dim), labels, hcoords, weight_scale, self.sigma,
+                                 bool(use_motion), _CLASS_KEYPOINTS)
 
 
 class ValStep(object):
