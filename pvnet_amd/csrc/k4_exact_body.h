@@ -392,20 +392,23 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
         const int left = (it.tpad - it.cg * npx + 31) >> 5;
         const int nti = left < ntiles ? left : ntiles;
         bf16x8 Aa = __builtin_bit_cast(bf16x8, lbase[0]), Ab = __builtin_bit_cast(bf16x8, lbase[64]);
-        // FOLD: before the first step nothing is due -- every step is a next(), the first one "closes" an idle cell into the
-        // zero flag word of the last hypothesis tile
+        // FOLD: a step closes the cell of the step before it.  Before an item's first step nothing is due: that step (wave-uniform
+        // branch) opens its cell with first().  (Until round 13 it was a next() on an idle cell -- ten moves and the 14 operations of a
+        // close that added no vote and shifted a zero into the still zero flag word of the last hypothesis tile, per item and wave.)
+        // The two-accumulator variant keeps the idle cell.
         OpenCell oc;
-        oc.idle();
+        if (NACC != 1) oc.idle();
         if (NACC == 1) {
-            // one pixel tile against the wave's MH hypothesis tiles
-            auto tile_steps = [&](const bf16x8& Ta, const bf16x8& Tb) __attribute__((always_inline)) {
+            // one pixel tile against the wave's MH hypothesis tiles; item_start: the item's first pixel tile
+            auto tile_steps = [&](const bf16x8& Ta, const bf16x8& Tb, const bool item_start) __attribute__((always_inline)) {
 #pragma unroll
                 for (int t = 0; t < MH; ++t) {
                     const f32x16 va = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ta, B[t], zero, 0, 0, 0);
                     const f32x16 vb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Tb, B[t], zero, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     if (FOLD) {
-                        oc.next(cnt[(t + MH - 1) % MH], flg[(t + MH - 1) % MH], va, vb);
+                        if (t == 0 && item_start) oc.first(va, vb);
+                        else oc.next(cnt[(t + MH - 1) % MH], flg[(t + MH - 1) % MH], va, vb);
                     } else {
                         asm volatile("s_nop 11");   // (the votes are inline asm: the wait states are ours, tools/check_mfma_hazard.py)
                         __builtin_amdgcn_sched_barrier(0);
@@ -422,12 +425,12 @@ __device__ __forceinline__ void score_exact_body(VoteParams P) {
                 const int n1 = tile + 1 < nti ? tile + 1 : tile;
                 const bf16x8 Na = __builtin_bit_cast(bf16x8, lbase[n1 * TILE_U4]);
                 const bf16x8 Nb = __builtin_bit_cast(bf16x8, lbase[n1 * TILE_U4 + 64]);
-                tile_steps(Aa, Ab);
+                tile_steps(Aa, Ab, tile == 0);
                 if (tile + 1 >= nti) break;   // (wave-uniform)
                 const int n2 = tile + 2 < nti ? tile + 2 : tile + 1;
                 Aa = __builtin_bit_cast(bf16x8, lbase[n2 * TILE_U4]);
                 Ab = __builtin_bit_cast(bf16x8, lbase[n2 * TILE_U4 + 64]);
-                tile_steps(Na, Nb);
+                tile_steps(Na, Nb, false);
             }
         } else {
         f32x16 va = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Aa, B[0], zero, 0, 0, 0);

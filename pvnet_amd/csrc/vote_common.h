@@ -355,8 +355,6 @@ __device__ __forceinline__ void b_col_exact(float hxo, float hyo, float rho, flo
 __device__ __forceinline__ void a_rows_exact(float4 q, float tau, float ox, float oy, float rho, uint4& alo, uint4& ahi,
                                              uint4& blo, uint4& bhi, float& mu) {
     const uint32_t never = 0xC080u;  // bf16 -4 in the spare slot of the dt' row: x = -4
-    alo = ahi = blo = bhi = make_uint4(0u, 0u, 0u, 0u);
-    mu = 1.f;
     const float m = fmaxf(fabsf(q.z), fabsf(q.w));
     const uint32_t e = (__float_as_uint(m) >> 23) & 0xFFu;
     const bool finite = fabsf(q.z) <= 3.4028235e38f && fabsf(q.w) <= 3.4028235e38f;  // false for NaN and Inf
@@ -370,11 +368,11 @@ __device__ __forceinline__ void a_rows_exact(float4 q, float tau, float ox, floa
         asm volatile("" : "+v"(nz));
         if (near_gate) dead = norm1_literal(nz, q.w) <= kF1e6;
     }
-    if (dead) {
-        ahi.w = pk(0u, never);  // dt' = -4, cr' = 0: x = -4, no vote and no flag
-        return;
-    }
-    if (e >= 127u + 61u) return;    // finite but >= 2^61: the reference's nx * nx may overflow -- zero rows: decided literally
+    // a dead row: dt' = -4, cr' = 0 -- x = -4, no vote and no flag.  A direction that is finite but >= 2^61 (the reference's nx * nx
+    // may overflow): zero rows -- decided literally.  Both are made by selecting the six INPUTS of the two a_row() below (round 13:
+    // the parts of +0 are zero words) and one select on the spare-slot word, not by selecting the ten distinct output words; what the
+    // arithmetic in between makes of a NaN, an Inf or a dead direction is never looked at.
+    const bool live = !dead && e < 127u + 61u;
     const float pre = __uint_as_float((254u - e) << 23);       // 2^(127 - e): max(|ux|, |uy|) -> [1, 2)   (e = 0: denormal, 2^127)
     const float u1x = q.z * pre, u1y = q.w * pre;               // exact
     const float g = __builtin_amdgcn_rsqf(fmaf(u1y, u1y, u1x * u1x));
@@ -383,13 +381,14 @@ __device__ __forceinline__ void a_rows_exact(float4 q, float tau, float ox, floa
     const float sig = rho * __builtin_amdgcn_rcpf(rho + r);
     const float gs = g * sig * 0.9997f;                                       //  an upper bound is all that is needed)
     // |M| = |u1| gs <= rho / (rho + r)  (and < sig as computed: the 3e-4 of slack is far above the roundings of g, sig and M)
-    mu = sig;
+    mu = live ? sig : 1.f;
     const float Mx = u1x * gs, My = u1y * gs;
     const float Tx = tau * Mx, Ty = tau * My;
     const float Ec = fmaf(cx, My, -cy * Mx);                    // cr = hx My - hy Mx - Ec
     const float Ed = fmaf(cx, Tx, cy * Ty);                     // dt = hx Tx + hy Ty - Ed
-    a_row(Tx, Ty, -Ed, alo, ahi);                               // dt' rows
-    a_row(My, -Mx, -Ec, blo, bhi);                              // cr' rows
+    a_row(live ? Tx : 0.f, live ? Ty : 0.f, live ? -Ed : 0.f, alo, ahi);   // dt' rows
+    a_row(live ? My : 0.f, live ? -Mx : 0.f, live ? -Ec : 0.f, blo, bhi);  // cr' rows
+    ahi.w = dead ? pk(0u, never) : ahi.w;
 }
 
 // v of lane (l ^ M), M a power of two below 64, without the LDS crossbar's address operand: DPP for 1, 2 and 8 (quad_perm, row_ror:8),
